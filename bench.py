@@ -15,7 +15,10 @@ N>1 (torchrun, one rank per GPU): molecules are sharded round-robin (global read
 RNG keyed by g), per-GPU batch fixed (weak scaling); every step ends with the RCCL gather of the per-rank record
 streams to rank 0 and the device-side interleave into global read order (the FASTQ-order exchange step).
 
-Prints ONE JSON line on rank 0 (contract in the round instructions), including
+Prints ONE JSON line on rank 0: `metric`, `value` (reads/s of the timed steps), `unit`, `higher_is_better`, `dtype`, `ms_per_step`
+(wall time of one timed step), Gbases/s and the configuration.  A plain run does only that: set-up, warm-up, the --steps timed steps,
+the line.  `--dump-outputs DIR` also writes what the last timed step handed its caller (see dump_outputs).  Everything else runs
+with `--full` only, and adds to the line
   `roofline`      dominant kernel = the larger of k_loop (error loop, one lane per read; with k_loopw, its wave-per-read form for the late rounds) and k_alnf (alignment windows
                   decoded and aligned bit-parallel, one lane per alignment; all its instantiations: 14-row pass, full-width redo and small rounds, q-score round) by EXCLUSIVE time: after the timed steps one
                   more step runs on one context alone (nothing else on the GPU) with HIP events around every launch on its stream;
@@ -25,7 +28,9 @@ Prints ONE JSON line on rank 0 (contract in the round instructions), including
   `cpu_baseline`  the CPU oracle (oracle/tksm_oracle.c, -O3 -march=native, kind "port") on a bounded sample of the same workload,
                   all host cores;
   `e2e_reads_per_s`  (N = 1) the `tksm sequence` binary on files (temporary directory): MDF text in, FASTQ file out, wall time of the whole process --
-                  PCIe and host I/O inclusive, never `value`.
+                  PCIe and host I/O inclusive, never `value`;
+  `side_legs`     (N = 1, bulk) short driver-timed legs on the scRNA-like, PCR-like and lognormal-length workloads;
+  `order_check`   (N > 1 or the forced exchange) the FASTQ order check of BASELINE config 4.
 """
 import argparse
 import json
@@ -38,6 +43,50 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0      # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_SAMPLE_READS = 2048    # --dump-outputs: records written byte for byte, a fixed seeded choice of the step's reads ...
+DUMP_SAMPLE_BYTES = 8 << 20     # ... holding at most this many record bytes (32 MiB as float32)
+DUMP_MAX_LENGTHS = 1 << 21      # record lengths of every read of the step, or of an even stride of at most this many (16 MiB)
+DUMP_CHUNK = 1 << 20            # the whole record stream folded into two sums per chunk of this many bytes
+
+
+def dump_outputs(d, c, r, dev):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step -- the FASTQ record stream of one batch and
+    its offsets (context `c`, result `r`) -- as float arrays, so that two builds run with the same arguments compare output for output:
+      records_sample.npy          the bytes of a seeded sample of records, concatenated in read order (float32)
+      records_sample_index.npy    their read indices in the step; records_sample_lengths.npy their lengths (float64)
+      record_lengths.npy          the length of every record (or of reads 0, s, 2s, ... when the step has more than DUMP_MAX_LENGTHS)
+      records_fold.npy            per DUMP_CHUNK bytes of the whole stream: sum of the bytes, and sum of byte x (position mod 251 + 1)
+      step_totals.npy             reads, record bytes, bases in, bases out of the step"""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    n, nb = int(r.n_reads), int(r.records_bytes)
+    off_t = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    r.copy_to_device(None, off_t.data_ptr())
+    buf = next((t for t in c.out_ts if t.data_ptr() == r.records_ptr), None)
+    if buf is None:                       # (records in the context's own buffer: copy them out)
+        buf = torch.empty(nb, dtype=torch.uint8, device=dev)
+        r.copy_to_device(buf.data_ptr(), None)
+    c.seqr.synchronize()
+    rec = buf[:nb]
+    w = torch.arange(DUMP_CHUNK, dtype=torch.int64, device=dev) % 251 + 1
+    fold = []
+    for lo in range(0, nb, 64 * DUMP_CHUNK):
+        blk = rec[lo:lo + 64 * DUMP_CHUNK].to(torch.int64)
+        blk = torch.nn.functional.pad(blk, (0, -blk.numel() % DUMP_CHUNK)).view(-1, DUMP_CHUNK)
+        fold.append(torch.stack((blk.sum(1), (blk * w).sum(1)), 1))
+    fold = torch.cat(fold).cpu().numpy() if fold else np.zeros((0, 2), np.int64)
+    offs = off_t.cpu().numpy()
+    lens = np.diff(offs)
+    idx = np.sort(np.random.RandomState(5).choice(n, min(n, DUMP_SAMPLE_READS), replace=False))
+    idx = idx[np.cumsum(lens[idx]) <= DUMP_SAMPLE_BYTES]
+    sample = torch.cat([rec[int(offs[i]):int(offs[i + 1])] for i in idx]).cpu().numpy() if len(idx) else np.zeros(0, np.uint8)
+    stride = -(-n // DUMP_MAX_LENGTHS)
+    arrays = {"records_sample": sample.astype(np.float32), "records_sample_index": idx.astype(np.float64),
+              "records_sample_lengths": lens[idx].astype(np.float64), "record_lengths": lens[::stride].astype(np.float64),
+              "records_fold": fold.astype(np.float64),
+              "step_totals": np.array([n, nb, r.bases_in, r.bases_out], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def cpu_baseline_worker(args):
@@ -232,7 +281,14 @@ def main():
                     help="N > 1 (or the forced exchange): after the timed steps every rank runs its round-robin shard of ONE common set of "
                          "N x this many molecules through the same exchange, and rank 0 compares the ordered stream with its own "
                          "single-GPU run of the whole set (BASELINE config 4's FASTQ order check); 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: CPU baseline, exclusive per-kernel time and roofline, "
+                         "side legs, end-to-end CLI leg, order check (each can still be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started as `python bench.py --gpus N`: this process becomes the launcher and never touches a GPU -- the N ranks are CHILD
@@ -248,7 +304,7 @@ def main():
     json_fd = os.dup(1)
     os.dup2(2, 1)
     cpu_base = None
-    if world == 1 and not args.no_cpu_baseline and not args.perfect:
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.perfect:
         # oracle leg first, before this process touches the GPU (it forks worker processes)
         cores = host_cores()
         n_cpu = args.cpu_sample or max(64, int(cores * 20.0 / 0.0023 * (1000.0 / args.mean_len)))
@@ -503,15 +559,19 @@ def main():
     bases_in = sum(r.bases_in for r in results)
     bases_out = sum(r.bases_out for r in results)
     overlapped = {"k_loop": float(np.mean([r.kernel_ms[5] for r in results])), "k_alnf": float(np.mean([r.kernel_ms[6] for r in results]))}
-    # exclusive per-kernel time: one more step on one context with the GPU to itself (untimed for `value`)
-    fence()
-    rx = run_step(ctxs[0], args.warmup * n_ctx + args.steps)
-    ctxs[0].seqr.synchronize()
-    fence()
-    exclusive = {"k_loop": float(rx.kernel_ms[5]), "k_alnf": float(rx.kernel_ms[6]),
-                 "simulate_stage_total": float(rx.kernel_ms[1]), "all_kernels": float(rx.kernel_ms[4])}
+    if args.dump_outputs and rank == 0:
+        # (before anything else runs on the contexts: the last step's records are still in its context's output buffer)
+        dump_outputs(args.dump_outputs, ctxs[(args.steps - 1) % n_ctx], results[-1], dev)
+    if args.full:
+        # exclusive per-kernel time: one more step on one context with the GPU to itself (untimed for `value`)
+        fence()
+        rx = run_step(ctxs[0], args.warmup * n_ctx + args.steps)
+        ctxs[0].seqr.synchronize()
+        fence()
+        exclusive = {"k_loop": float(rx.kernel_ms[5]), "k_alnf": float(rx.kernel_ms[6]),
+                     "simulate_stage_total": float(rx.kernel_ms[1]), "all_kernels": float(rx.kernel_ms[4])}
     order_check = None
-    if exchange_on and args.order_check_reads > 0 and not args.perfect:
+    if args.full and exchange_on and args.order_check_reads > 0 and not args.perfect:
         order_check = run_order_check()
     if exchange_on:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -531,28 +591,29 @@ def main():
         return
     reads = args.batch * world * args.steps
     value = reads / elapsed
-    alg = synthetic.algorithmic_bytes(m, rec_bytes / args.steps)
-    if args.perfect:
-        # --perfect: one kernel writes the records straight from the packed reference (timed as the emit stage)
-        dom, dom_ms = "k_perfect", float(rx.kernel_ms[3])
-        overlapped = {"k_perfect": float(np.mean([r.kernel_ms[3] for r in results]))}
-        exclusive = {"k_perfect": dom_ms, "all_kernels": float(rx.kernel_ms[4])}
-    elif exclusive["k_loop"] + exclusive["k_alnf"] == 0.0:
-        dom, dom_ms = "k_simulate", exclusive["simulate_stage_total"]
-    else:
-        dom = max(("k_loop", "k_alnf"), key=lambda k: exclusive[k])
-        dom_ms = exclusive[dom]
-    achieved = alg / (dom_ms * 1e-3) / 1e9
-    traffic, traffic_source = None, None
-    tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            if tj.get("batch") == args.batch and tj.get("kind", "bulk") == args.kind and not args.perfect:
-                traffic = tj.get("hbm_bytes_per_step", {}).get(dom)
-                traffic_source = f"profiles/{tj.get('profile', 'traffic_latest.json')} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command; not measured in this run)"
-        except Exception:
-            traffic = None
+    if args.full:
+        alg = synthetic.algorithmic_bytes(m, rec_bytes / args.steps)
+        if args.perfect:
+            # --perfect: one kernel writes the records straight from the packed reference (timed as the emit stage)
+            dom, dom_ms = "k_perfect", float(rx.kernel_ms[3])
+            overlapped = {"k_perfect": float(np.mean([r.kernel_ms[3] for r in results]))}
+            exclusive = {"k_perfect": dom_ms, "all_kernels": float(rx.kernel_ms[4])}
+        elif exclusive["k_loop"] + exclusive["k_alnf"] == 0.0:
+            dom, dom_ms = "k_simulate", exclusive["simulate_stage_total"]
+        else:
+            dom = max(("k_loop", "k_alnf"), key=lambda k: exclusive[k])
+            dom_ms = exclusive[dom]
+        achieved = alg / (dom_ms * 1e-3) / 1e9
+        traffic, traffic_source = None, None
+        tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                if tj.get("batch") == args.batch and tj.get("kind", "bulk") == args.kind and not args.perfect:
+                    traffic = tj.get("hbm_bytes_per_step", {}).get(dom)
+                    traffic_source = f"profiles/{tj.get('profile', 'traffic_latest.json')} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command; not measured in this run)"
+            except Exception:
+                traffic = None
     kind_name = {"bulk": "Bulk", "scrna": "scRNA-like (barcode, UMI, polyA literals)", "pcr": "PCR-amplified (substitution-heavy)"}[args.kind]
     out = {
         "metric": "sequenced reads/s", "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps,
@@ -568,14 +629,15 @@ def main():
                    **({"rehearsal": "every rank on GPU 0, collectives over gloo on host copies: not a measurement"} if rehearse else {})},
         "gbases_per_s": bases_in_all / elapsed / 1e9,
         "gbases_out_per_s": bases_out_all / elapsed / 1e9,
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source, "kernel": dom,
-                     "kernel_ms": dom_ms, "kernel_ms_is": "exclusive: summed launch durations of the kernel in one step run alone on the GPU",
-                     "algorithmic_bytes_per_launch": alg,
-                     "exclusive_ms_per_step": exclusive, "overlapped_ms_per_step": overlapped,
-                     "overlapped_all_kernels_ms": float(np.mean(tot_ms)), "overlapped_simulate_stage_ms": float(np.mean(sim_ms))},
     }
-    if world == 1 and not exchange_on and not args.no_side_legs and not args.perfect and args.kind == "bulk" and not args.lognormal_sigma:
+    if args.full:
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source, "kernel": dom,
+                           "kernel_ms": dom_ms, "kernel_ms_is": "exclusive: summed launch durations of the kernel in one step run alone on the GPU",
+                           "algorithmic_bytes_per_launch": alg,
+                           "exclusive_ms_per_step": exclusive, "overlapped_ms_per_step": overlapped,
+                           "overlapped_all_kernels_ms": float(np.mean(tot_ms)), "overlapped_simulate_stage_ms": float(np.mean(sim_ms))}
+    if args.full and world == 1 and not exchange_on and not args.no_side_legs and not args.perfect and args.kind == "bulk" and not args.lognormal_sigma:
         # short driver-timed legs on the other workloads (same contexts, models and genome; 1 warm-up round + 3 timed steps each;
         # never `value`): BASELINE config 3's scRNA-like molecules, config 5's substitution-heavy molecules, transcript-like lengths
         side = {}
@@ -611,7 +673,7 @@ def main():
             except Exception as e:                   # a side leg never costs the bench line
                 side[name] = {"reads_per_s": None, "error": repr(e)[:300]}
         out["side_legs"] = side
-    if world == 1 and not args.no_e2e and not args.perfect and args.kind == "bulk":
+    if args.full and world == 1 and not args.no_e2e and not args.perfect and args.kind == "bulk":
         # the CLI is another process on the same GPU: release this one's contexts and buffers first
         if xseq is not None:
             xseq.close()
@@ -628,7 +690,8 @@ def main():
             e2e = {"reads_per_s": None, "error": repr(e)[:300]}
         out["e2e_reads_per_s"] = e2e["reads_per_s"]
         out["e2e"] = e2e
-    out["cpu_baseline"] = cpu_base
+    if args.full:
+        out["cpu_baseline"] = cpu_base
     if order_check is not None:
         out["order_check"] = order_check
     sys.stdout.flush()

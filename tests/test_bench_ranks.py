@@ -59,8 +59,9 @@ def test_take_rebuilds_a_shard_of_a_molecule_set(kind):
         assert synthetic.mdf_text(synthetic.take(m, sel), names) == "".join(mols[i] for i in sel)
 
 
-SMALL = ["--batch", "49152", "--steps", "4", "--warmup", "1", "--genome-contigs", "4", "--contig-mb", "4", "--no-cpu-baseline", "--no-e2e",
-         "--no-side-legs", "--order-check-reads", "20000"]
+# --full: the order check runs with it
+SMALL = ["--batch", "49152", "--steps", "4", "--warmup", "1", "--genome-contigs", "4", "--contig-mb", "4", "--full", "--no-cpu-baseline",
+         "--no-e2e", "--no-side-legs", "--order-check-reads", "20000"]
 
 
 @pytest.mark.gpu

@@ -5,7 +5,7 @@ export GPU_MAX_HW_QUEUES=16
 K=$1; N=$2; shift; shift
 out=gpurun_out/exp_ab_kind.log
 : > $out
-B="python bench.py --kind $K --steps 12 --warmup 2 --no-cpu-baseline --no-e2e --no-side-legs"
+B="python bench.py --full --kind $K --steps 12 --warmup 2 --no-cpu-baseline --no-e2e --no-side-legs"
 one() { echo -n "$K $1: " >> $out; TKSMSEQ_LIB=$1 $B 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.readline())

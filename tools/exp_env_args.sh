@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 export GPU_MAX_HW_QUEUES=16
 out=gpurun_out/exp_env.log
 : > $out
-B="python bench.py --steps 9 --warmup 2 --no-cpu-baseline --no-e2e --no-side-legs $BENCH_ARGS"
+B="python bench.py --full --steps 9 --warmup 2 --no-cpu-baseline --no-e2e --no-side-legs $BENCH_ARGS"
 for e in "$@"; do
   echo -n "$e: " >> $out
   env $e $B 2>/dev/null | python -c "

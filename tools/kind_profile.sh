@@ -4,7 +4,7 @@ kind=$1; shift
 R=$PWD; out=$R/gpurun_out/kind_$kind; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 export GPU_MAX_HW_QUEUES=16
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python $R/bench.py --kind $kind --no-cpu-baseline --no-e2e --no-side-legs --pipeline 1 --steps 4 "$@" > $out/bench.json 2> $out/err.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python $R/bench.py --full --kind $kind --no-cpu-baseline --no-e2e --no-side-legs --pipeline 1 --steps 4 "$@" > $out/bench.json 2> $out/err.log
 cp $out/stats/*/*kernel_stats.csv $out/kernel_stats.csv; rm -rf $out/stats
 python3 - <<PY
 import csv,json

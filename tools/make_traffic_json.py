@@ -28,7 +28,7 @@ fe, wr = sums("fetch", "FETCH_SIZE"), sums("write", "WRITE_SIZE")
 fc = {k: v * FETCH_FACTOR.get(k, 1.0) for k, v in fe.items()}
 print(json.dumps({
     "batch": batch, "kind": "bulk", "profile": f"{tag}_hbm_traffic.json",
-    "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), python bench.py --steps 3 --warmup 1 "
+    "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), python bench.py --full --steps 3 --warmup 1 "
               f"--no-cpu-baseline --no-e2e (3 contexts in flight: 3 warm-up + 3 timed steps + the exclusive step); per-kernel sums divided by {nsteps} steps",
     "units": f"bytes per step ({batch:,} reads); the counters report KiB",
     "calibration": "fetch_bytes_per_step = FETCH_SIZE x the per-pattern factor of profiles/r02_fetch_calibration.json (see this tool's docstring); "
