@@ -331,6 +331,68 @@ typedef struct {
 } tksmseq_trc_params;
 int tksmseq_truncate(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_trc_params* params, tksmseq_batch** out);
 
+/* ---- segment edits: polyA, tag, scb, flip (the single-cell route of the reference README: plA -> Tag -> SCB -> Tag -> PCR -> Flp ->
+ * Tag -> Seq) ------------------------------------------------------------------------------------------------------------------
+ * Each takes a batch and returns a new one on the device, like tksmseq_truncate: molecules depth-unrolled (id_0, id_1, ...), written in
+ * input order with depth 1; randomness depends only on (seed, first_molecule_index + i); comments carried through (re-serialised
+ * like dump_comment), none with TKSMSEQ_MOL_NO_COMMENTS.  A new segment is a literal (contig name = its sequence) on the plus strand;
+ * the output literal table is the input's followed by the new entries (TKSMSEQ_ELIMIT at 2^31 entries).
+ *
+ * tksmseq_polya replaces add_polyA / polya_transformer (src/polyA.cpp:133-148; module src/polyA.cpp:17-237): appends "A" x L,
+ * L = the draw truncated toward zero, clamped to [min_length, max_length] (clamped in double first: huge and NaN draws are defined);
+ * L = 0 appends nothing.  Gamma / Weibull: a = shape, b = scale (std:: parameterisation); Poisson: a = lambda; normal: a = mu,
+ * b = sigma.  Exact samplers.  Parameters for which the std:: distribution is undefined (a, b, lambda or
+ * sigma <= 0, non-finite values) are TKSMSEQ_EINVAL -- the reference's behaviour there is undefined; max_length above 2^20 is
+ * TKSMSEQ_ELIMIT. */
+#define TKSMSEQ_PLA_GAMMA 0
+#define TKSMSEQ_PLA_POISSON 1
+#define TKSMSEQ_PLA_WEIBULL 2
+#define TKSMSEQ_PLA_NORMAL 3
+typedef struct {
+    uint64_t seed;
+    uint64_t first_molecule_index;   /* index of the batch's first molecule in the whole input (RNG key) */
+    int32_t dist;                    /* TKSMSEQ_PLA_* (--gamma / --poisson / --weibull / --normal) */
+    int32_t flags;                   /* TKSMSEQ_MOL_NO_COMMENTS or 0 */
+    double a, b;                     /* the distribution's parameters (b unused for Poisson) */
+    int32_t min_length, max_length;  /* --min-length (0), --max-length (5000) */
+} tksmseq_polya_params;
+int tksmseq_polya(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_polya_params* params, tksmseq_batch** out);
+
+/* tksmseq_tag replaces TAG_module::run (src/tag.cpp:70-113): prepends a tag drawn from format5 and appends one drawn from format3,
+ * each letter uniform over fmt2seq's IUPAC choices (src/util.h:53-92); letters outside that table (lower case included) add nothing,
+ * an empty tag adds no segment.  The formats are taken as they are: the CLI's digit rule ("10" -> "NNNNNNNNNN", src/tag.cpp:84-91)
+ * is applied by the caller.  A format without ambiguous letters (an adapter) is one literal shared by every molecule. */
+typedef struct {
+    uint64_t seed;
+    uint64_t first_molecule_index;
+    const char* format5;             /* -5/--format5, NULL or "" for none */
+    const char* format3;             /* -3/--format3 */
+    int32_t flags;                   /* TKSMSEQ_MOL_NO_COMMENTS or 0 */
+    int32_t reserved;
+} tksmseq_tag_params;
+int tksmseq_tag(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_tag_params* params, tksmseq_batch** out);
+
+/* tksmseq_scb replaces SingleCellBarcoder_module::run (src/scb.cpp:57-80): appends the first value of the CB comment (unless it is
+ * ".") as a literal segment and drops the CB key unless keep_meta_barcodes.  A molecule without CB (the reference's meta.at throws)
+ * and a batch without comments are TKSMSEQ_EINVAL.  No randomness. */
+typedef struct {
+    int32_t keep_meta_barcodes;      /* --keep-meta-barcodes */
+    int32_t flags;                   /* TKSMSEQ_MOL_NO_COMMENTS or 0 (CB is still read from the input's comments) */
+} tksmseq_scb_params;
+int tksmseq_scb(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_scb_params* params, tksmseq_batch** out);
+
+/* tksmseq_flip replaces StrandMan_module (src/strand_man.cpp:37-46, flip_molecule src/interval.h:908-920): molecule i is flipped --
+ * segment order reversed, every strand toggled, substitutions and comments kept -- when u01(Philox(seed, i, 29)) < flip_probability.
+ * Any probability is accepted (the reference only logs a value outside [0, 1]): <= 0 flips nothing, >= 1 everything. */
+typedef struct {
+    uint64_t seed;
+    uint64_t first_molecule_index;
+    double flip_probability;         /* -p/--flip-probability */
+    int32_t flags;                   /* TKSMSEQ_MOL_NO_COMMENTS or 0 */
+    int32_t reserved;
+} tksmseq_flip_params;
+int tksmseq_flip(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_flip_params* params, tksmseq_batch** out);
+
 /* The batch as MDF text, the way molecule_descriptor::operator<< writes it (src/interval.h:898-905): "+id<TAB>depth<TAB>comment",
  * then "chr<TAB>start<TAB>end<TAB>strand<TAB>pos<base>,..." per segment; depth 1 per molecule; comments re-serialised key-sorted
  * like dump_comment (:880-890).  *text is malloc'ed: release with tksmseq_text_free. */
@@ -341,6 +403,13 @@ void tksmseq_text_free(char* text);
  * top of the functions above: same flags, MDF file in, MDF file out; argv[0] is the module name. */
 int tksmseq_pcr_main(int argc, char** argv);
 int tksmseq_truncate_main(int argc, char** argv);
+/* `tksm polyA`, `tksm tag`, `tksm scb`, `tksm flip` (PolyA_module src/polyA.cpp:17-237, TAG_module src/tag.cpp:16-129, SingleCellBarcoder_module
+ * src/scb.cpp:14-92, StrandMan_module src/strand_man.cpp:20-124): the reference's flags and validation messages, MDF file in, MDF file out,
+ * streamed in batches of --batch-bytes over --devices like `tksm truncate`. */
+int tksmseq_polya_main(int argc, char** argv);
+int tksmseq_tag_main(int argc, char** argv);
+int tksmseq_scb_main(int argc, char** argv);
+int tksmseq_flip_main(int argc, char** argv);
 int tksmseq_sequence_main(int argc, char** argv);
 
 #ifdef __cplusplus

@@ -51,6 +51,29 @@ class TrcParams(C.Structure):
 
 TRC_NORMAL, TRC_LOGNORMAL, TRC_KDE = 0, 1, 2
 
+
+class PolyaParams(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("first_molecule_index", C.c_uint64), ("dist", C.c_int32), ("flags", C.c_int32),
+                ("a", C.c_double), ("b", C.c_double), ("min_length", C.c_int32), ("max_length", C.c_int32)]
+
+
+class TagParams(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("first_molecule_index", C.c_uint64), ("format5", C.c_char_p), ("format3", C.c_char_p),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ScbParams(C.Structure):
+    _fields_ = [("keep_meta_barcodes", C.c_int32), ("flags", C.c_int32)]
+
+
+class FlipParams(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("first_molecule_index", C.c_uint64), ("flip_probability", C.c_double), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+PLA_GAMMA, PLA_POISSON, PLA_WEIBULL, PLA_NORMAL = 0, 1, 2, 3
+MOL_NO_COMMENTS = 1
+
 SYMBOLS = [
     "tksmseq_create", "tksmseq_destroy", "tksmseq_last_error", "tksmseq_version", "tksmseq_set_stream",
     "tksmseq_synchronize", "tksmseq_reference_add_fasta", "tksmseq_reference_add_contig",
@@ -63,6 +86,8 @@ SYMBOLS = [
     "tksmseq_set_host_threads", "tksmseq_model_available",
     "tksmseq_device_alloc", "tksmseq_device_free", "tksmseq_copy_to_host", "tksmseq_pcr_preset", "tksmseq_pcr", "tksmseq_pcr_template_counts", "tksmseq_truncate", "tksmseq_batch_to_mdf_text", "tksmseq_text_free",
     "tksmseq_molecules_from_mdf_text", "tksmseq_pcr_main", "tksmseq_truncate_main", "tksmseq_run_diagnostics",
+    "tksmseq_polya", "tksmseq_tag", "tksmseq_scb", "tksmseq_flip",
+    "tksmseq_polya_main", "tksmseq_tag_main", "tksmseq_scb_main", "tksmseq_flip_main",
 ]
 
 _lib = None
@@ -105,6 +130,10 @@ def load():
         "tksmseq_pcr": (C.c_int, [vp, vp, vp, P(vp)]),
         "tksmseq_pcr_template_counts": (C.c_int, [vp, vp, vp, P(C.c_uint64)]),
         "tksmseq_truncate": (C.c_int, [vp, vp, vp, P(vp)]),
+        "tksmseq_polya": (C.c_int, [vp, vp, P(PolyaParams), P(vp)]),
+        "tksmseq_tag": (C.c_int, [vp, vp, P(TagParams), P(vp)]),
+        "tksmseq_scb": (C.c_int, [vp, vp, P(ScbParams), P(vp)]),
+        "tksmseq_flip": (C.c_int, [vp, vp, P(FlipParams), P(vp)]),
         "tksmseq_batch_to_mdf_text": (C.c_int, [vp, vp, P(vp), P(u64)]),
         "tksmseq_text_free": (None, [vp]),
         "tksmseq_molecules_from_mdf_text": (C.c_int, [vp, C.c_char_p, u64, P(vp)]),

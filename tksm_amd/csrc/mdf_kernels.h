@@ -1,6 +1,6 @@
 // mdf_kernels.h -- device side of the molecule-description transforms upstream of Seq in BASELINE config 5:
-// PCR amplification (src/pcr.cpp:22-89) and truncation (src/truncate.cpp:23-65, :77-227, :322-351).
-// Both read a molecule batch in the binary layout of include/tksmseq.h and write a new one, on the device.
+// PCR amplification (src/pcr.cpp:22-89) and truncation (src/truncate.cpp:23-65, :77-227, :322-351), and the segment edits of polyA,
+// tag, scb and flip.  All read a molecule batch in the binary layout of include/tksmseq.h and write a new one, on the device.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,5 +63,36 @@ hipError_t launch_trc_plan(const MolView& m, const TrcParams& p, uint64_t first_
                            double* tr_len, double* tr_side, uint64_t* n_ivls, uint64_t* n_mods, uint64_t* n_idlen, hipStream_t s);
 hipError_t launch_trc_write(const MolView& m, const uint32_t* keep_from, const uint32_t* keep_to, const uint64_t* ivl_off,
                             const uint64_t* mod_off, const uint64_t* id_off, const MolOut& o, hipStream_t s);
+
+
+// polyA / tag / scb / flip (src/polyA.cpp:133-148, src/tag.cpp:70-113, src/scb.cpp:57-80, src/interval.h:908-920): a plan per molecule
+// (literal in front, literal behind, flip), then one generic count + write pass
+constexpr uint32_t EDIT_NONE = 0xffffffffu;
+constexpr uint32_t PLA_MAX_ATTEMPTS = 64;   // rejection attempts of the gamma / PTRS samplers (blocks of 4 words for the multiplication method)
+enum { PLA_GAMMA = 0, PLA_POISSON = 1, PLA_WEIBULL = 2, PLA_NORMAL = 3 };
+struct PlaParams {
+    uint64_t seed;
+    int dist;                             // PLA_*
+    double a, b;                          // gamma / weibull (shape, scale), poisson (lambda, -), normal (mu, sigma)
+    int min_len, max_len;
+    uint32_t lit_base;                    // literal lit_base + L - 1 is "A" x L, L = 1 .. max_len
+};
+hipError_t launch_pla_plan(uint64_t n, const PlaParams& p, uint64_t first_index, uint32_t* post, hipStream_t s);
+struct TagEnd {
+    const uint8_t* fmt;                   // the format's letters that fmt2seq's table knows, upper case (device)
+    int len;
+    uint32_t shared;                      // a format without ambiguous letters: its one literal; EDIT_NONE otherwise
+    uint32_t lit_base;                    // otherwise molecule r gets literal lit_base + r, bytes at pool_base + r x len
+    uint64_t pool_base;
+};
+struct TagParams { uint64_t seed; TagEnd end[2]; };     // [0] 5' (prepended), [1] 3' (appended)
+hipError_t launch_tag_plan(uint64_t n, const TagParams& p, uint64_t first_index, uint32_t* pre, uint32_t* post, uint64_t* lits, uint8_t* pool,
+                           hipStream_t s);
+hipError_t launch_flip_plan(uint64_t n, uint64_t seed, double p, uint64_t first_index, uint8_t* flip, hipStream_t s);
+// pre / post / flip: [n_reads], any may be null (nothing of that kind); lits: the OUTPUT literal table (new literals' lengths)
+hipError_t launch_edit_count(const MolView& m, const uint32_t* pre, const uint32_t* post, uint64_t* n_ivls, uint64_t* n_mods, uint64_t* n_idlen,
+                             hipStream_t s);
+hipError_t launch_edit_write(const MolView& m, const uint32_t* pre, const uint32_t* post, const uint8_t* flip, const uint64_t* lits,
+                             const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off, const MolOut& o, hipStream_t s);
 
 }  // namespace tk

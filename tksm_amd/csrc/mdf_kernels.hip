@@ -7,6 +7,10 @@
 //   einterval::truncate          src/interval.h:708-735   cut segment: new bounds, substitutions re-based and filtered
 //   custom_distribution / 2D     src/truncate.cpp:77-227  empirical samplers of the KDE truncation model
 //   truncate_transformer(_kde)   src/truncate.cpp:322-351 3' truncation, then 5' truncation of the flipped molecule
+//   add_polyA                    src/polyA.cpp:133-148    append "A" x len, len ~ gamma / poisson / weibull / normal, clamped
+//   TAG_module::run              src/tag.cpp:70-113       prepend / append a tag drawn from an IUPAC format (fmt2seq, src/util.h:53-92)
+//   SingleCellBarcoder::run      src/scb.cpp:57-80        append the CB barcode of the header comment
+//   flip_molecule                src/interval.h:908-920   reverse the segment order, toggle every strand
 // Integer / byte work, one LANE per molecule: the tables of a molecule are a few dozen bytes, the work per molecule is a short
 // serial walk (tree of copies; list of segments).  The reference draws from a sequential Mersenne Twister; here every
 // decision has its own Philox counter (template molecule, path of copy cycles, purpose), so the result does not depend on
@@ -18,7 +22,8 @@ namespace tk {
 #define DEV __device__ __forceinline__
 
 struct Ph4m { uint32_t x, y, z, w; };
-enum { ST_PCR_PICK = 16, ST_PCR_EMIT = 17, ST_PCR_CHILD = 18, ST_PCR_MUT = 19, ST_TRC_LEN = 24, ST_TRC_SIDE = 25 };
+enum { ST_PCR_PICK = 16, ST_PCR_EMIT = 17, ST_PCR_CHILD = 18, ST_PCR_MUT = 19, ST_TRC_LEN = 24, ST_TRC_SIDE = 25,
+       ST_PLA_LEN = 26, ST_TAG5 = 27, ST_TAG3 = 28, ST_FLIP = 29 };
 
 DEV Ph4m philox_raw(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
@@ -378,6 +383,182 @@ __global__ void k_trc_write(MolView M, const uint32_t* __restrict__ keep_from, c
 }
 
 // ------------------------------------------------------------------------------------------------
+// polyA / tag / scb / flip: one generic segment edit.  A plan kernel per module decides, per molecule, a literal to put in front
+// (pre), a literal to put behind (post) -- EDIT_NONE for none -- and whether the segments are flipped; k_edit_count sizes the
+// result, k_edit_write copies it.  New literal intervals are {0x80000000 | literal, 0, len, mod_begin | plus}.
+// ------------------------------------------------------------------------------------------------
+DEV double u01o(uint32_t x) { return ((double)x + 1.0) * (1.0 / 4294967296.0); }       // (0, 1]
+DEV double box_muller(uint32_t a, uint32_t b) { return sqrt(-2.0 * log(u01o(a))) * cos(6.283185307179586 * u01(b)); }
+
+// std::poisson_distribution<int>: multiplication for lambda < 10 (uniforms: the words of blocks 0, 1, ... of the stream in order),
+// PTRS (Hoermann 1993, "The transformed rejection method for generating Poisson random variables") above, one block per attempt
+DEV double pla_poisson(uint64_t seed, uint64_t g, double lam) {
+    if (lam < 10.0) {
+        const double enlam = exp(-lam);
+        double prod = 1.0, k = 0.0;
+        for (uint32_t n = 0; n < PLA_MAX_ATTEMPTS * 4; n++) {
+            const Ph4m w = philox_mol(seed, g, ST_PLA_LEN, n);
+            const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+            for (int j = 0; j < 4; j++) {
+                prod *= u01(ws[j]);
+                if (prod > enlam) k += 1.0; else return k;
+            }
+        }
+        return k;
+    }
+    const double slam = sqrt(lam), loglam = log(lam);
+    const double b = 0.931 + 2.53 * slam, a = -0.059 + 0.02483 * b;
+    const double invalpha = 1.1239 + 1.1328 / (b - 3.4), vr = 0.9277 - 3.6224 / (b - 2.0);
+    for (uint32_t n = 0; n < PLA_MAX_ATTEMPTS; n++) {
+        const Ph4m w = philox_mol(seed, g, ST_PLA_LEN, n);
+        const double U = u01(w.x) - 0.5, V = u01(w.y);
+        const double us = 0.5 - fabs(U);
+        const double k = floor((2.0 * a / us + b) * U + lam + 0.43);
+        if (us >= 0.07 && V <= vr) return k;
+        if (k < 0.0 || (us < 0.013 && V > us)) continue;
+        if (log(V) + log(invalpha) - log(a / (us * us) + b) <= -lam + k * loglam - lgamma(k + 1.0)) return k;
+    }
+    return floor(lam);
+}
+
+DEV double pla_draw(const PlaParams& P, uint64_t g) {
+    if (P.dist == PLA_POISSON) return pla_poisson(P.seed, g, P.a);
+    if (P.dist == PLA_NORMAL) { const Ph4m w = philox_mol(P.seed, g, ST_PLA_LEN, 0); return P.a + P.b * box_muller(w.x, w.y); }
+    if (P.dist == PLA_WEIBULL) { const Ph4m w = philox_mol(P.seed, g, ST_PLA_LEN, 0); return P.b * pow(-log(u01o(w.x)), 1.0 / P.a); }
+    // gamma(shape a, scale b): Marsaglia & Tsang 2000 on shape a (a >= 1) or a + 1 (a < 1, times u^(1/a)); attempt n uses block n:
+    // x, y -> the normal deviate, z -> the acceptance uniform, w -> the boost
+    const double al = P.a < 1.0 ? P.a + 1.0 : P.a;
+    const double d = al - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
+    for (uint32_t n = 0; n < PLA_MAX_ATTEMPTS; n++) {
+        const Ph4m w = philox_mol(P.seed, g, ST_PLA_LEN, n);
+        const double z = box_muller(w.x, w.y);
+        const double t = 1.0 + c * z;
+        if (t <= 0.0) continue;
+        const double v = t * t * t;
+        if (log(u01o(w.z)) < 0.5 * z * z + d - d * v + d * log(v)) {
+            double x = d * v;
+            if (P.a < 1.0) x = x * pow(u01o(w.w), 1.0 / P.a);
+            return x * P.b;
+        }
+    }
+    return d * P.b;
+}
+
+// add_polyA (src/polyA.cpp:133-148): the draw, clamped to [min, max] in double (NaN -> min), then truncated toward zero
+DEV int pla_length(const PlaParams& P, uint64_t g) {
+    const double v = pla_draw(P, g);
+    if (!(v >= (double)P.min_len)) return P.min_len;
+    if (v > (double)P.max_len) return P.max_len;
+    return (int)v;
+}
+
+__global__ void k_pla_plan(uint64_t n, PlaParams P, uint64_t first_index, uint32_t* __restrict__ post) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const int len = pla_length(P, first_index + r);
+    post[r] = len > 0 ? P.lit_base + (uint32_t)(len - 1) : EDIT_NONE;     // literal lit_base + L - 1 is "A" x L
+}
+
+// fmt2seq's table (src/util.h:62-80): the choices of an IUPAC letter, packed a byte each, and their number (0: not in the table)
+DEV uint32_t iupac(uint8_t c, int& k) {
+    k = 1;
+    switch (c) {
+        case 'A': return 'A'; case 'G': return 'G'; case 'T': return 'T'; case 'C': return 'C'; case 'U': return 'U';
+        case 'R': k = 2; return 'G' | 'A' << 8;                 case 'Y': k = 2; return 'T' | 'C' << 8;
+        case 'K': k = 2; return 'G' | 'T' << 8;                 case 'M': k = 2; return 'A' | 'C' << 8;
+        case 'S': k = 2; return 'G' | 'C' << 8;                 case 'W': k = 2; return 'A' | 'T' << 8;
+        case 'B': k = 3; return 'G' | 'T' << 8 | 'C' << 16;     case 'D': k = 3; return 'G' | 'A' << 8 | 'T' << 16;
+        case 'H': k = 3; return 'A' | 'C' << 8 | 'T' << 16;     case 'V': k = 3; return 'G' | 'C' << 8 | 'A' << 16;
+        case 'N': k = 4; return 'A' | 'G' << 8 | 'C' << 16 | (uint32_t)'T' << 24;
+        default: k = 0; return 0u;
+    }
+}
+
+// one tag: character j of the (table-only) format is choice umulhi(word j of the stream, k) -- word j = component j % 4 of block j / 4
+DEV void tag_draw(uint64_t seed, uint64_t g, uint32_t stream, const uint8_t* fmt, int len, uint8_t* dst) {
+    Ph4m w{};
+    for (int j = 0; j < len; j++) {
+        if ((j & 3) == 0) w = philox_mol(seed, g, stream, (uint32_t)j >> 2);
+        const uint32_t word = (j & 3) == 0 ? w.x : (j & 3) == 1 ? w.y : (j & 3) == 2 ? w.z : w.w;
+        int k;
+        const uint32_t opts = iupac(fmt[j], k);
+        dst[j] = (uint8_t)(opts >> (8 * __umulhi(word, (uint32_t)k)));
+    }
+}
+
+__global__ void k_tag_plan(uint64_t n, TagParams T, uint64_t first_index, uint32_t* __restrict__ pre, uint32_t* __restrict__ post,
+                           uint64_t* __restrict__ lits, uint8_t* __restrict__ pool) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const uint64_t g = first_index + r;
+    for (int e = 0; e < 2; e++) {
+        const TagEnd& E = T.end[e];
+        uint32_t li = E.shared;
+        if (li == EDIT_NONE && E.len > 0) {
+            // a literal of its own: entry lit_base + r, bytes at pool_base + r x len
+            li = E.lit_base + (uint32_t)r;
+            const uint64_t off = E.pool_base + r * (uint64_t)E.len;
+            tag_draw(T.seed, g, e == 0 ? ST_TAG5 : ST_TAG3, E.fmt, E.len, pool + off);
+            lits[2ull * li] = off; lits[2ull * li + 1] = (uint64_t)E.len;
+        }
+        (e == 0 ? pre : post)[r] = li;
+    }
+}
+
+__global__ void k_flip_plan(uint64_t n, uint64_t seed, double p, uint64_t first_index, uint8_t* __restrict__ flip) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    flip[r] = u01(philox_mol(seed, first_index + r, ST_FLIP, 0).x) < p ? 1 : 0;
+}
+
+DEV uint32_t unrolled_id_len(const MolView& M, uint64_t r) {
+    return M.B.ids[2 * r + 1] + ((M.dup && (M.dup[r] >> 31)) ? 1u + (uint32_t)ndig(M.dup[r] & 0x7fffffffu) : 0u);
+}
+
+__global__ void k_edit_count(MolView M, const uint32_t* __restrict__ pre, const uint32_t* __restrict__ post, uint64_t* __restrict__ n_ivls,
+                             uint64_t* __restrict__ n_mods, uint64_t* __restrict__ n_idlen) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= M.B.n_reads) return;
+    n_ivls[r] = M.B.reads[2 * r + 1] + ((pre && pre[r] != EDIT_NONE) ? 1u : 0u) + ((post && post[r] != EDIT_NONE) ? 1u : 0u);
+    n_mods[r] = mol_mods(M.B, (uint32_t)r);
+    n_idlen[r] = unrolled_id_len(M, r);
+}
+
+__global__ void k_edit_write(MolView M, const uint32_t* __restrict__ pre, const uint32_t* __restrict__ post, const uint8_t* __restrict__ flip,
+                             const uint64_t* __restrict__ lits, const uint64_t* __restrict__ ivl_off, const uint64_t* __restrict__ mod_off,
+                             const uint64_t* __restrict__ id_off, MolOut O) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= M.B.n_reads) return;
+    const BatchView& B = M.B;
+    const uint32_t ib = B.reads[2 * r], ic = B.reads[2 * r + 1];
+    uint64_t io = ivl_off[r], mo = mod_off[r];
+    O.reads[2 * r] = (uint32_t)io; O.reads[2 * r + 1] = (uint32_t)(ivl_off[r + 1] - io);
+    {
+        uint8_t* d = O.idpool + id_off[r];
+        const uint32_t so = B.ids[2 * r], sl = B.ids[2 * r + 1];
+        uint32_t k = 0;
+        for (; k < sl; k++) d[k] = B.idpool[so + k];
+        if (M.dup && (M.dup[r] >> 31)) { d[k++] = '_'; k += (uint32_t)put_dec(d + k, M.dup[r] & 0x7fffffffu); }
+        O.ids[2 * r] = (uint32_t)id_off[r]; O.ids[2 * r + 1] = k;
+    }
+    auto put_literal = [&](uint32_t li) {
+        uint32_t* ov = O.intervals + 4ull * io++;
+        ov[0] = 0x80000000u | li; ov[1] = 0u; ov[2] = (uint32_t)lits[2ull * li + 1]; ov[3] = (uint32_t)mo;
+    };
+    if (pre && pre[r] != EDIT_NONE) put_literal(pre[r]);
+    const bool fl = flip && flip[r];
+    for (uint32_t q = 0; q < ic; q++) {
+        const uint32_t i = fl ? ic - 1 - q : q;
+        const uint32_t* iv = B.intervals + 4ull * (ib + i);
+        uint32_t* ov = O.intervals + 4ull * io++;
+        ov[0] = iv[0]; ov[1] = iv[1]; ov[2] = iv[2]; ov[3] = (uint32_t)mo | ((iv[3] ^ (fl ? 0x80000000u : 0u)) & 0x80000000u);
+        const uint32_t mb = iv[3] & 0x7fffffffu, me = iv[7] & 0x7fffffffu;
+        for (uint32_t m = mb; m < me; m++) { O.mods[2 * mo] = B.mods[2ull * m]; O.mods[2 * mo + 1] = B.mods[2ull * m + 1]; mo++; }
+    }
+    if (post && post[r] != EDIT_NONE) put_literal(post[r]);
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
 static inline unsigned nblk(uint64_t n) { return (unsigned)((n + 127) / 128); }
@@ -409,6 +590,35 @@ hipError_t launch_trc_write(const MolView& m, const uint32_t* keep_from, const u
                             const uint64_t* mod_off, const uint64_t* id_off, const MolOut& o, hipStream_t s) {
     if (!m.B.n_reads) return hipSuccess;
     hipLaunchKernelGGL(k_trc_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, keep_from, keep_to, ivl_off, mod_off, id_off, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_pla_plan(uint64_t n, const PlaParams& p, uint64_t first_index, uint32_t* post, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_pla_plan, dim3(nblk(n)), dim3(128), 0, s, n, p, first_index, post);
+    return hipGetLastError();
+}
+hipError_t launch_tag_plan(uint64_t n, const TagParams& p, uint64_t first_index, uint32_t* pre, uint32_t* post, uint64_t* lits, uint8_t* pool,
+                           hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_tag_plan, dim3(nblk(n)), dim3(128), 0, s, n, p, first_index, pre, post, lits, pool);
+    return hipGetLastError();
+}
+hipError_t launch_flip_plan(uint64_t n, uint64_t seed, double p, uint64_t first_index, uint8_t* flip, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_flip_plan, dim3(nblk(n)), dim3(128), 0, s, n, seed, p, first_index, flip);
+    return hipGetLastError();
+}
+hipError_t launch_edit_count(const MolView& m, const uint32_t* pre, const uint32_t* post, uint64_t* n_ivls, uint64_t* n_mods, uint64_t* n_idlen,
+                             hipStream_t s) {
+    if (!m.B.n_reads) return hipSuccess;
+    hipLaunchKernelGGL(k_edit_count, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, pre, post, n_ivls, n_mods, n_idlen);
+    return hipGetLastError();
+}
+hipError_t launch_edit_write(const MolView& m, const uint32_t* pre, const uint32_t* post, const uint8_t* flip, const uint64_t* lits,
+                             const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off, const MolOut& o, hipStream_t s) {
+    if (!m.B.n_reads) return hipSuccess;
+    hipLaunchKernelGGL(k_edit_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, pre, post, flip, lits, ivl_off, mod_off, id_off, o);
     return hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-// mdf_modules.cpp -- the `tksm pcr` and `tksm truncate` modules on top of the C-ABI (MDF file in, MDF file out).
+// mdf_modules.cpp -- the `tksm pcr`, `truncate`, `polyA`, `tag`, `scb` and `flip` modules on top of the C-ABI (MDF file in, MDF file out).
 //
 // Mirrors (file:line into vpc-ccg/tksm):
 //   PCR_module::impl        src/pcr.cpp:91-260       flags -i -o --molecule-count --cycles --error-rate --efficiency -x/--preset,
@@ -6,8 +6,12 @@
 //                                                    ratio needs the number of templates), the output is streamed
 //   Truncate_module::impl   src/truncate.cpp:236-451 flags -i -o --kde-model --always-end --kde-models-length --normal --lognormal,
 //                                                    "exactly one of kde-model, normal or lognormal"; a stream transform (:322-351)
+//   PolyA_module            src/polyA.cpp:17-237     --gamma / --poisson / --weibull / --normal, --min-length, --max-length
+//   TAG_module              src/tag.cpp:16-129       -5/--format5, -3/--format3 (a leading digit: that many N's)
+//   SingleCellBarcoder      src/scb.cpp:14-92        --keep-meta-barcodes
+//   StrandMan_module        src/strand_man.cpp:20-124 -p/--flip-probability (outside [0, 1]: logged, not refused)
 //   utility flags           src/module.h:75-104      -s/--seed (default 42), --verbosity, --log-file, -h
-// Both stream: `truncate` reads the input in batches of whole molecules (--batch-bytes), `pcr` amplifies its templates in slices
+// All stream: `truncate` and the four segment edits read the input in batches of whole molecules (--batch-bytes), `pcr` amplifies its templates in slices
 // of about --slice-molecules output molecules (tksmseq_pcr_params::template_begin / _end); the pieces go round the entries of
 // --devices D[,D...] (two contexts per entry: one formats its text while the other computes) and are written in input order, so the
 // output does not depend on the device list or the piece size.
@@ -24,6 +28,8 @@
 #include <string>
 #include <thread>
 #include <algorithm>
+#include <cctype>
+#include <cmath>
 #include <vector>
 
 #include "../../include/tksmseq.h"
@@ -146,6 +152,68 @@ int run_pieces(const Common& c, Logger& log, const char* what, Prepare prepare, 
     log.log(Logger::INFO, "%s: %llu molecules written in %.2f s (%d device group(s))", what, (unsigned long long)molecules.load(),
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), (int)c.devices.size());
     return 0;
+}
+
+// A stream transform (truncate, polyA, tag, scb, flip): the input in pieces of whole molecules, op(ctx, batch, index of its first
+// molecule, out) on each, the outputs written in input order.
+template <class Op>
+int stream_transform(const Common& c, Logger& log, const char* what, Op op) {
+    // a reader thread of its own cuts the input into pieces of whole molecules and numbers them (input order), a few pieces ahead of the
+    // workers: what the engine serialises is a pop from this queue, not the read + scan of a piece.  Its state lives on the heap and is
+    // shared with the thread: after an error the module returns without waiting for a reader that may sit in a read() on a pipe nobody
+    // closes (the thread is detached and ends with the process).
+    struct ReaderState {
+        tkmod::ChunkReader rd;
+        std::mutex m; std::condition_variable put, get; std::deque<Piece> pieces; bool done = false, stop = false; size_t cap = 3;
+    };
+    auto rs = std::make_shared<ReaderState>();
+    rs->rd.in = fopen(c.input.c_str(), "rb");
+    if (!rs->rd.in) { fprintf(stderr, "Could not open file %s\n", c.input.c_str()); return 1; }
+    rs->rd.bytes = c.batch_bytes;
+    rs->cap = c.devices.size() * 2 + 1;
+    std::thread reader([rs]() {
+        uint64_t seq = 0, first = 0;
+        for (;;) {
+            Piece pc;
+            if (!rs->rd.next(pc.text)) {
+                if (seq) break;
+                pc.text.clear();                                  // an empty input still makes an (empty) output
+            }
+            pc.seq = seq++; pc.first = first;
+            first += tkmod::count_reads(pc.text.data(), pc.text.size());
+            std::unique_lock<std::mutex> l(rs->m);
+            rs->put.wait(l, [&] { return rs->pieces.size() < rs->cap || rs->stop; });
+            if (rs->stop) break;
+            rs->pieces.push_back(std::move(pc));
+            rs->get.notify_one();
+        }
+        { std::lock_guard<std::mutex> l(rs->m); rs->done = true; }
+        rs->get.notify_all();
+    });
+    auto prepare = [&](tksmseq_ctx*, void**) -> bool { return true; };
+    auto next_piece = [&](Piece& pc) -> bool {
+        std::unique_lock<std::mutex> l(rs->m);
+        rs->get.wait(l, [&] { return !rs->pieces.empty() || rs->done; });
+        if (rs->pieces.empty()) return false;
+        pc = std::move(rs->pieces.front()); rs->pieces.pop_front();
+        rs->put.notify_one();
+        return true;
+    };
+    auto work = [&](tksmseq_ctx* ctx, void*, const Piece& pc, tksmseq_batch** out) -> int {
+        tksmseq_batch* in = nullptr;
+        int rc = tksmseq_molecules_from_mdf_text(ctx, pc.text.data(), pc.text.size(), &in);
+        if (rc) return rc;
+        rc = op(ctx, in, pc.first, out);
+        tksmseq_batch_free(ctx, in);
+        return rc;
+    };
+    const int rc = run_pieces(c, log, what, prepare, next_piece, work);
+    bool finished;
+    { std::lock_guard<std::mutex> l(rs->m); rs->stop = true; finished = rs->done; }      // (an error: the reader may be waiting for room, or for input)
+    rs->put.notify_all();
+    if (rc == 0 || finished) { reader.join(); fclose(rs->rd.in); }
+    else reader.detach();
+    return rc;
 }
 
 }  // namespace
@@ -271,62 +339,193 @@ extern "C" int tksmseq_truncate_main(int argc0, char** argv0) {
     if (!open_log(c, "truncate", log)) return 1;
     if (!kde.empty()) { p.mode = TKSMSEQ_TRC_KDE; p.kde_model_path = kde.c_str(); }
     p.seed = (uint64_t)c.seed;
-    // a reader thread of its own cuts the input into pieces of whole molecules and numbers them (input order), a few pieces ahead of the
-    // workers: what the engine serialises is a pop from this queue, not the read + scan of a piece.  Its state lives on the heap and is
-    // shared with the thread: after an error the module returns without waiting for a reader that may sit in a read() on a pipe nobody
-    // closes (the thread is detached and ends with the process).
-    struct ReaderState {
-        tkmod::ChunkReader rd;
-        std::mutex m; std::condition_variable put, get; std::deque<Piece> pieces; bool done = false, stop = false; size_t cap = 3;
-    };
-    auto rs = std::make_shared<ReaderState>();
-    rs->rd.in = fopen(c.input.c_str(), "rb");
-    if (!rs->rd.in) { fprintf(stderr, "Could not open file %s\n", c.input.c_str()); return 1; }
-    rs->rd.bytes = c.batch_bytes;
-    rs->cap = c.devices.size() * 2 + 1;
-    std::thread reader([rs]() {
-        uint64_t seq = 0, first = 0;
-        for (;;) {
-            Piece pc;
-            if (!rs->rd.next(pc.text)) {
-                if (seq) break;
-                pc.text.clear();                                  // an empty input still makes an (empty) output
-            }
-            pc.seq = seq++; pc.first = first;
-            first += tkmod::count_reads(pc.text.data(), pc.text.size());
-            std::unique_lock<std::mutex> l(rs->m);
-            rs->put.wait(l, [&] { return rs->pieces.size() < rs->cap || rs->stop; });
-            if (rs->stop) break;
-            rs->pieces.push_back(std::move(pc));
-            rs->get.notify_one();
-        }
-        { std::lock_guard<std::mutex> l(rs->m); rs->done = true; }
-        rs->get.notify_all();
-    });
-    auto prepare = [&](tksmseq_ctx*, void**) -> bool { return true; };
-    auto next_piece = [&](Piece& pc) -> bool {
-        std::unique_lock<std::mutex> l(rs->m);
-        rs->get.wait(l, [&] { return !rs->pieces.empty() || rs->done; });
-        if (rs->pieces.empty()) return false;
-        pc = std::move(rs->pieces.front()); rs->pieces.pop_front();
-        rs->put.notify_one();
-        return true;
-    };
-    auto work = [&](tksmseq_ctx* ctx, void*, const Piece& pc, tksmseq_batch** out) -> int {
-        tksmseq_batch* in = nullptr;
-        int rc = tksmseq_molecules_from_mdf_text(ctx, pc.text.data(), pc.text.size(), &in);
-        if (rc) return rc;
+    return stream_transform(c, log, "truncate", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, uint64_t first, tksmseq_batch** out) {
         tksmseq_trc_params q = p;
-        q.first_molecule_index = pc.first;
-        rc = tksmseq_truncate(ctx, in, &q, out);
-        tksmseq_batch_free(ctx, in);
-        return rc;
-    };
-    const int rc = run_pieces(c, log, "truncate", prepare, next_piece, work);
-    bool finished;
-    { std::lock_guard<std::mutex> l(rs->m); rs->stop = true; finished = rs->done; }      // (an error: the reader may be waiting for room, or for input)
-    rs->put.notify_all();
-    if (rc == 0 || finished) { reader.join(); fclose(rs->rd.in); }
-    else reader.detach();
-    return rc;
+        q.first_molecule_index = first;
+        return tksmseq_truncate(ctx, in, &q, out);
+    });
+}
+
+// comma-separated doubles (cxxopts' vector<double>); false on a malformed list
+static bool parse_doubles(const char* v, std::vector<double>& out) {
+    out.clear();
+    const char* q = v;
+    for (;;) {
+        char* e = nullptr;
+        const double d = strtod(q, &e);
+        if (e == q || (*e && *e != ',')) return false;
+        out.push_back(d);
+        if (!*e) return true;
+        q = e + 1;
+    }
+}
+
+extern "C" int tksmseq_polya_main(int argc0, char** argv0) {
+    std::vector<std::string> arg_store; std::vector<char*> arg_ptrs;
+    tkmod::split_equals(argc0, argv0, arg_store, arg_ptrs);
+    const int argc = (int)arg_ptrs.size(); char** const argv = arg_ptrs.data();
+    Common c;
+    tksmseq_polya_params p{};
+    p.min_length = 0; p.max_length = 5000;
+    static const char* names[4] = {"gamma", "poisson", "weibull", "normal"};
+    static const char* titles[4] = {"Gamma", "Poisson", "Weibull", "Normal"};
+    std::vector<double> vals[4];
+    int count[4] = {0, 0, 0, 0};
+    for (int i = 1; i < argc; i++) {
+        const int k = common_flag(argc, argv, i, c);
+        if (k < 0) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; }
+        if (k) continue;
+        const std::string o = argv[i];
+        const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
+        int d = -1;
+        for (int q = 0; q < 4; q++) if (o == std::string("--") + names[q]) d = q;
+        if (d >= 0 && v) { if (!parse_doubles(v, vals[d])) { fprintf(stderr, "Option '%s' needs a comma-separated list of numbers\n", o.c_str()); return 1; } count[d]++; i++; }
+        else if (o == "--min-length" && v) { p.min_length = atoi(v); i++; }
+        else if (o == "--max-length" && v) { p.max_length = atoi(v); i++; }
+        else { fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1; }
+    }
+    if (c.help) { printf("polyA module: adds polyA tails to molecules with given size distribution\n"
+                         "usage: polyA -i INPUT -o OUTPUT (--gamma A,B | --poisson L | --weibull A,B | --normal MU,SIGMA) [--min-length N] [--max-length N]\n"
+                         "             [-s SEED] [--devices D[,D...]] [--batch-bytes B] [--verbosity L] [--log-file F]\n"); return 0; }
+    // validate_arguments (src/polyA.cpp:61-118)
+    int missing = 0;
+    if (c.input.empty()) { fprintf(stderr, "Missing parameter: input\n"); missing++; }
+    if (c.output.empty()) { fprintf(stderr, "Missing parameter: output\n"); missing++; }
+    const int n_dist = (count[0] > 0) + (count[1] > 0) + (count[2] > 0) + (count[3] > 0);
+    if (n_dist == 0) { fprintf(stderr, "No distribution specified\n"); missing++; }
+    if (n_dist > 1) { fprintf(stderr, "Multiple distributions specified\n"); missing++; }
+    for (int q = 0; q < 4; q++) {
+        const size_t want = q == 1 ? 1 : 2;
+        if (count[q] && vals[q].size() != want) { fprintf(stderr, "%s distribution requires %s\n", titles[q], want == 1 ? "one parameter" : "two parameters"); missing++; }
+    }
+    if (p.min_length < 0) { fprintf(stderr, "Minimum length of polyA cannot be negative\n"); missing++; }
+    if (p.max_length < 0) { fprintf(stderr, "Maximum length of polyA cannot be negative\n"); missing++; }
+    if (p.min_length > p.max_length) { fprintf(stderr, "Minimum length of polyA cannot be greater than maximum length of polyA\n"); missing++; }
+    if (missing) return 1;
+    for (int q = 0; q < 4; q++)
+        if (count[q]) { p.dist = q == 0 ? TKSMSEQ_PLA_GAMMA : q == 1 ? TKSMSEQ_PLA_POISSON : q == 2 ? TKSMSEQ_PLA_WEIBULL : TKSMSEQ_PLA_NORMAL; p.a = vals[q][0]; p.b = vals[q].size() > 1 ? vals[q][1] : 0.0; }
+    // (parameters the std:: distributions leave undefined: rejected before any work, with the library's message)
+    {
+        const bool two = p.dist != TKSMSEQ_PLA_POISSON;
+        if (!std::isfinite(p.a) || (two && !std::isfinite(p.b)) || (p.dist != TKSMSEQ_PLA_NORMAL && !(p.a > 0.0)) || (two && !(p.b > 0.0))) {
+            fprintf(stderr, "Error: %s distribution parameters must be finite and positive (the mean of a normal distribution may be any finite number)\n", titles[p.dist == TKSMSEQ_PLA_GAMMA ? 0 : p.dist == TKSMSEQ_PLA_POISSON ? 1 : p.dist == TKSMSEQ_PLA_WEIBULL ? 2 : 3]);
+            return 1;
+        }
+    }
+    Logger log;
+    if (!open_log(c, "polyA", log)) return 1;
+    p.seed = (uint64_t)c.seed;
+    return stream_transform(c, log, "polyA", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, uint64_t first, tksmseq_batch** out) {
+        tksmseq_polya_params q = p;
+        q.first_molecule_index = first;
+        return tksmseq_polya(ctx, in, &q, out);
+    });
+}
+
+extern "C" int tksmseq_tag_main(int argc0, char** argv0) {
+    std::vector<std::string> arg_store; std::vector<char*> arg_ptrs;
+    tkmod::split_equals(argc0, argv0, arg_store, arg_ptrs);
+    const int argc = (int)arg_ptrs.size(); char** const argv = arg_ptrs.data();
+    Common c;
+    std::string fmt[2];
+    for (int i = 1; i < argc; i++) {
+        const int k = common_flag(argc, argv, i, c);
+        if (k < 0) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; }
+        if (k) continue;
+        const std::string o = argv[i];
+        const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
+        if ((o == "-5" || o == "--format5") && v) { fmt[0] = v; i++; }
+        else if ((o == "-3" || o == "--format3") && v) { fmt[1] = v; i++; }
+        else { fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1; }
+    }
+    if (c.help) { printf("TAGging module\nusage: tag -i INPUT -o OUTPUT [-5 FORMAT5] [-3 FORMAT3] [-s SEED]\n"
+                         "           [--devices D[,D...]] [--batch-bytes B] [--verbosity L] [--log-file F]\n"
+                         "FORMAT: IUPAC letters (ACGTU RYKMSW BDHV N), or a number of N's\n"); return 0; }
+    // validate_arguments (src/tag.cpp:41-63)
+    int missing = 0;
+    if (c.input.empty()) { fprintf(stderr, "input is required!\n"); missing++; }
+    if (c.output.empty()) { fprintf(stderr, "output is required!\n"); missing++; }
+    if (fmt[0].empty() && fmt[1].empty()) { fprintf(stderr, "At least one of the TAG formats must be provided\n"); missing++; }
+    if (missing) return 1;
+    // a format that starts with a digit is that many N's (std::stoi, src/tag.cpp:84-91)
+    for (auto& f : fmt)
+        if (!f.empty() && isdigit((unsigned char)f[0])) {
+            const long long len = strtoll(f.c_str(), nullptr, 10);
+            if (len > (1 << 20)) { fprintf(stderr, "Error: tag length %s is not supported (at most 1048576)\n", f.c_str()); return 1; }
+            f.assign((size_t)len, 'N');
+        }
+    Logger log;
+    if (!open_log(c, "tag", log)) return 1;
+    tksmseq_tag_params p{};
+    p.seed = (uint64_t)c.seed; p.format5 = fmt[0].c_str(); p.format3 = fmt[1].c_str();
+    return stream_transform(c, log, "tag", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, uint64_t first, tksmseq_batch** out) {
+        tksmseq_tag_params q = p;
+        q.first_molecule_index = first;
+        return tksmseq_tag(ctx, in, &q, out);
+    });
+}
+
+extern "C" int tksmseq_scb_main(int argc0, char** argv0) {
+    std::vector<std::string> arg_store; std::vector<char*> arg_ptrs;
+    tkmod::split_equals(argc0, argv0, arg_store, arg_ptrs);
+    const int argc = (int)arg_ptrs.size(); char** const argv = arg_ptrs.data();
+    Common c;
+    tksmseq_scb_params p{};
+    for (int i = 1; i < argc; i++) {
+        const int k = common_flag(argc, argv, i, c);
+        if (k < 0) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; }
+        if (k) continue;
+        const std::string o = argv[i];
+        if (o == "--keep-meta-barcodes") {
+            p.keep_meta_barcodes = 1;
+            // (cxxopts' boolean: --keep-meta-barcodes=true|false)
+            if (i + 1 < argc && (!strcmp(argv[i + 1], "true") || !strcmp(argv[i + 1], "false"))) p.keep_meta_barcodes = !strcmp(argv[++i], "true");
+        } else { fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1; }
+    }
+    if (c.help) { printf("Single cell barcode module\nusage: scb -i INPUT -o OUTPUT [--keep-meta-barcodes]\n"
+                         "           [--devices D[,D...]] [--batch-bytes B] [--verbosity L] [--log-file F]\n"); return 0; }
+    int missing = 0;
+    if (c.input.empty()) { fprintf(stderr, "Missing parameter: input\n"); missing++; }
+    if (c.output.empty()) { fprintf(stderr, "Missing parameter: output\n"); missing++; }
+    if (missing) return 1;
+    Logger log;
+    if (!open_log(c, "scb", log)) return 1;
+    return stream_transform(c, log, "scb", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, uint64_t, tksmseq_batch** out) {
+        return tksmseq_scb(ctx, in, &p, out);
+    });
+}
+
+extern "C" int tksmseq_flip_main(int argc0, char** argv0) {
+    std::vector<std::string> arg_store; std::vector<char*> arg_ptrs;
+    tkmod::split_equals(argc0, argv0, arg_store, arg_ptrs);
+    const int argc = (int)arg_ptrs.size(); char** const argv = arg_ptrs.data();
+    Common c;
+    tksmseq_flip_params p{};
+    bool have_p = false;
+    for (int i = 1; i < argc; i++) {
+        const int k = common_flag(argc, argv, i, c);
+        if (k < 0) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; }
+        if (k) continue;
+        const std::string o = argv[i];
+        const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
+        if ((o == "-p" || o == "--flip-probability") && v) { p.flip_probability = atof(v); have_p = true; i++; }
+        else { fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1; }
+    }
+    if (c.help) { printf("Flip module\nusage: flip -i INPUT -o OUTPUT -p PROBABILITY [-s SEED]\n"
+                         "            [--devices D[,D...]] [--batch-bytes B] [--verbosity L] [--log-file F]\n"); return 0; }
+    int missing = 0;
+    if (c.input.empty()) { fprintf(stderr, "Missing parameter: input\n"); missing++; }
+    if (c.output.empty()) { fprintf(stderr, "Missing parameter: output\n"); missing++; }
+    if (!have_p) { fprintf(stderr, "Missing parameter: flip-probability\n"); missing++; }
+    if (missing) return 1;
+    // the reference logs this and runs anyway (validate_arguments returns 0: src/strand_man.cpp:80-85)
+    if (p.flip_probability < 0.0 || p.flip_probability > 1.0) fprintf(stderr, "Flip probability must be between 0 and 1\n");
+    Logger log;
+    if (!open_log(c, "flip", log)) return 1;
+    p.seed = (uint64_t)c.seed;
+    return stream_transform(c, log, "flip", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, uint64_t first, tksmseq_batch** out) {
+        tksmseq_flip_params q = p;
+        q.first_molecule_index = first;
+        return tksmseq_flip(ctx, in, &q, out);
+    });
 }

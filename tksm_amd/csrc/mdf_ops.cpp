@@ -1,6 +1,7 @@
 // mdf_ops.cpp -- host side of the molecule-description transforms upstream of Seq (BASELINE config 5) and of the MDF writer:
 //   tksmseq_pcr            src/pcr.cpp:22-89, :138 (presets), :215-229 (whole input in memory, at most 2 x target templates)
 //   tksmseq_truncate       src/truncate.cpp:23-65, :77-227, :322-351, :362-404
+//   tksmseq_polya / _tag / _scb / _flip   src/polyA.cpp:133-148, src/tag.cpp:70-113, src/scb.cpp:57-80, src/interval.h:908-920
 //   tksmseq_batch_to_mdf_text   molecule_descriptor::operator<<, src/interval.h:898-905 (+ dump_comment :880-890)
 // The molecule tables stay on the device from one transform to the next and into tksmseq_run; only sizes, per-read lengths
 // (which the host needs to size and order a Seq batch) and, for the text writer, the tables themselves come back.
@@ -9,6 +10,7 @@
 #include <cstring>
 #include <map>
 #include <memory>
+#include <unordered_map>
 
 #include "ctx.h"
 #include <thread>
@@ -52,10 +54,11 @@ int copy_literals(tksmseq_ctx* ctx, const tksmseq_batch* in, tksmseq_batch* out)
     return TKSMSEQ_OK;
 }
 
-// std::map<string, vector<string>> round trip of a header comment (molecule_descriptor::comment / dump_comment,
-// src/interval.h:809-830, :880-890), with extra values appended
-std::string normalize_comment(const char* c, size_t n, const std::vector<std::pair<std::string, std::string>>& extra) {
-    std::map<std::string, std::vector<std::string>> meta;
+using Meta = std::map<std::string, std::vector<std::string>>;
+
+// molecule_descriptor::comment (src/interval.h:809-830): "k=v1,v2;flag;" -> key -> values ("." for a bare key)
+Meta parse_meta(const char* c, size_t n) {
+    Meta meta;
     size_t a = 0;
     while (a < n) {
         size_t b = a;
@@ -82,7 +85,11 @@ std::string normalize_comment(const char* c, size_t n, const std::vector<std::pa
         }
         a = b + 1;
     }
-    for (auto& kv : extra) meta[kv.first].push_back(kv.second);
+    return meta;
+}
+
+// dump_comment (src/interval.h:880-890)
+std::string dump_meta(const Meta& meta) {
     std::string out;
     for (auto& kv : meta) {
         if (kv.second.empty()) continue;
@@ -94,6 +101,14 @@ std::string normalize_comment(const char* c, size_t n, const std::vector<std::pa
         out += ';';
     }
     return out;
+}
+
+// std::map<string, vector<string>> round trip of a header comment (molecule_descriptor::comment / dump_comment,
+// src/interval.h:809-830, :880-890), with extra values appended
+std::string normalize_comment(const char* c, size_t n, const std::vector<std::pair<std::string, std::string>>& extra) {
+    Meta meta = parse_meta(c, n);
+    for (auto& kv : extra) meta[kv.first].push_back(kv.second);
+    return dump_meta(meta);
 }
 
 // fmt's "{}" of a double: the shortest digits that round-trip, in FIXED notation while the decimal exponent is in [-4, 16) and in
@@ -435,6 +450,249 @@ int tksmseq_truncate(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_tr
     if ((rc = finalize_device_batch(ctx, b.get()))) return rc;
     *out = b.release();
     return TKSMSEQ_OK;
+}
+
+// ---- segment edits: polyA, tag, scb, flip ----------------------------------------------------------------------------------------
+// The output's literal table: the input's entries and pool (the pool copied whole, its capacity), then n_new entries and new_bytes
+// pool bytes behind them; lit_base / pool_base: where the new ones start.
+static int edit_literals(tksmseq_ctx* ctx, const tksmseq_batch* in, tksmseq_batch* b, uint64_t n_new, uint64_t new_bytes, uint32_t& lit_base,
+                         uint64_t& pool_base) {
+    const uint64_t nl = in->n_literals + n_new;
+    if (nl >= 0x80000000ull) { ctx->err = "more than 2^31 literals in one batch (split the input)"; return TKSMSEQ_ELIMIT; }
+    hipStream_t s = ctx->stream;
+    b->n_literals = nl;
+    pool_base = in->litpool.cap;
+    lit_base = (uint32_t)in->n_literals;
+    HIPCHK(ctx, b->literals.ensure(nl * 16 + 64));
+    HIPCHK(ctx, b->litpool.ensure(pool_base + new_bytes + 64));
+    if (in->n_literals) HIPCHK(ctx, hipMemcpyAsync(b->literals.p, in->literals.p, in->n_literals * 16, hipMemcpyDeviceToDevice, s));
+    if (in->litpool.cap) HIPCHK(ctx, hipMemcpyAsync(b->litpool.p, in->litpool.p, in->litpool.cap, hipMemcpyDeviceToDevice, s));
+    return TKSMSEQ_OK;
+}
+
+// count, scan, allocate, write: every molecule of `in` (unrolled) with literal pre[r] in front of and post[r] behind its segments, which
+// are reversed and strand-toggled where flip[r] (device arrays; null: none of that kind).  b's literal table is already complete.
+static int edit_apply(tksmseq_ctx* ctx, const tksmseq_batch* in, const uint32_t* pre, const uint32_t* post, const uint8_t* flip, tksmseq_batch* b) {
+    hipStream_t s = ctx->stream;
+    const uint64_t n = in->n_reads;
+    tk::MolView M{view_of(in), in->d_dup.p ? in->d_dup.as<uint32_t>() : nullptr, in->n_intervals, in->n_mods, nullptr, n};
+    DevBuf n_ivl, n_mod, n_idl, o_ivl, o_mod, o_id;
+    for (DevBuf* pb_ : {&n_ivl, &n_mod, &n_idl, &o_ivl, &o_mod, &o_id}) { pb_->pooled = true; pb_->pool_stream = s; }   // (per-call temporaries: DevCache, ctx.h)
+    for (DevBuf* x : {&n_ivl, &n_mod, &n_idl}) HIPCHK(ctx, x->ensure(n * 8 + 16));
+    HIPCHK(ctx, tk::launch_edit_count(M, pre, post, n_ivl.as<uint64_t>(), n_mod.as<uint64_t>(), n_idl.as<uint64_t>(), s));
+    uint64_t t_ivl = 0, t_mod = 0, t_id = 0;
+    int rc;
+    if ((rc = scan_to(ctx, n_ivl, o_ivl, n, &t_ivl)) || (rc = scan_to(ctx, n_mod, o_mod, n, &t_mod)) || (rc = scan_to(ctx, n_idl, o_id, n, &t_id))) return rc;
+    if (t_ivl >= 0x7fffffffull || t_mod >= 0x7fffffffull || t_id >= 0xffffffffull) { ctx->err = "output batch too large (split the input)"; return TKSMSEQ_ELIMIT; }
+    b->n_reads = n; b->n_intervals = t_ivl; b->n_mods = t_mod;
+    HIPCHK(ctx, b->reads.ensure(n * 8 + 64));
+    HIPCHK(ctx, b->intervals.ensure((t_ivl + 1) * 16 + 64));
+    HIPCHK(ctx, b->mods.ensure(t_mod * 8 + 64));
+    HIPCHK(ctx, b->ids.ensure(n * 8 + 64));
+    HIPCHK(ctx, b->idpool.ensure(t_id + 64));
+    tk::MolOut O{b->reads.as<uint32_t>(), b->intervals.as<uint32_t>(), b->mods.as<uint32_t>(), b->ids.as<uint32_t>(), b->idpool.as<uint8_t>()};
+    HIPCHK(ctx, tk::launch_edit_write(M, pre, post, flip, b->literals.as<uint64_t>(), o_ivl.as<uint64_t>(), o_mod.as<uint64_t>(), o_id.as<uint64_t>(), O, s));
+    const uint32_t sentinel[4] = {0u, 0u, 0u, (uint32_t)t_mod};
+    HIPCHK(ctx, hipMemcpyAsync(b->intervals.as<uint32_t>() + 4 * t_ivl, sentinel, 16, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));                    // (sentinel and the callers' host tables are read by now)
+    return TKSMSEQ_OK;
+}
+
+// comments unchanged (the writer re-serialises them, normalize_comment)
+static void edit_comments(const tksmseq_batch* in, tksmseq_batch* b, int32_t flags) {
+    if (flags & TKSMSEQ_MOL_NO_COMMENTS) return;
+    b->h_comments = in->h_comments; b->h_comment_pool = in->h_comment_pool;
+}
+
+static int edit_finish(tksmseq_ctx* ctx, std::unique_ptr<tksmseq_batch>& b, tksmseq_batch** out) {
+    const int rc = finalize_device_batch(ctx, b.get());
+    if (rc) return rc;
+    *out = b.release();
+    return TKSMSEQ_OK;
+}
+
+int tksmseq_polya(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_polya_params* p, tksmseq_batch** out) {
+    if (!ctx || !in || !p || !out) return TKSMSEQ_EINVAL;
+    *out = nullptr;
+    // validate_arguments (src/polyA.cpp:61-118), plus the parameters std:: leaves undefined
+    if (p->dist < TKSMSEQ_PLA_GAMMA || p->dist > TKSMSEQ_PLA_NORMAL) { ctx->err = "polyA: unknown distribution"; return TKSMSEQ_EINVAL; }
+    if (p->min_length < 0) { ctx->err = "Minimum length of polyA cannot be negative"; return TKSMSEQ_EINVAL; }
+    if (p->max_length < 0) { ctx->err = "Maximum length of polyA cannot be negative"; return TKSMSEQ_EINVAL; }
+    if (p->min_length > p->max_length) { ctx->err = "Minimum length of polyA cannot be greater than maximum length of polyA"; return TKSMSEQ_EINVAL; }
+    const bool two = p->dist != TKSMSEQ_PLA_POISSON;
+    if (!std::isfinite(p->a) || (two && !std::isfinite(p->b))) { ctx->err = "polyA: distribution parameters must be finite"; return TKSMSEQ_EINVAL; }
+    if ((p->dist != TKSMSEQ_PLA_NORMAL && !(p->a > 0.0)) || (two && !(p->b > 0.0))) {
+        ctx->err = p->dist == TKSMSEQ_PLA_NORMAL ? "polyA: sigma must be positive" : "polyA: distribution parameters must be positive";
+        return TKSMSEQ_EINVAL;
+    }
+    if (p->max_length > (1 << 20)) { ctx->err = "polyA: --max-length above 1048576 is not supported"; return TKSMSEQ_ELIMIT; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint64_t n = in->n_reads, L = (uint64_t)p->max_length;
+    std::unique_ptr<tksmseq_batch> b(new tksmseq_batch());
+    uint32_t lit_base = 0; uint64_t pool_base = 0;
+    int rc = edit_literals(ctx, in, b.get(), L, L, lit_base, pool_base);
+    if (rc) return rc;
+    // literal lit_base + k is "A" x (k + 1): all of them at the start of one run of max_length 'A's
+    std::vector<uint64_t> ent(2 * L);
+    for (uint64_t k = 0; k < L; k++) { ent[2 * k] = pool_base; ent[2 * k + 1] = k + 1; }
+    if (L) {
+        HIPCHK(ctx, hipMemcpyAsync(b->literals.as<uint64_t>() + 2ull * lit_base, ent.data(), L * 16, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemsetAsync(b->litpool.as<uint8_t>() + pool_base, 'A', L, s));
+    }
+    DevBuf d_post;
+    d_post.pooled = true; d_post.pool_stream = s;
+    HIPCHK(ctx, d_post.ensure(n * 4 + 16));
+    tk::PlaParams P{p->seed, p->dist, p->a, p->b, p->min_length, p->max_length, lit_base};
+    HIPCHK(ctx, tk::launch_pla_plan(n, P, p->first_molecule_index, d_post.as<uint32_t>(), s));
+    if ((rc = edit_apply(ctx, in, nullptr, d_post.as<uint32_t>(), nullptr, b.get()))) return rc;
+    edit_comments(in, b.get(), p->flags);
+    return edit_finish(ctx, b, out);
+}
+
+// fmt2seq's table (src/util.h:62-80): number of choices of a letter, 0 if the table does not know it
+static int iupac_choices(char c) {
+    switch (c) {
+        case 'A': case 'G': case 'T': case 'C': case 'U': return 1;
+        case 'R': case 'Y': case 'K': case 'M': case 'S': case 'W': return 2;
+        case 'B': case 'D': case 'H': case 'V': return 3;
+        case 'N': return 4;
+        default: return 0;
+    }
+}
+
+int tksmseq_tag(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_tag_params* p, tksmseq_batch** out) {
+    if (!ctx || !in || !p || !out) return TKSMSEQ_EINVAL;
+    *out = nullptr;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint64_t n = in->n_reads;
+    std::string fmt[2];
+    bool amb[2] = {false, false};
+    for (int e = 0; e < 2; e++) {
+        const char* f = e == 0 ? p->format5 : p->format3;
+        for (; f && *f; f++) { const int k = iupac_choices(*f); if (k) { fmt[e] += *f; amb[e] |= k > 1; } }
+        if (fmt[e].size() > (1u << 20)) { ctx->err = "tag: formats longer than 1048576 letters are not supported"; return TKSMSEQ_ELIMIT; }
+    }
+    // new literals: a shared one per adapter (no ambiguous letter), one per molecule per ambiguous format
+    uint64_t n_new = 0, bytes = 0;
+    for (int e = 0; e < 2; e++)
+        if (!fmt[e].empty()) { n_new += amb[e] ? n : 1; bytes += (amb[e] ? n : 1) * fmt[e].size(); }
+    std::unique_ptr<tksmseq_batch> b(new tksmseq_batch());
+    uint32_t lit_base = 0; uint64_t pool_base = 0;
+    int rc = edit_literals(ctx, in, b.get(), n_new, bytes, lit_base, pool_base);
+    if (rc) return rc;
+    DevBuf d_fmt[2], d_pre, d_post;
+    for (DevBuf* pb_ : {&d_fmt[0], &d_fmt[1], &d_pre, &d_post}) { pb_->pooled = true; pb_->pool_stream = s; }
+    tk::TagParams T{};
+    T.seed = p->seed;
+    uint64_t li = lit_base, off = pool_base;
+    uint64_t ent[2][2];
+    for (int e = 0; e < 2; e++) {
+        tk::TagEnd& E = T.end[e];
+        E.len = (int)fmt[e].size(); E.shared = tk::EDIT_NONE;
+        if (fmt[e].empty()) continue;
+        HIPCHK(ctx, d_fmt[e].ensure(fmt[e].size() + 16));
+        HIPCHK(ctx, hipMemcpyAsync(d_fmt[e].p, fmt[e].data(), fmt[e].size(), hipMemcpyHostToDevice, s));
+        E.fmt = d_fmt[e].as<uint8_t>();
+        if (amb[e]) { E.lit_base = (uint32_t)li; E.pool_base = off; li += n; off += n * fmt[e].size(); continue; }
+        E.shared = (uint32_t)li;
+        ent[e][0] = off; ent[e][1] = fmt[e].size();
+        HIPCHK(ctx, hipMemcpyAsync(b->literals.as<uint64_t>() + 2 * li, ent[e], 16, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(b->litpool.as<uint8_t>() + off, fmt[e].data(), fmt[e].size(), hipMemcpyHostToDevice, s));
+        li += 1; off += fmt[e].size();
+    }
+    HIPCHK(ctx, d_pre.ensure(n * 4 + 16));
+    HIPCHK(ctx, d_post.ensure(n * 4 + 16));
+    HIPCHK(ctx, tk::launch_tag_plan(n, T, p->first_molecule_index, d_pre.as<uint32_t>(), d_post.as<uint32_t>(), b->literals.as<uint64_t>(),
+                                    b->litpool.as<uint8_t>(), s));
+    if ((rc = edit_apply(ctx, in, d_pre.as<uint32_t>(), d_post.as<uint32_t>(), nullptr, b.get()))) return rc;
+    edit_comments(in, b.get(), p->flags);
+    return edit_finish(ctx, b, out);
+}
+
+// id of molecule r as the writer prints it (with the unroll suffix), for error messages
+static std::string molecule_id(tksmseq_ctx* ctx, const tksmseq_batch* in, uint64_t r) {
+    uint32_t e[2] = {0, 0};
+    std::string id;
+    if (hipMemcpy(e, in->ids.as<uint32_t>() + 2 * r, 8, hipMemcpyDeviceToHost) != hipSuccess) return "#" + std::to_string(r);
+    id.resize(e[1]);
+    if (e[1] && hipMemcpy(&id[0], in->idpool.as<uint8_t>() + e[0], e[1], hipMemcpyDeviceToHost) != hipSuccess) return "#" + std::to_string(r);
+    if (!in->h_dup.empty() && (in->h_dup[r] >> 31)) id += "_" + std::to_string(in->h_dup[r] & 0x7fffffffu);
+    return id;
+}
+
+int tksmseq_scb(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_scb_params* p, tksmseq_batch** out) {
+    if (!ctx || !in || !p || !out) return TKSMSEQ_EINVAL;
+    *out = nullptr;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint64_t n = in->n_reads;
+    if (n && in->h_comments.empty()) { ctx->err = "scb: the batch carries no header comments (CB barcodes)"; return TKSMSEQ_EINVAL; }
+    // the host resolves the barcodes (get_comment("CB")[0]) in one pass and de-duplicates them into literals
+    std::unique_ptr<tksmseq_batch> b(new tksmseq_batch());
+    const bool want_comments = !(p->flags & TKSMSEQ_MOL_NO_COMMENTS);
+    std::vector<uint32_t> post(n);
+    std::unordered_map<std::string, uint32_t> index;
+    std::vector<uint64_t> ent;
+    std::string bytes;
+    if (want_comments) b->h_comments.reserve(2 * n);
+    for (uint64_t r = 0; r < n; r++) {
+        Meta meta = parse_meta(in->h_comment_pool.data() + in->h_comments[2 * r], in->h_comments[2 * r + 1]);
+        auto it = meta.find("CB");
+        if (it == meta.end() || it->second.empty()) { ctx->err = "scb: molecule " + molecule_id(ctx, in, r) + " has no CB comment"; return TKSMSEQ_EINVAL; }
+        const std::string& bc = it->second[0];
+        if (bc == ".") post[r] = tk::EDIT_NONE;
+        else {
+            auto f = index.find(bc);
+            if (f == index.end()) {
+                f = index.emplace(bc, (uint32_t)index.size()).first;
+                ent.push_back(bytes.size()); ent.push_back(bc.size());
+                bytes += bc;
+            }
+            post[r] = f->second;
+        }
+        if (want_comments) {
+            if (!p->keep_meta_barcodes) meta.erase(it);
+            const std::string c = dump_meta(meta);
+            if (b->h_comment_pool.size() + c.size() >= 0xffffffffull) { ctx->err = "scb: more than 4 GB of header comments in one batch (split the input)"; return TKSMSEQ_ELIMIT; }
+            b->h_comments.push_back((uint32_t)b->h_comment_pool.size()); b->h_comments.push_back((uint32_t)c.size());
+            b->h_comment_pool.insert(b->h_comment_pool.end(), c.begin(), c.end());
+        }
+    }
+    uint32_t lit_base = 0; uint64_t pool_base = 0;
+    int rc = edit_literals(ctx, in, b.get(), index.size(), bytes.size(), lit_base, pool_base);
+    if (rc) return rc;
+    for (uint64_t r = 0; r < n; r++) if (post[r] != tk::EDIT_NONE) post[r] += lit_base;
+    for (size_t k = 0; k < ent.size(); k += 2) ent[k] += pool_base;
+    if (!ent.empty()) {
+        HIPCHK(ctx, hipMemcpyAsync(b->literals.as<uint64_t>() + 2ull * lit_base, ent.data(), ent.size() * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(b->litpool.as<uint8_t>() + pool_base, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s));
+    }
+    DevBuf d_post;
+    d_post.pooled = true; d_post.pool_stream = s;
+    HIPCHK(ctx, d_post.ensure(n * 4 + 16));
+    if (n) HIPCHK(ctx, hipMemcpyAsync(d_post.p, post.data(), n * 4, hipMemcpyHostToDevice, s));
+    if ((rc = edit_apply(ctx, in, nullptr, d_post.as<uint32_t>(), nullptr, b.get()))) return rc;
+    return edit_finish(ctx, b, out);
+}
+
+int tksmseq_flip(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_flip_params* p, tksmseq_batch** out) {
+    if (!ctx || !in || !p || !out) return TKSMSEQ_EINVAL;
+    *out = nullptr;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint64_t n = in->n_reads;
+    std::unique_ptr<tksmseq_batch> b(new tksmseq_batch());
+    int rc = copy_literals(ctx, in, b.get());
+    if (rc) return rc;
+    DevBuf d_flip;
+    d_flip.pooled = true; d_flip.pool_stream = s;
+    HIPCHK(ctx, d_flip.ensure(n + 16));
+    HIPCHK(ctx, tk::launch_flip_plan(n, p->seed, p->flip_probability, p->first_molecule_index, d_flip.as<uint8_t>(), s));
+    if ((rc = edit_apply(ctx, in, nullptr, nullptr, d_flip.as<uint8_t>(), b.get()))) return rc;
+    edit_comments(in, b.get(), p->flags);
+    return edit_finish(ctx, b, out);
 }
 
 int tksmseq_batch_to_mdf_text(tksmseq_ctx* ctx, const tksmseq_batch* b, char** text, uint64_t* len) {

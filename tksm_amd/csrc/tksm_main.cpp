@@ -1,7 +1,8 @@
 // tksm_main.cpp -- minimal dispatcher with the reference's calling convention (src/tksm.cpp:118-200):
 // `tksm sequence [args]` constructs the module with (argc - 1, argv + 1) and returns run().
-// This build provides the Seq exit module and the two modules upstream of it in BASELINE config 5 (pcr, truncate); every other
-// module name is reported as unknown.
+// This build provides the Seq exit module, the two modules upstream of it in BASELINE config 5 (pcr, truncate) and the segment edits
+// of the single-cell route (polyA, tag, scb, flip; spelled as src/tksm.cpp:146-161 spells them); every other module name is reported
+// as unknown.
 #include <cstdio>
 #include <cstring>
 
@@ -13,7 +14,11 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[1], "sequence")) return Sequencer_module{argc - 1, argv + 1}.run();
     if (!strcmp(argv[1], "pcr")) return tksmseq_pcr_main(argc - 1, argv + 1);
     if (!strcmp(argv[1], "truncate")) return tksmseq_truncate_main(argc - 1, argv + 1);
-    if (!strcmp(argv[1], "list")) { printf("sequence\npcr\ntruncate\n"); return 0; }
-    fprintf(stderr, "Unknown kisim: %s (this build provides `sequence`, `pcr` and `truncate`)\n", argv[1]);
+    if (!strcmp(argv[1], "polyA")) return tksmseq_polya_main(argc - 1, argv + 1);
+    if (!strcmp(argv[1], "tag")) return tksmseq_tag_main(argc - 1, argv + 1);
+    if (!strcmp(argv[1], "scb")) return tksmseq_scb_main(argc - 1, argv + 1);
+    if (!strcmp(argv[1], "flip")) return tksmseq_flip_main(argc - 1, argv + 1);
+    if (!strcmp(argv[1], "list")) { printf("sequence\npcr\ntruncate\npolyA\ntag\nscb\nflip\n"); return 0; }
+    fprintf(stderr, "Unknown kisim: %s (this build provides `sequence`, `pcr`, `truncate`, `polyA`, `tag`, `scb` and `flip`)\n", argv[1]);
     return 1;
 }

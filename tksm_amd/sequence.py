@@ -271,6 +271,55 @@ class Sequencer:
         self._chk(self._lib.tksmseq_truncate(self._ctx, batch._h, C.byref(p), C.byref(h)))
         return Batch(self, h)
 
+    # ---- segment edits of the single-cell route (device to device)
+    def polya(self, batch, gamma=None, poisson=None, weibull=None, normal=None, min_length=0, max_length=5000, seed=42,
+              first_molecule_index=0, comments=True):
+        """add_polyA (src/polyA.cpp:133-148) on the device: exactly one of gamma=(shape, scale), poisson=lam, weibull=(shape, scale),
+        normal=(mu, sigma)."""
+        given = [(d, v) for d, v in ((L.PLA_GAMMA, gamma), (L.PLA_POISSON, poisson), (L.PLA_WEIBULL, weibull), (L.PLA_NORMAL, normal))
+                 if v is not None]
+        if len(given) != 1:
+            raise ValueError("No distribution specified" if not given else "Multiple distributions specified")
+        dist, v = given[0]
+        a, b = (float(v), 0.0) if dist == L.PLA_POISSON else (float(v[0]), float(v[1]))
+        p = L.PolyaParams(seed, first_molecule_index, dist, 0 if comments else L.MOL_NO_COMMENTS, a, b, min_length, max_length)
+        h = C.c_void_p()
+        self._chk(self._lib.tksmseq_polya(self._ctx, batch._h, C.byref(p), C.byref(h)))
+        return Batch(self, h)
+
+    def tag(self, batch, format5="", format3="", seed=42, first_molecule_index=0, comments=True):
+        """TAG_module::run (src/tag.cpp:70-113) on the device; a format that starts with a digit is that many N's, as the CLI does."""
+        def digits(f):
+            if f and f[0].isdigit():
+                n = 0
+                for ch in f:
+                    if not ch.isdigit():
+                        break
+                    n = 10 * n + int(ch)
+                return "N" * n
+            return f
+        format5, format3 = digits(format5 or ""), digits(format3 or "")
+        if not format5 and not format3:
+            raise ValueError("At least one of the TAG formats must be provided")
+        p = L.TagParams(seed, first_molecule_index, format5.encode(), format3.encode(), 0 if comments else L.MOL_NO_COMMENTS, 0)
+        h = C.c_void_p()
+        self._chk(self._lib.tksmseq_tag(self._ctx, batch._h, C.byref(p), C.byref(h)))
+        return Batch(self, h)
+
+    def scb(self, batch, keep_meta_barcodes=False, comments=True):
+        """SingleCellBarcoder_module::run (src/scb.cpp:57-80) on the device: the CB barcode appended as a segment."""
+        p = L.ScbParams(1 if keep_meta_barcodes else 0, 0 if comments else L.MOL_NO_COMMENTS)
+        h = C.c_void_p()
+        self._chk(self._lib.tksmseq_scb(self._ctx, batch._h, C.byref(p), C.byref(h)))
+        return Batch(self, h)
+
+    def flip(self, batch, p, seed=42, first_molecule_index=0, comments=True):
+        """StrandMan_module (src/strand_man.cpp:37-46) on the device: each molecule flipped with probability p."""
+        q = L.FlipParams(seed, first_molecule_index, float(p), 0 if comments else L.MOL_NO_COMMENTS, 0)
+        h = C.c_void_p()
+        self._chk(self._lib.tksmseq_flip(self._ctx, batch._h, C.byref(q), C.byref(h)))
+        return Batch(self, h)
+
     def to_mdf_text(self, batch):
         """molecule_descriptor::operator<< of every molecule (src/interval.h:898-905)."""
         t, n = C.c_void_p(), C.c_uint64()
