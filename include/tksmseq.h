@@ -257,6 +257,37 @@ int tksmseq_result_download_range(tksmseq_ctx* ctx, uint8_t* dst, uint64_t offse
 /* Device-to-device copies of the last result into caller buffers (either may be NULL): records_bytes bytes and
  * n_reads + 1 u64 offsets.  Asynchronous on the context's stream. */
 int tksmseq_result_copy_device(tksmseq_ctx* ctx, void* records_dst, void* offsets_dst);
+/* ---- BGZF on the device ------------------------------------------------------------------------
+ * A record stream compressed where it was made: a sequence of BGZF members (SAM specification 4.1, what `bgzip` writes -- gzip members
+ * with the 'BC' extra subfield), member c holding bytes [65280 c, 65280 (c + 1)) of the input whatever the record boundaries, at most
+ * 65536 bytes each.  Every gzip reader reads the result; the members of several calls concatenate, and a file is closed by the 28
+ * bytes of tksmseq_gzip_eof (never appended here).  The encoder is FASTQ-aware Huffman coding plus byte runs, not LZ77: header,
+ * sequence and quality lines get deflate blocks and code tables of their own.  The bytes are a pure function of the
+ * input bytes and the format.  The compressed buffer lives until the next tksmseq_run or gzip call on the context. */
+#define TKSMSEQ_GZIP_RAW 0      /* any bytes: one code table per member */
+#define TKSMSEQ_GZIP_FASTA 1    /* records of two lines */
+#define TKSMSEQ_GZIP_FASTQ 2    /* records of four lines */
+typedef struct {
+    const void* data;             /* device pointer, `bytes` bytes */
+    const void* member_offsets;   /* device u64[n_members + 1] */
+    uint64_t bytes;
+    uint64_t n_members;
+    float device_ms;              /* device time of the call by HIP events, 0 if timing is off */
+    float reserved;
+} tksmseq_gzip_result;
+/* Compresses the records of the last tksmseq_run on the context's stream; line classes follow that run's `fastq` flag. */
+int tksmseq_result_gzip(tksmseq_ctx* ctx, tksmseq_gzip_result* out);
+/* The same for any device bytes (e.g. an interleaved multi-GPU stream); format: TKSMSEQ_GZIP_*. */
+int tksmseq_gzip_device(tksmseq_ctx* ctx, const void* src_device, uint64_t bytes, int format, tksmseq_gzip_result* out);
+/* A slice of the last compressed stream to host memory, like tksmseq_result_download_range; member offsets (n_members + 1) if asked for. */
+int tksmseq_gzip_download_range(tksmseq_ctx* ctx, uint8_t* dst, uint64_t offset, uint64_t bytes, int async);
+int tksmseq_gzip_download_offsets(tksmseq_ctx* ctx, uint64_t* offsets);
+/* Device-to-device copy of the last compressed stream (asynchronous on the context's stream): what a writer keeps while the context
+ * runs its next batch. */
+int tksmseq_gzip_copy_device(tksmseq_ctx* ctx, void* dst);
+/* The empty member that ends a BGZF file. */
+int tksmseq_gzip_eof(uint8_t out[28]);
+
 /* Per-read debug statistics of the last badread run with collect_stats = 1: int32[n_reads][16]
  * {n_draws, change_count, n_aligns, frag_len, new_len, start_trim, end_trim, status, ...} +
  * double[n_reads][2] {errors, target_identity}. */

@@ -32,6 +32,14 @@ class Result(C.Structure):
                 ("kernel_ms", C.c_float * 8)]
 
 
+class GzipResult(C.Structure):            # tksmseq_gzip_result
+    _fields_ = [("data", C.c_void_p), ("member_offsets", C.c_void_p), ("bytes", C.c_uint64), ("n_members", C.c_uint64),
+                ("device_ms", C.c_float), ("reserved", C.c_float)]
+
+
+GZIP_RAW, GZIP_FASTA, GZIP_FASTQ = 0, 1, 2
+
+
 class TailModelDesc(C.Structure):            # tksmseq_tail_model
     _fields_ = [("n_lx", C.c_uint32), ("n_ly", C.c_uint32), ("lx", C.c_void_p), ("ly", C.c_void_p), ("grid", C.c_void_p),
                 ("trans", C.c_double * 16), ("ratio", C.c_double), ("bases", C.c_uint8 * 4), ("pad", C.c_uint8 * 4)]
@@ -88,6 +96,8 @@ SYMBOLS = [
     "tksmseq_molecules_from_mdf_text", "tksmseq_pcr_main", "tksmseq_truncate_main", "tksmseq_run_diagnostics",
     "tksmseq_polya", "tksmseq_tag", "tksmseq_scb", "tksmseq_flip",
     "tksmseq_polya_main", "tksmseq_tag_main", "tksmseq_scb_main", "tksmseq_flip_main",
+    "tksmseq_result_gzip", "tksmseq_gzip_device", "tksmseq_gzip_download_range", "tksmseq_gzip_download_offsets",
+    "tksmseq_gzip_copy_device", "tksmseq_gzip_eof",
 ]
 
 _lib = None
@@ -158,6 +168,12 @@ def load():
         "tksmseq_stats_download": (C.c_int, [vp, vp, vp]),
         "tksmseq_interleave_records": (C.c_int, [vp, C.c_int, P(vp), P(vp), P(u64), vp, u64, P(u64)]),
         "tksmseq_sequence_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
+        "tksmseq_result_gzip": (C.c_int, [vp, P(GzipResult)]),
+        "tksmseq_gzip_device": (C.c_int, [vp, vp, u64, C.c_int, P(GzipResult)]),
+        "tksmseq_gzip_download_range": (C.c_int, [vp, vp, u64, u64, C.c_int]),
+        "tksmseq_gzip_download_offsets": (C.c_int, [vp, vp]),
+        "tksmseq_gzip_copy_device": (C.c_int, [vp, vp]),
+        "tksmseq_gzip_eof": (C.c_int, [vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

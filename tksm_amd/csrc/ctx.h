@@ -226,6 +226,11 @@ struct tksmseq_ctx : ContigLookup {
     hipEvent_t ev[6] = {};
     tksmseq_result last{};
     bool have_last = false, have_stats = false;
+    // device-side BGZF (gzip_api.cpp): per-chunk tables, and the compressed stream of the last gzip call (from DevCache: its size changes
+    // with every batch)
+    DevBuf g_counts, g_nlscan, g_sizes, g_offs, g_plans, g_out;
+    tksmseq_gzip_result last_gzip{};
+    bool have_gzip = false, last_fastq = false;   // last_fastq: the record format of `last`
 
     int find(const std::string& name) const override {
         auto it = contig_index.find(name);

@@ -50,6 +50,7 @@ struct Args {
     std::vector<std::string> references;
     bool skip_qual = false, list = false, help = false;
     int threads = 1, in_flight = 3;
+    std::string gzip = "host";                           // --gzip host|device: where a .gz output is compressed
     std::vector<int> devices{0};
     long long seed = 42;
     uint64_t batch_bytes = 64ull << 20;
@@ -74,7 +75,8 @@ void usage(FILE* f) {
             "usage: sequence [-h] -i INPUT [-r REFERENCES [REFERENCES ...]] [-o BADREAD] [--perfect PERFECT]\n"
             "                [--skip-qual-compute] [-O {fastq,fasta}] [-t THREADS] [--badread-identity BADREAD_IDENTITY]\n"
             "                [--badread-error-model M] [--badread-qscore-model M] [--badread-tail-model M] [--list]\n"
-            "                [-s SEED] [--devices D[,D...]] [--batch-bytes B] [--in-flight N] [--verbosity L] [--log-file F]\n"
+            "                [-s SEED] [--devices D[,D...]] [--batch-bytes B] [--in-flight N] [--gzip {host,device}] [--verbosity L]\n"
+            "                [--log-file F]\n"
             "                [--pcr-cycles C --pcr-molecule-count N (--pcr-preset X | --pcr-error-rate E --pcr-efficiency F)]\n"
             "                [--truncate-normal MU,SIGMA | --truncate-lognormal MU,SIGMA | --truncate-kde-model M.json\n"
             "                 [--truncate-always-end] [--truncate-kde-models-length]]\n");
@@ -96,6 +98,7 @@ bool gzip_member(const uint8_t* d, size_t n, std::vector<uint8_t>& out) {
 
 struct Writer {
     int fd = -1; bool gz = false, fastq = false, wrote = false;
+    bool bgzf = false;                                   // --gzip device: the bytes are BGZF members made on the device; close() ends the file
     bool positional = false;                             // a regular file: the workers write their batches at their offsets (pwrite)
     void classify(const std::string& path) {             // get_output_file, py/sequence.py:291-300: the NAME decides format and compression
         std::string p = path;
@@ -132,7 +135,11 @@ struct Writer {
     bool close() {                                       // false: the last bytes could not be written
         if (fd < 0) return true;
         bool ok = true;
-        if (gz && !wrote) { std::vector<uint8_t> e; if (gzip_member(nullptr, 0, e)) ok = write(e.data(), e.size()); }   // a valid empty .gz
+        if (gz && bgzf) {                                // the EOF member, behind everything the run has written (an empty run: it alone)
+            uint8_t e[28];
+            tksmseq_gzip_eof(e);
+            ok = (!positional || lseek(fd, 0, SEEK_END) >= 0) && write(e, sizeof e);
+        } else if (gz && !wrote) { std::vector<uint8_t> e; if (gzip_member(nullptr, 0, e)) ok = write(e.data(), e.size()); }   // a valid empty .gz
         ok = ::close(fd) == 0 && ok;
         fd = -1;
         return ok;
@@ -220,7 +227,7 @@ const OptSpec LONG_OPTS[] = {
     {"--help", false}, {"--input", true}, {"--references", true}, {"--badread", true}, {"--perfect", true}, {"--skip-qual-compute", false},
     {"--output-format", true}, {"--threads", true}, {"--badread-identity", true}, {"--badread-error-model", true},
     {"--badread-qscore-model", true}, {"--badread-tail-model", true}, {"--list", false}, {"--seed", true}, {"--devices", true},
-    {"--batch-bytes", true}, {"--in-flight", true}, {"--pcr-cycles", true}, {"--pcr-molecule-count", true}, {"--pcr-error-rate", true},
+    {"--batch-bytes", true}, {"--in-flight", true}, {"--gzip", true}, {"--pcr-cycles", true}, {"--pcr-molecule-count", true}, {"--pcr-error-rate", true},
     {"--pcr-efficiency", true}, {"--pcr-preset", true}, {"--pcr-slice-molecules", true}, {"--truncate-normal", true},
     {"--truncate-lognormal", true}, {"--truncate-kde-model", true}, {"--truncate-always-end", false},
     {"--truncate-kde-models-length", false}, {"--verbosity", true}, {"--log-file", true}};
@@ -308,6 +315,7 @@ class Sequencer_module::impl {
                 a.in_flight = atoi(v);
                 if (a.in_flight < 1) { usage(stderr); fprintf(stderr, "sequence: error: argument --in-flight: expected a positive integer, got '%s'\n", v); return 2; }
             }
+            else if (o == "--gzip") { if (!(v = need(i))) return 2; a.gzip = v; }
             else if (o == "--pcr-cycles") { if (!(v = need(i))) return 2; a.pcr.cycles = atoi(v); a.pcr_have_cycles = true; }
             else if (o == "--pcr-molecule-count") { if (!(v = need(i))) return 2; a.pcr.target_count = strtoull(v, nullptr, 10); a.pcr_have_count = true; }
             else if (o == "--pcr-error-rate") { if (!(v = need(i))) return 2; a.pcr.error_rate = atof(v); a.pcr_have_er = true; }
@@ -386,6 +394,7 @@ public:
             if (missing) return 1;
             a.pcr.seed = (uint64_t)a.seed;
         }
+        if (a.gzip != "host" && a.gzip != "device") return die("Error: --gzip must be 'host' or 'device', got '" + a.gzip + "'");
         if (a.trc_n > 1) return die("Only one of kde-model, normal or lognormal is allowed!");
         if (a.trc_n == 1) { a.trc.seed = (uint64_t)a.seed; if (a.trc.mode == TKSMSEQ_TRC_KDE) a.trc.kde_model_path = a.trc_kde.c_str(); }
 
@@ -413,6 +422,7 @@ public:
         bool compute_q = false;
         if (!a.badread.empty()) { wb.classify(a.badread); compute_q = !a.skip_qual && wb.fastq; }
         if (!a.perfect.empty()) wp.classify(a.perfect);
+        const bool gzip_device = a.gzip == "device";
         if (!a.badread.empty() && !a.perfect.empty())
             log.log(Logger::WARN, "with both -o and --perfect the reference writes the badread sequence (quals 'K') to the "
                                   "--perfect file (py/sequence.py:317-319); reproduced here");
@@ -505,6 +515,7 @@ public:
         { struct stat st_in; in_regular = fstat(in_fd, &st_in) == 0 && S_ISREG(st_in.st_mode); }
         if (!a.badread.empty() && !wb.open(a.badread)) { fclose(in); destroy_all(); return die("Error: cannot open " + a.badread); }
         if (!a.perfect.empty() && !wp.open(a.perfect)) { fclose(in); wb.close(); destroy_all(); return die("Error: cannot open " + a.perfect); }
+        wb.bgzf = wb.gz && gzip_device; wp.bgzf = wp.gz && gzip_device;
         ChunkQueue queue;
         queue.cap = (size_t)n_workers;
         std::vector<std::unique_ptr<ParsedQueue>> pq;
@@ -531,7 +542,9 @@ public:
         // the device, and a writer thread per worker streams them out -- at their place in a regular file, in batch order into
         // anything else -- while the worker's context runs its next batch.  (.gz outputs keep whole-batch host buffers: the members
         // are compressed side by side.)
-        const bool behind = (a.badread.empty() || !wb.gz) && (a.perfect.empty() || !wp.gz);
+        // With --gzip device a .gz output goes the same way: the batch is compressed on the device, and the compressed stream is just bytes
+        // of known size.
+        const bool behind = (a.badread.empty() || !wb.gz || wb.bgzf) && (a.perfect.empty() || !wp.gz || wp.bgzf);
         uint64_t written_upto[2] = {0, 0};                                                          // non-seekable outputs: batches written; guarded by done_m
         uint64_t next_place[2] = {0, 0}, place[2] = {0, 0};                                        // per output; guarded by done_m
         // stage clocks (TKSMSEQ_VERBOSE): seconds spent parsing, running, copying, writing, reading
@@ -628,14 +641,23 @@ public:
                                           std::chrono::duration<double>(now() - t_run).count(), (unsigned long long)n, std::chrono::duration<double>(now() - t_start).count());
                     Writer& wr = k == 0 ? wb : wp;
                     if (behind || (positional && !wr.gz)) {
+                        // what goes out: the records, or (--gzip device) their BGZF members
+                        uint64_t out_bytes = r.records_bytes;
+                        if (wr.bgzf) {
+                            tksmseq_gzip_result g{};
+                            const auto t_gz = now();
+                            if (tksmseq_result_gzip(W.ctx, &g)) { set_error(tksmseq_last_error(W.ctx)); return false; }
+                            add_clk(1, t_gz);
+                            out_bytes = g.bytes;
+                        }
                         // an uncompressed output (or the plain regular file next to a .gz one); a regular file: the batch's place in it is known as soon as every earlier batch has announced
                         // its size (writes into ONE file are serialised by the file system: 11 - 13.5 GB/s on the test box whatever
                         // the number of threads, tools/fs_write_probe.py -- the bound of the end-to-end rate)
                         uint64_t off = 0;
-                        if (!take_place(k, c.seq, r.records_bytes, n, off)) return false;
+                        if (!take_place(k, c.seq, out_bytes, n, off)) return false;
                         // (blocks allocated ahead of the writes: the writes into one file are serialised by the file system, and
                         // the allocation would happen inside them -- 12 -> 13.5 GB/s on the test box, tools/fs_write_probe.py)
-                        if (r.records_bytes && wr.positional) (void)posix_fallocate(wr.fd, (off_t)off, (off_t)r.records_bytes);
+                        if (out_bytes && wr.positional) (void)posix_fallocate(wr.fd, (off_t)off, (off_t)out_bytes);
                         // the records move into a staging buffer of the writer thread's (device to device), which streams them
                         // out while this context runs its next batch
                         const auto t_copy = now();
@@ -648,12 +670,12 @@ public:
                             W.stage_busy[q] = true;
                             W.cur_stage ^= 1;
                         }
-                        if (!W.stage_reserve(q, r.records_bytes)) { set_error("out of device memory for the output staging buffers"); return false; }
-                        if (r.records_bytes && (tksmseq_result_copy_device(W.ctx, W.stage[q], nullptr) || tksmseq_synchronize(W.ctx))) { set_error(tksmseq_last_error(W.ctx)); return false; }
+                        if (!W.stage_reserve(q, out_bytes)) { set_error("out of device memory for the output staging buffers"); return false; }
+                        if (out_bytes && ((wr.bgzf ? tksmseq_gzip_copy_device(W.ctx, W.stage[q]) : tksmseq_result_copy_device(W.ctx, W.stage[q], nullptr)) || tksmseq_synchronize(W.ctx))) { set_error(tksmseq_last_error(W.ctx)); return false; }
                         add_clk(2, t_copy);
-                        { std::lock_guard<std::mutex> l(W.m); Worker::Job j; j.stage = q; j.k = k; j.bytes = r.records_bytes; j.off = off; j.seq = c.seq; W.jobs.push_back(j); }
+                        { std::lock_guard<std::mutex> l(W.m); Worker::Job j; j.stage = q; j.k = k; j.bytes = out_bytes; j.off = off; j.seq = c.seq; W.jobs.push_back(j); }
                         W.cv.notify_all();
-                        fin.bytes[k] = r.records_bytes;
+                        fin.bytes[k] = out_bytes;
                         return true;
                     }
                     const auto t_wait = now();

@@ -19,6 +19,9 @@ import numpy as np
 
 from . import _lib as L
 
+# the empty member that ends a BGZF file (SAM specification 4.1.2); tksmseq_gzip_eof returns the same 28 bytes
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
 
 class TksmSeqError(RuntimeError):
     def __init__(self, code, msg):
@@ -72,6 +75,13 @@ class RunResult:
     def records(self):
         rec, off = self.download()
         return [rec[int(off[i]):int(off[i + 1])] for i in range(self.n_reads)]
+
+    def gzip(self, with_info=False):
+        """The records as BGZF members compressed on the device (tksmseq_result_gzip): bytes that every gzip reader reads; members
+        of several batches concatenate, a file ends with BGZF_EOF.  with_info: (bytes, member offsets u64[n + 1], device ms)."""
+        g = L.GzipResult()
+        self._seq._chk(self._seq._lib.tksmseq_result_gzip(self._seq._ctx, C.byref(g)))
+        return self._seq._gzip_fetch(g, with_info)
 
     def stats(self):
         ist = np.empty((self.n_reads, 16), np.int32)
@@ -352,6 +362,22 @@ class Sequencer:
             return self.run(b, target=target, **kw).records()
         finally:
             b.free()
+
+    def _gzip_fetch(self, g, with_info):
+        out = np.empty(g.bytes, np.uint8)
+        self._chk(self._lib.tksmseq_gzip_download_range(self._ctx, out.ctypes.data, 0, g.bytes, 0))
+        if not with_info:
+            return out.tobytes()
+        off = np.empty(g.n_members + 1, np.uint64)
+        self._chk(self._lib.tksmseq_gzip_download_offsets(self._ctx, off.ctypes.data))
+        return out.tobytes(), off, g.device_ms
+
+    def gzip_device(self, ptr, nbytes, format=L.GZIP_RAW, with_info=False):
+        """BGZF members of `nbytes` device bytes at `ptr` (tksmseq_gzip_device); format: "raw" / "fasta" / "fastq" or GZIP_*."""
+        fmt = {"raw": L.GZIP_RAW, "fasta": L.GZIP_FASTA, "fastq": L.GZIP_FASTQ}.get(format, format)
+        g = L.GzipResult()
+        self._chk(self._lib.tksmseq_gzip_device(self._ctx, C.c_void_p(ptr) if ptr else None, nbytes, fmt, C.byref(g)))
+        return self._gzip_fetch(g, with_info)
 
     def set_host_threads(self, n):
         """host threads of the MDF parser and writer (tksmseq_set_host_threads; the CLI's -t)"""
