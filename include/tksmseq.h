@@ -102,6 +102,10 @@ int tksmseq_reference_add_fasta(tksmseq_ctx* ctx, const char* path /* .fa / .fa.
 int tksmseq_reference_add_contig(tksmseq_ctx* ctx, const char* name, const uint8_t* ascii, uint64_t len,
                                  int on_device);
 int tksmseq_reference_contig_id(const tksmseq_ctx* ctx, const char* name);   /* -1 if absent */
+/* A contig known by name and length only -- what `<reference>.fai` gives (src/random_wgs.cpp:139-161 reads nothing else).  tksmseq_wgs and
+ * the MDF writer work on a context with declared contigs; tksmseq_run on it fails with TKSMSEQ_ESTATE (there are no bases to read).
+ * A later tksmseq_reference_add_contig of the same name supplies the bases. */
+int tksmseq_reference_declare_contig(tksmseq_ctx* ctx, const char* name, uint64_t len);
 int tksmseq_reference_info(const tksmseq_ctx* ctx, uint64_t* n_contigs, uint64_t* total_bases,
                            uint64_t* device_bytes);
 
@@ -424,6 +428,48 @@ typedef struct {
 } tksmseq_flip_params;
 int tksmseq_flip(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_flip_params* params, tksmseq_batch** out);
 
+/* ---- random-wgs: whole-genome fragments made on the device ---------------------------------------------------------------------------
+ * tksmseq_wgs replaces the loop of RWGS_module::run (src/random_wgs.cpp:181-207; position_dist / frag_length_dist / strand_dist, the
+ * contig look-up :190-194, the clip to the contig end :195-198, the molecule :200-204, the stop rule :188, :205).  There is no input
+ * batch: CANDIDATE c = 0, 1, 2, ... of the run draws, from Philox keyed by (seed, c), a position uniform on [0, ref_length - 1] (the
+ * contig is the first whose running sum of lengths reaches it, ref_pos = pos - so_far + len, as the reference computes them), a length
+ * from the named distribution (std:: parameterisation: normal(a, b), uniform real on [a, b), lognormal(a, b) = exp of the normal,
+ * exponential(a)), clamped in double to the int range (NaN: 0), truncated toward zero and clipped to the contig end, and a strand.  A
+ * candidate is EMITTED when its clipped length is at least 1 (the reference also writes empty and inverted intervals, which no later
+ * module handles).  Candidates are taken in order while the bases of the emitted candidates before them are below base_count: the output
+ * of a run is a prefix of its emitted candidates, its total at least base_count and below it without the last molecule; base_count <= 0
+ * gives nothing.  Molecule: id "{index}_{contig}:{ref_pos}-{ref_pos + len}{+|-}" (index: position among the emitted molecules of the
+ * whole run), depth 1, no comment, one segment without substitutions.
+ * A call covers candidates [first_candidate, first_candidate + n_candidates) and carries the run's state in and out, so that consecutive
+ * calls, one after the other, give the output of one call over the whole range: results depend on (seed, candidate index) and on prefix
+ * sums only.  The contig table is the context's reference in the order its contigs were added (with or without bases).  *out is an
+ * ordinary batch (possibly empty; free with tksmseq_batch_free).  A call whose candidates emit nothing returns normally (progress shows
+ * it): a caller that loops must stop by itself when whole calls stay empty (`exponential 1000`: every draw below one base).
+ * TKSMSEQ_EINVAL: unknown distribution, non-finite a or b, a <= 0 or b < 0 (refused by the reference, :122), uniform with b < a;
+ * TKSMSEQ_ESTATE: no contigs, or none with a base; TKSMSEQ_ELIMIT: a contig of 2^31 bases or more, more than 2^28 candidates per call. */
+#define TKSMSEQ_WGS_NORMAL 0
+#define TKSMSEQ_WGS_UNIFORM 1
+#define TKSMSEQ_WGS_LOGNORMAL 2
+#define TKSMSEQ_WGS_EXPONENTIAL 3
+typedef struct {
+    uint64_t seed;
+    int32_t dist;                    /* TKSMSEQ_WGS_* (--frag-len-dist "NAME A [B]") */
+    int32_t reserved;
+    double a, b;
+    int64_t base_count;              /* --base-count, or (int64)(depth x ref_length) for --depth */
+    uint64_t first_candidate;        /* index of this call's first candidate in the whole run (RNG key) */
+    uint64_t n_candidates;
+    uint64_t molecules_before;       /* carried state: molecules and bases emitted by the calls before this one (0, 0 at the start) */
+    uint64_t bases_before;
+} tksmseq_wgs_params;
+typedef struct {
+    uint64_t next_candidate;         /* the first candidate the next call takes (reached: one past the run's last molecule) */
+    uint64_t molecules, bases;       /* carried state after this call */
+    int32_t reached;                 /* 1: base_count was reached inside (or before) this call -- the run is complete */
+    int32_t reserved;
+} tksmseq_wgs_progress;
+int tksmseq_wgs(tksmseq_ctx* ctx, const tksmseq_wgs_params* params, tksmseq_batch** out, tksmseq_wgs_progress* progress);
+
 /* The batch as MDF text, the way molecule_descriptor::operator<< writes it (src/interval.h:898-905): "+id<TAB>depth<TAB>comment",
  * then "chr<TAB>start<TAB>end<TAB>strand<TAB>pos<base>,..." per segment; depth 1 per molecule; comments re-serialised key-sorted
  * like dump_comment (:880-890).  *text is malloc'ed: release with tksmseq_text_free. */
@@ -441,6 +487,10 @@ int tksmseq_polya_main(int argc, char** argv);
 int tksmseq_tag_main(int argc, char** argv);
 int tksmseq_scb_main(int argc, char** argv);
 int tksmseq_flip_main(int argc, char** argv);
+/* `tksm random-wgs` (RWGS_module src/random_wgs.cpp:24-229): -r/--reference, --frag-len-dist "NAME A [B]", -o/--output, --base-count |
+ * --depth, the reference's messages and exit codes; the contig table from <reference>.fai (from the FASTA itself when that is missing);
+ * MDF text out, streamed in batches of --batch-molecules candidates over --devices. */
+int tksmseq_random_wgs_main(int argc, char** argv);
 int tksmseq_sequence_main(int argc, char** argv);
 
 #ifdef __cplusplus

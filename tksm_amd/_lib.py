@@ -80,6 +80,21 @@ class FlipParams(C.Structure):
 
 
 PLA_GAMMA, PLA_POISSON, PLA_WEIBULL, PLA_NORMAL = 0, 1, 2, 3
+
+
+class WgsParams(C.Structure):                # tksmseq_wgs_params
+    _fields_ = [("seed", C.c_uint64), ("dist", C.c_int32), ("reserved", C.c_int32), ("a", C.c_double), ("b", C.c_double),
+                ("base_count", C.c_int64), ("first_candidate", C.c_uint64), ("n_candidates", C.c_uint64),
+                ("molecules_before", C.c_uint64), ("bases_before", C.c_uint64)]
+
+
+class WgsProgress(C.Structure):              # tksmseq_wgs_progress
+    _fields_ = [("next_candidate", C.c_uint64), ("molecules", C.c_uint64), ("bases", C.c_uint64), ("reached", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+WGS_NORMAL, WGS_UNIFORM, WGS_LOGNORMAL, WGS_EXPONENTIAL = 0, 1, 2, 3
+WGS_DISTS = {"normal": WGS_NORMAL, "uniform": WGS_UNIFORM, "lognormal": WGS_LOGNORMAL, "exponential": WGS_EXPONENTIAL}
 MOL_NO_COMMENTS = 1
 
 SYMBOLS = [
@@ -98,6 +113,7 @@ SYMBOLS = [
     "tksmseq_polya_main", "tksmseq_tag_main", "tksmseq_scb_main", "tksmseq_flip_main",
     "tksmseq_result_gzip", "tksmseq_gzip_device", "tksmseq_gzip_download_range", "tksmseq_gzip_download_offsets",
     "tksmseq_gzip_copy_device", "tksmseq_gzip_eof",
+    "tksmseq_reference_declare_contig", "tksmseq_wgs", "tksmseq_random_wgs_main",
 ]
 
 _lib = None
@@ -174,6 +190,9 @@ def load():
         "tksmseq_gzip_download_offsets": (C.c_int, [vp, vp]),
         "tksmseq_gzip_copy_device": (C.c_int, [vp, vp]),
         "tksmseq_gzip_eof": (C.c_int, [vp]),
+        "tksmseq_reference_declare_contig": (C.c_int, [vp, C.c_char_p, u64]),
+        "tksmseq_wgs": (C.c_int, [vp, P(WgsParams), P(vp), P(WgsProgress)]),
+        "tksmseq_random_wgs_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

@@ -71,6 +71,7 @@ int tksmseq_clone(const tksmseq_ctx* src, tksmseq_ctx** out) {
     tksmseq_ctx* c = *out;
     c->contig_names = src->contig_names; c->contig_index = src->contig_index; c->contigs = src->contigs;
     c->total_alloc = src->total_alloc; c->total_bases = src->total_bases; c->pool_blocks = src->pool_blocks;
+    c->contig_declared = src->contig_declared; c->n_declared = src->n_declared;
     c->d_packed.borrow(src->d_packed); c->d_blocktab.borrow(src->d_blocktab); c->d_pool.borrow(src->d_pool); c->d_contigs.borrow(src->d_contigs);
     c->em = src->em; c->qm = src->qm; c->idm = src->idm; c->em_uniform = src->em_uniform; c->em_alt0 = src->em_alt0;
     c->d_pself.borrow(src->d_pself); c->d_pseg.borrow(src->d_pseg); c->d_pt0.borrow(src->d_pt0); c->d_cdf32.borrow(src->d_cdf32); c->d_cdf.borrow(src->d_cdf); c->d_alts.borrow(src->d_alts); c->d_altenc.borrow(src->d_altenc);
@@ -197,12 +198,41 @@ int tksmseq_reference_add_contig(tksmseq_ctx* ctx, const char* name, const uint8
         ctx->contig_index[nm] = (int)ctx->contig_names.size();
         ctx->contig_names.push_back(nm);
         ctx->contigs.push_back(gstart); ctx->contigs.push_back(len);
+        ctx->contig_declared.push_back(0);
     } else {
         ctx->total_bases -= ctx->contigs[2 * it->second + 1];
         ctx->contigs[2 * it->second] = gstart; ctx->contigs[2 * it->second + 1] = len;
+        if (ctx->contig_declared[(size_t)it->second]) { ctx->contig_declared[(size_t)it->second] = 0; ctx->n_declared--; }   // (declared before: now it has bases)
     }
     ctx->total_alloc = gstart + nblk * BLK;
     ctx->total_bases += len;
+    ctx->ref_version++;
+    HIPCHK(ctx, ctx->d_contigs.ensure(ctx->contigs.size() * 8 + 16));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_contigs.p, ctx->contigs.data(), ctx->contigs.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return TKSMSEQ_OK;
+}
+
+int tksmseq_reference_declare_contig(tksmseq_ctx* ctx, const char* name, uint64_t len) {
+    if (!ctx || !name) return TKSMSEQ_EINVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (len > (1ull << 44)) { ctx->err = "reference larger than 2^44 bases"; return TKSMSEQ_ELIMIT; }
+    // name and length only: no packed bases behind it (gstart is never dereferenced: tksmseq_run refuses while n_declared > 0)
+    std::string nm(name);
+    auto it = ctx->contig_index.find(nm);
+    if (it == ctx->contig_index.end()) {
+        ctx->contig_index[nm] = (int)ctx->contig_names.size();
+        ctx->contig_names.push_back(nm);
+        ctx->contigs.push_back(ctx->total_alloc); ctx->contigs.push_back(len);
+        ctx->contig_declared.push_back(1);
+        ctx->n_declared++;
+    } else {
+        ctx->total_bases -= ctx->contigs[2 * it->second + 1];
+        ctx->contigs[2 * it->second + 1] = len;
+        if (!ctx->contig_declared[(size_t)it->second]) { ctx->contig_declared[(size_t)it->second] = 1; ctx->n_declared++; }
+    }
+    ctx->total_bases += len;
+    ctx->ref_version++;
     HIPCHK(ctx, ctx->d_contigs.ensure(ctx->contigs.size() * 8 + 16));
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_contigs.p, ctx->contigs.data(), ctx->contigs.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1229,6 +1259,7 @@ int tksmseq_run(tksmseq_ctx* ctx, const tksmseq_batch* batch, const tksmseq_run_
         if (!ctx->idm.set) { ctx->err = "identity distribution not set"; return TKSMSEQ_ESTATE; }
         if (p->compute_qual && p->fastq && ctx->qm.n_slots == 0) { ctx->err = "no q-score model loaded"; return TKSMSEQ_ESTATE; }
     }
+    if (ctx->n_declared) { ctx->err = "the reference holds contigs declared without bases (tksmseq_reference_declare_contig): there is nothing to sequence from"; return TKSMSEQ_ESTATE; }
     tksmseq_batch* b = const_cast<tksmseq_batch*>(batch);
     bool overflow = false;
     memset(ctx->last_diag, 0, sizeof(ctx->last_diag));

@@ -186,6 +186,11 @@ struct tksmseq_ctx : ContigLookup {
     uint64_t total_alloc = 0;             // bases allocated in the global coordinate (block aligned)
     uint64_t total_bases = 0;
     uint32_t pool_blocks = 0;
+    // contigs declared by name and length only (tksmseq_reference_declare_contig): tksmseq_run refuses while there are any
+    std::vector<uint8_t> contig_declared; uint32_t n_declared = 0;
+    // random-wgs: the contig table as its kernels read it (running sums, names), rebuilt when the reference has changed
+    uint64_t ref_version = 0, wgs_version = ~0ull;
+    DevBuf d_wgs_sofar, d_wgs_nameoff, d_wgs_namelen, d_wgs_names;
     DevBuf d_packed, d_blocktab, d_pool, d_contigs, d_stage;
 
     // models

@@ -95,4 +95,23 @@ hipError_t launch_edit_count(const MolView& m, const uint32_t* pre, const uint32
 hipError_t launch_edit_write(const MolView& m, const uint32_t* pre, const uint32_t* post, const uint8_t* flip, const uint64_t* lits,
                              const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off, const MolOut& o, hipStream_t s);
 
+// random-wgs (src/random_wgs.cpp:181-207): fragments of the whole genome, one lane per candidate; see mdf_kernels.hip
+constexpr int WGS_LDS_CONTIGS = 2048;       // running sums of that many contigs are searched in LDS (16 KB), more in global memory
+enum { WGS_NORMAL = 0, WGS_UNIFORM = 1, WGS_LOGNORMAL = 2, WGS_EXPONENTIAL = 3 };
+struct WgsParams {
+    uint64_t seed;
+    int dist;                             // WGS_*
+    double a, b;                          // normal / lognormal (mean, sigma), uniform [a, b), exponential (rate, -)
+    uint64_t ref_length;                  // sum of the contig lengths (> 0)
+    uint32_t n_contigs;
+};
+// plan[t] = {contig, ref_pos, clipped length (0: not emitted), strand minus}; flag / bases: what launch_scan ranks and sums
+hipError_t launch_wgs_plan(const WgsParams& p, const uint64_t* so_far, uint64_t first, uint64_t n, uint4* plan, uint64_t* flag, uint64_t* bases, hipStream_t s);
+// idlen[t]: id bytes of a candidate inside the run's prefix (0: outside, or not emitted); cut[4] (zeroed by the caller) = {molecules, bases,
+// candidates consumed, 1} when base_count is reached inside the call
+hipError_t launch_wgs_cut(uint64_t n, const uint4* plan, const uint64_t* rank, const uint64_t* bsum, const uint32_t* name_len, uint64_t mols_before,
+                          uint64_t bases_before, uint64_t base_count, uint64_t* idlen, uint64_t* cut, hipStream_t s);
+hipError_t launch_wgs_write(uint64_t n, const uint4* plan, const uint64_t* rank, const uint64_t* idlen, const uint64_t* id_off, const uint32_t* name_off,
+                            const uint32_t* name_len, const uint8_t* names, uint64_t mols_before, const MolOut& o, hipStream_t s);
+
 }  // namespace tk

@@ -11,6 +11,7 @@
 //   TAG_module::run              src/tag.cpp:70-113       prepend / append a tag drawn from an IUPAC format (fmt2seq, src/util.h:53-92)
 //   SingleCellBarcoder::run      src/scb.cpp:57-80        append the CB barcode of the header comment
 //   flip_molecule                src/interval.h:908-920   reverse the segment order, toggle every strand
+//   RWGS_module::run             src/random_wgs.cpp:181-207 whole-genome fragments: position, length and strand draws, no input
 // Integer / byte work, one LANE per molecule: the tables of a molecule are a few dozen bytes, the work per molecule is a short
 // serial walk (tree of copies; list of segments).  The reference draws from a sequential Mersenne Twister; here every
 // decision has its own Philox counter (template molecule, path of copy cycles, purpose), so the result does not depend on
@@ -23,7 +24,7 @@ namespace tk {
 
 struct Ph4m { uint32_t x, y, z, w; };
 enum { ST_PCR_PICK = 16, ST_PCR_EMIT = 17, ST_PCR_CHILD = 18, ST_PCR_MUT = 19, ST_TRC_LEN = 24, ST_TRC_SIDE = 25,
-       ST_PLA_LEN = 26, ST_TAG5 = 27, ST_TAG3 = 28, ST_FLIP = 29 };
+       ST_PLA_LEN = 26, ST_TAG5 = 27, ST_TAG3 = 28, ST_FLIP = 29, ST_WGS_POS = 32, ST_WGS_LEN = 33, ST_WGS_STRAND = 34 };
 
 DEV Ph4m philox_raw(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
@@ -559,6 +560,98 @@ __global__ void k_edit_write(MolView M, const uint32_t* __restrict__ pre, const 
 }
 
 // ------------------------------------------------------------------------------------------------
+// random-wgs (src/random_wgs.cpp:181-207): molecules made here, not read.  One lane per CANDIDATE c (0, 1, 2, ... over the whole run): a
+// uniform position on the concatenated contigs, a length from the named distribution clipped to the contig end, a strand.  A candidate
+// whose clipped length is at least 1 is emitted; the run's output is the prefix of the emitted candidates whose bases before them are
+// below base_count.  k_wgs_plan draws; launch_scan ranks the emitted ones and sums their bases; k_wgs_cut finds the end of the prefix and
+// sizes the ids (the molecule index is the rank: known only after the scan); k_wgs_write fills the tables.
+// ------------------------------------------------------------------------------------------------
+DEV double u53(uint32_t hi, uint32_t lo) { return (double)(((unsigned long long)hi << 21) | (lo >> 11)) * (1.0 / 9007199254740992.0); }            // [0, 1)
+DEV double u53o(uint32_t hi, uint32_t lo) { return ((double)(((unsigned long long)hi << 21) | (lo >> 11)) + 1.0) * (1.0 / 9007199254740992.0); }   // (0, 1]
+DEV int ndig64(unsigned long long v) { int d = 1; while (v >= 10ull) { v /= 10ull; d++; } return d; }
+DEV int put_dec64(uint8_t* o, unsigned long long v) { const int d = ndig64(v); for (int i = d - 1; i >= 0; i--) { o[i] = (uint8_t)('0' + v % 10ull); v /= 10ull; } return d; }
+
+// the raw fragment length of candidate g (std:: parameterisation of a, b)
+DEV double wgs_draw(const WgsParams& W, uint64_t g) {
+    const Ph4m w = philox_mol(W.seed, g, ST_WGS_LEN, 0);
+    if (W.dist == WGS_UNIFORM) return W.a + (W.b - W.a) * u53(w.x, w.y);
+    if (W.dist == WGS_EXPONENTIAL) return -log(u53o(w.x, w.y)) / W.a;
+    const double v = W.a + W.b * box_muller(w.x, w.y);
+    return W.dist == WGS_LOGNORMAL ? exp(v) : v;
+}
+// double -> int toward zero, clamped to the int range in double first; NaN gives 0
+DEV int wgs_to_int(double v) { return !(v == v) ? 0 : v >= 2147483647.0 ? 2147483647 : (v <= -2147483648.0 ? (-2147483647 - 1) : (int)v); }
+
+// so_far: [n_contigs] running sums of the contig lengths.  The table is searched in LDS when it fits (WGS_LDS_CONTIGS entries), in
+// global memory otherwise: first i with pos <= so_far[i] (the reference's while loop, :190-193)
+__global__ void __launch_bounds__(256) k_wgs_plan(WgsParams W, const uint64_t* __restrict__ so_far, uint64_t first, uint64_t n,
+                                                  uint4* __restrict__ plan, uint64_t* __restrict__ flag, uint64_t* __restrict__ bases) {
+    __shared__ uint64_t tab[WGS_LDS_CONTIGS];
+    const bool in_lds = W.n_contigs <= (uint32_t)WGS_LDS_CONTIGS;
+    if (in_lds) {
+        for (uint32_t i = threadIdx.x; i < W.n_contigs; i += blockDim.x) tab[i] = so_far[i];
+        __syncthreads();
+    }
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const uint64_t g = first + t;
+    const Ph4m wp = philox_mol(W.seed, g, ST_WGS_POS, 0);
+    const unsigned long long pos = __umul64hi(((unsigned long long)wp.x << 32) | wp.y, W.ref_length);
+    uint32_t lo = 0, hi = W.n_contigs - 1;                            // pos < ref_length = so_far[n_contigs - 1]: the answer is in [0, n_contigs)
+    if (in_lds) { while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (tab[mid] < pos) lo = mid + 1; else hi = mid; } }
+    else { while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (so_far[mid] < pos) lo = mid + 1; else hi = mid; } }
+    const unsigned long long end = in_lds ? tab[lo] : so_far[lo], begin = lo ? (in_lds ? tab[lo - 1] : so_far[lo - 1]) : 0ull;
+    const long long len = (long long)(end - begin);
+    const long long ref_pos = (long long)(pos - end) + len;           // (:194) == pos - begin: 1 .. len, or 0 .. len on the first contig
+    long long fl = wgs_to_int(wgs_draw(W, g));
+    if (fl > len - ref_pos) fl = len - ref_pos;                       // (:196-198)
+    const bool minus = (philox_mol(W.seed, g, ST_WGS_STRAND, 0).x & 1u) != 0u;
+    const bool emit = fl >= 1;
+    plan[t] = make_uint4(lo, (uint32_t)ref_pos, emit ? (uint32_t)fl : 0u, minus ? 1u : 0u);
+    flag[t] = emit ? 1ull : 0ull;
+    bases[t] = emit ? (unsigned long long)fl : 0ull;
+}
+
+// rank / bsum: exclusive scans of flag / bases ([n + 1]).  Candidate t is kept when it is emitted and the bases of the emitted candidates
+// before it -- of this call and of the calls before (bases_before) -- are below base_count.  idlen[t]: bytes of the id of a kept candidate,
+// "{index}_{contig}:{ref_pos}-{end}{+|-}", 0 otherwise.  The kept candidate that reaches base_count (at most one: emitted lengths are
+// positive) reports the end of the run: cut = {molecules kept, bases kept, candidates consumed, 1}
+__global__ void k_wgs_cut(uint64_t n, const uint4* __restrict__ plan, const uint64_t* __restrict__ rank, const uint64_t* __restrict__ bsum,
+                          const uint32_t* __restrict__ name_len, uint64_t mols_before, uint64_t bases_before, uint64_t base_count,
+                          uint64_t* __restrict__ idlen, uint64_t* __restrict__ cut) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const uint4 p = plan[t];
+    const unsigned long long before = bases_before + bsum[t];
+    const bool keep = p.z != 0u && before < base_count;
+    idlen[t] = keep ? (uint64_t)(ndig64(mols_before + rank[t]) + 1 + (int)name_len[p.x] + 1 + ndig(p.y) + 1 + ndig(p.y + p.z) + 1) : 0ull;
+    if (keep && before + p.z >= base_count) { cut[0] = rank[t] + 1ull; cut[1] = bsum[t] + p.z; cut[2] = t + 1ull; cut[3] = 1ull; }
+}
+
+__global__ void k_wgs_write(uint64_t n, const uint4* __restrict__ plan, const uint64_t* __restrict__ rank, const uint64_t* __restrict__ idlen,
+                            const uint64_t* __restrict__ id_off, const uint32_t* __restrict__ name_off, const uint32_t* __restrict__ name_len,
+                            const uint8_t* __restrict__ names, uint64_t mols_before, MolOut O) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n || idlen[t] == 0ull) return;
+    const uint4 p = plan[t];
+    const uint64_t j = rank[t];
+    O.reads[2 * j] = (uint32_t)j; O.reads[2 * j + 1] = 1u;
+    uint32_t* ov = O.intervals + 4ull * j;
+    ov[0] = p.x; ov[1] = p.y; ov[2] = p.y + p.z; ov[3] = p.w << 31;   // no substitutions: mod_begin 0
+    uint8_t* d = O.idpool + id_off[t];
+    uint32_t k = (uint32_t)put_dec64(d, mols_before + j);
+    d[k++] = '_';
+    const uint8_t* nm = names + name_off[p.x];
+    const uint32_t nl = name_len[p.x];
+    for (uint32_t q = 0; q < nl; q++) d[k + q] = nm[q];
+    k += nl;
+    d[k++] = ':'; k += (uint32_t)put_dec(d + k, p.y);
+    d[k++] = '-'; k += (uint32_t)put_dec(d + k, p.y + p.z);
+    d[k++] = p.w ? '-' : '+';
+    O.ids[2 * j] = (uint32_t)id_off[t]; O.ids[2 * j + 1] = k;
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
 static inline unsigned nblk(uint64_t n) { return (unsigned)((n + 127) / 128); }
@@ -619,6 +712,24 @@ hipError_t launch_edit_write(const MolView& m, const uint32_t* pre, const uint32
                              const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off, const MolOut& o, hipStream_t s) {
     if (!m.B.n_reads) return hipSuccess;
     hipLaunchKernelGGL(k_edit_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, pre, post, flip, lits, ivl_off, mod_off, id_off, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_wgs_plan(const WgsParams& p, const uint64_t* so_far, uint64_t first, uint64_t n, uint4* plan, uint64_t* flag, uint64_t* bases, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_wgs_plan, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, so_far, first, n, plan, flag, bases);
+    return hipGetLastError();
+}
+hipError_t launch_wgs_cut(uint64_t n, const uint4* plan, const uint64_t* rank, const uint64_t* bsum, const uint32_t* name_len, uint64_t mols_before,
+                          uint64_t bases_before, uint64_t base_count, uint64_t* idlen, uint64_t* cut, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_wgs_cut, dim3(nblk(n)), dim3(128), 0, s, n, plan, rank, bsum, name_len, mols_before, bases_before, base_count, idlen, cut);
+    return hipGetLastError();
+}
+hipError_t launch_wgs_write(uint64_t n, const uint4* plan, const uint64_t* rank, const uint64_t* idlen, const uint64_t* id_off, const uint32_t* name_off,
+                            const uint32_t* name_len, const uint8_t* names, uint64_t mols_before, const MolOut& o, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_wgs_write, dim3(nblk(n)), dim3(128), 0, s, n, plan, rank, idlen, id_off, name_off, name_len, names, mols_before, o);
     return hipGetLastError();
 }
 

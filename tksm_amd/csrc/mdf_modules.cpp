@@ -1,4 +1,5 @@
-// mdf_modules.cpp -- the `tksm pcr`, `truncate`, `polyA`, `tag`, `scb` and `flip` modules on top of the C-ABI (MDF file in, MDF file out).
+// mdf_modules.cpp -- the `tksm pcr`, `truncate`, `polyA`, `tag`, `scb` and `flip` modules on top of the C-ABI (MDF file in, MDF file out),
+// and `random-wgs` (no input: MDF file out).
 //
 // Mirrors (file:line into vpc-ccg/tksm):
 //   PCR_module::impl        src/pcr.cpp:91-260       flags -i -o --molecule-count --cycles --error-rate --efficiency -x/--preset,
@@ -10,6 +11,7 @@
 //   TAG_module              src/tag.cpp:16-129       -5/--format5, -3/--format3 (a leading digit: that many N's)
 //   SingleCellBarcoder      src/scb.cpp:14-92        --keep-meta-barcodes
 //   StrandMan_module        src/strand_man.cpp:20-124 -p/--flip-probability (outside [0, 1]: logged, not refused)
+//   RWGS_module             src/random_wgs.cpp:24-229 -r/--reference, --frag-len-dist "NAME A [B]", -o, --base-count | --depth
 //   utility flags           src/module.h:75-104      -s/--seed (default 42), --verbosity, --log-file, -h
 // All stream: `truncate` and the four segment edits read the input in batches of whole molecules (--batch-bytes), `pcr` amplifies its templates in slices
 // of about --slice-molecules output molecules (tksmseq_pcr_params::template_begin / _end); the pieces go round the entries of
@@ -33,6 +35,7 @@
 #include <vector>
 
 #include "../../include/tksmseq.h"
+#include "host.h"
 #include "module_log.h"
 #include "sequencer_module.h"
 
@@ -528,4 +531,163 @@ extern "C" int tksmseq_flip_main(int argc0, char** argv0) {
         q.first_molecule_index = first;
         return tksmseq_flip(ctx, in, &q, out);
     });
+}
+
+// The contig table of random-wgs: names and lengths from <reference>.fai (src/random_wgs.cpp:139-161: the first two columns), or, when
+// there is no such file, from the FASTA itself (the reference reads nothing then, and writes nothing).
+static bool wgs_contig_table(const std::string& reference, std::vector<std::pair<std::string, uint64_t>>& table, std::string& err) {
+    table.clear();
+    const std::string fai = reference + ".fai";
+    if (FILE* f = fopen(fai.c_str(), "rb")) {
+        std::string text;
+        char buf[1 << 16];
+        size_t n;
+        while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
+        fclose(f);
+        size_t a = 0;
+        while (a < text.size()) {
+            size_t e = text.find('\n', a);
+            if (e == std::string::npos) e = text.size();
+            size_t i = a;
+            while (i < e && isspace((unsigned char)text[i])) i++;
+            size_t j = i;
+            while (j < e && !isspace((unsigned char)text[j])) j++;
+            if (j > i) {
+                size_t k = j;
+                while (k < e && isspace((unsigned char)text[k])) k++;
+                char* end = nullptr;
+                const std::string num = text.substr(k, e - k);
+                const unsigned long long len = strtoull(num.c_str(), &end, 10);
+                if (num.empty() || end == num.c_str() || num[0] == '-') { err = "malformed line in " + fai + ": " + text.substr(a, e - a); return false; }
+                table.emplace_back(text.substr(i, j - i), (uint64_t)len);
+            }
+            a = e + 1;
+        }
+        return true;
+    }
+    std::vector<tkh::FastaRecord> recs;
+    if (!tkh::read_fasta(reference, recs, err)) return false;
+    for (auto& r : recs) table.emplace_back(r.name, (uint64_t)r.seq.size());
+    return true;
+}
+
+extern "C" int tksmseq_random_wgs_main(int argc0, char** argv0) {
+    std::vector<std::string> arg_store; std::vector<char*> arg_ptrs;
+    tkmod::split_equals(argc0, argv0, arg_store, arg_ptrs);
+    const int argc = (int)arg_ptrs.size(); char** const argv = arg_ptrs.data();
+    Common c;
+    std::string reference, dist_text;
+    bool have_bc = false, have_depth = false, have_dist = false;
+    long long base_count = 0; double depth = 0.0;
+    uint64_t batch_molecules = 2000000;
+    for (int i = 1; i < argc; i++) {
+        const std::string o = argv[i];
+        const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
+        // (this module's -r and --batch-molecules first: the common flags know -i and --batch-bytes, which it does not have)
+        if ((o == "-r" || o == "--reference") && v) { reference = v; i++; continue; }
+        if (o == "--frag-len-dist" && v) { dist_text = v; have_dist = true; i++; continue; }
+        if (o == "--base-count" && v) { base_count = atoll(v); have_bc = true; i++; continue; }
+        if (o == "--depth" && v) { depth = atof(v); have_depth = true; i++; continue; }
+        if (o == "--batch-molecules" && v) { batch_molecules = strtoull(v, nullptr, 10); if (batch_molecules < 1 || batch_molecules > (1ull << 28)) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; } i++; continue; }
+        if (o == "-i" || o == "--input" || o == "--batch-bytes" || o == "--slice-molecules") { fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1; }
+        const int k = common_flag(argc, argv, i, c);
+        if (k < 0) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; }
+        if (k) continue;
+        fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1;
+    }
+    static const char* help =
+        "Random whole-genome fragments module\nusage: random-wgs -r REFERENCE --frag-len-dist \"NAME A [B]\" -o OUTPUT (--base-count N | --depth D) [-s SEED]\n"
+        "                  [--devices D[,D...]] [--batch-molecules M] [--verbosity L] [--log-file F]\n"
+        "NAME: normal MEAN SIGMA | uniform LOW HIGH | lognormal M S | exponential RATE; the contig table comes from REFERENCE.fai\n"
+        "(from REFERENCE itself when there is no such file)\n";
+    if (c.help) { printf("%s", help); return 0; }
+    // validate_arguments (src/random_wgs.cpp:95-127)
+    int missing = 0;
+    if (reference.empty()) { fprintf(stderr, "reference is required!\n"); missing++; }
+    if (c.output.empty()) { fprintf(stderr, "output is required!\n"); missing++; }
+    if (!have_dist) { fprintf(stderr, "frag-len-dist is required!\n"); missing++; }
+    if (missing) { fprintf(stderr, "%s\n", help); return 1; }
+    if (!have_bc && !have_depth) { fprintf(stderr, "Either base-count or depth is required!\n"); return 1; }
+    tksmseq_wgs_params p{};
+    {
+        int dist = 0;
+        const int bad = tkmod::parse_frag_len_dist(dist_text, dist, p.a, p.b);
+        if (bad) { fprintf(stderr, bad == 1 ? "Invalid fragment length distribution\n" : "Invalid fragment length distribution parameters\n"); return 1; }
+        p.dist = dist;
+    }
+    Logger log;
+    if (!open_log(c, "random-wgs", log)) return 1;
+    std::vector<std::pair<std::string, uint64_t>> table;
+    {
+        std::string err;
+        if (!wgs_contig_table(reference, table, err)) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
+        std::vector<std::string> names;
+        for (auto& t : table) names.push_back(t.first);
+        std::sort(names.begin(), names.end());
+        for (size_t i = 1; i < names.size(); i++)
+            if (names[i] == names[i - 1]) { fprintf(stderr, "Error: contig name %s appears more than once in the reference\n", names[i].c_str()); return 1; }
+    }
+    uint64_t ref_length = 0;
+    for (auto& t : table) ref_length += t.second;
+    log.log(Logger::INFO, "Reference length: %llu", (unsigned long long)ref_length);
+    if (!ref_length) { fprintf(stderr, "Error: the reference has no contigs (or none with a base)\n"); return 1; }
+    p.seed = (uint64_t)c.seed;
+    p.base_count = have_bc ? (int64_t)base_count : (int64_t)(depth * (double)ref_length);      // (:169-176)
+
+    OrderedOut out;
+    out.f = fopen(c.output.c_str(), "wb");
+    if (!out.f) { fprintf(stderr, "Error: cannot write %s\n", c.output.c_str()); return 1; }
+    const int per_device = 2, n_ctx = (int)c.devices.size() * per_device;
+    std::mutex err_m, gen_m; std::string first_error; std::atomic<bool> failed{false};
+    auto set_error = [&](const std::string& e) { std::lock_guard<std::mutex> l(err_m); if (!failed.exchange(true)) first_error = e; out.fail(); };
+    // the only state that is serial across batches (guarded by gen_m): next candidate, molecules and bases so far, next piece number
+    tksmseq_wgs_progress st{}; uint64_t next_seq = 0; bool done = p.base_count <= 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto worker = [&](int wi) {
+        tksmseq_ctx* ctx = nullptr;
+        if (tksmseq_create(c.devices[(size_t)(wi / per_device)], &ctx)) { set_error(tksmseq_last_error(nullptr)); return; }
+        tksmseq_set_host_threads(ctx, (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency() / (unsigned)std::max(1, n_ctx / 2))));
+        for (auto& t : table)
+            if (tksmseq_reference_declare_contig(ctx, t.first.c_str(), t.second)) { set_error(tksmseq_last_error(ctx)); break; }
+        while (!failed) {
+            tksmseq_batch* b = nullptr;
+            uint64_t seq = 0, n = 0;
+            {
+                // made under the lock: a batch's carried state is known once the batch before it has been made (milliseconds; the text is
+                // formatted outside)
+                std::lock_guard<std::mutex> l(gen_m);
+                if (done || failed) break;
+                tksmseq_wgs_params q = p;
+                q.first_candidate = st.next_candidate; q.n_candidates = batch_molecules; q.molecules_before = st.molecules; q.bases_before = st.bases;
+                tksmseq_wgs_progress pr{};
+                if (tksmseq_wgs(ctx, &q, &b, &pr)) { set_error(std::string("random-wgs: ") + tksmseq_last_error(ctx)); break; }
+                tksmseq_batch_info(b, &n, nullptr, nullptr);
+                if (!n && !pr.reached) {
+                    tksmseq_batch_free(ctx, b);
+                    set_error("random-wgs: none of " + std::to_string(batch_molecules) + " candidate fragments has a base (fragment length distribution '" + dist_text + "'): giving up");
+                    break;
+                }
+                st = pr; seq = next_seq++;
+                if (pr.reached) done = true;
+            }
+            char* text = nullptr; uint64_t len = 0;
+            if (tksmseq_batch_to_mdf_text(ctx, b, &text, &len)) set_error(std::string("random-wgs: ") + tksmseq_last_error(ctx));
+            else {
+                log.log(Logger::DEBUG, "piece %llu: %llu molecules, %.1f MB of text (context %d)", (unsigned long long)seq, (unsigned long long)n, len / 1e6, wi);
+                if (!out.put(seq, text, len) && !failed) set_error("cannot write " + c.output);
+            }
+            tksmseq_text_free(text);
+            tksmseq_batch_free(ctx, b);
+        }
+        tksmseq_destroy(ctx);
+    };
+    std::vector<std::thread> th;
+    for (int w = 0; w < n_ctx; w++) th.emplace_back(worker, w);
+    for (auto& t : th) t.join();
+    const bool close_ok = fclose(out.f) == 0;
+    if (failed) { fprintf(stderr, "Error: %s\n", first_error.c_str()); return 1; }
+    if (!close_ok || out.failed) { fprintf(stderr, "Error: cannot write %s\n", c.output.c_str()); return 1; }
+    log.log(Logger::INFO, "random-wgs: %llu molecules, %llu bases from %llu candidates written in %.2f s (%d device group(s))", (unsigned long long)st.molecules,
+            (unsigned long long)st.bases, (unsigned long long)st.next_candidate, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), (int)c.devices.size());
+    return 0;
 }

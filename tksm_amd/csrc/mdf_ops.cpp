@@ -2,6 +2,7 @@
 //   tksmseq_pcr            src/pcr.cpp:22-89, :138 (presets), :215-229 (whole input in memory, at most 2 x target templates)
 //   tksmseq_truncate       src/truncate.cpp:23-65, :77-227, :322-351, :362-404
 //   tksmseq_polya / _tag / _scb / _flip   src/polyA.cpp:133-148, src/tag.cpp:70-113, src/scb.cpp:57-80, src/interval.h:908-920
+//   tksmseq_wgs            src/random_wgs.cpp:181-207 (no input: the molecules are made on the device)
 //   tksmseq_batch_to_mdf_text   molecule_descriptor::operator<<, src/interval.h:898-905 (+ dump_comment :880-890)
 // The molecule tables stay on the device from one transform to the next and into tksmseq_run; only sizes, per-read lengths
 // (which the host needs to size and order a Seq batch) and, for the text writer, the tables themselves come back.
@@ -693,6 +694,107 @@ int tksmseq_flip(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_flip_p
     if ((rc = edit_apply(ctx, in, nullptr, nullptr, d_flip.as<uint8_t>(), b.get()))) return rc;
     edit_comments(in, b.get(), p->flags);
     return edit_finish(ctx, b, out);
+}
+
+// ---- random-wgs ------------------------------------------------------------------------------------------------------------------
+// the contig table as the kernels read it: running sums of the lengths, and the names (for the ids) in one pool
+static int wgs_table(tksmseq_ctx* ctx) {
+    if (ctx->wgs_version == ctx->ref_version && ctx->d_wgs_sofar.p) return TKSMSEQ_OK;
+    const size_t nc = ctx->contig_names.size();
+    std::vector<uint64_t> so_far(nc);
+    std::vector<uint32_t> noff(nc), nlen(nc);
+    std::string pool;
+    uint64_t acc = 0;
+    for (size_t i = 0; i < nc; i++) {
+        acc += ctx->contigs[2 * i + 1];
+        so_far[i] = acc; noff[i] = (uint32_t)pool.size(); nlen[i] = (uint32_t)ctx->contig_names[i].size();
+        pool += ctx->contig_names[i];
+        if (pool.size() >= 0xffffffffull) { ctx->err = "random-wgs: more than 4 GB of contig names"; return TKSMSEQ_ELIMIT; }
+    }
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx, ctx->d_wgs_sofar.ensure(nc * 8 + 16)); HIPCHK(ctx, ctx->d_wgs_nameoff.ensure(nc * 4 + 16));
+    HIPCHK(ctx, ctx->d_wgs_namelen.ensure(nc * 4 + 16)); HIPCHK(ctx, ctx->d_wgs_names.ensure(pool.size() + 16));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_wgs_sofar.p, so_far.data(), nc * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_wgs_nameoff.p, noff.data(), nc * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_wgs_namelen.p, nlen.data(), nc * 4, hipMemcpyHostToDevice, s));
+    if (!pool.empty()) HIPCHK(ctx, hipMemcpyAsync(ctx->d_wgs_names.p, pool.data(), pool.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    ctx->wgs_version = ctx->ref_version;
+    return TKSMSEQ_OK;
+}
+
+int tksmseq_wgs(tksmseq_ctx* ctx, const tksmseq_wgs_params* p, tksmseq_batch** out, tksmseq_wgs_progress* progress) {
+    if (!ctx || !p || !out || !progress) return TKSMSEQ_EINVAL;
+    *out = nullptr;
+    memset(progress, 0, sizeof *progress);
+    // validate_arguments (src/random_wgs.cpp:118-125), plus what std:: leaves undefined
+    if (p->dist < TKSMSEQ_WGS_NORMAL || p->dist > TKSMSEQ_WGS_EXPONENTIAL) { ctx->err = "Invalid fragment length distribution"; return TKSMSEQ_EINVAL; }
+    if (!std::isfinite(p->a) || !std::isfinite(p->b) || !(p->a > 0.0) || p->b < 0.0 || (p->dist == TKSMSEQ_WGS_UNIFORM && p->b < p->a)) {
+        ctx->err = "Invalid fragment length distribution parameters"; return TKSMSEQ_EINVAL;
+    }
+    const size_t nc = ctx->contig_names.size();
+    if (!nc || !ctx->total_bases) { ctx->err = "random-wgs: the reference has no contigs (or none with a base)"; return TKSMSEQ_ESTATE; }
+    for (size_t i = 0; i < nc; i++)
+        if (ctx->contigs[2 * i + 1] >= 0x80000000ull) { ctx->err = "random-wgs: contig " + ctx->contig_names[i] + " has 2^31 bases or more"; return TKSMSEQ_ELIMIT; }
+    const uint64_t n = p->n_candidates;
+    if (n > (1ull << 28)) { ctx->err = "random-wgs: more than 2^28 candidates in one call (split the range)"; return TKSMSEQ_ELIMIT; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    int rc = wgs_table(ctx);
+    if (rc) return rc;
+    progress->next_candidate = p->first_candidate; progress->molecules = p->molecules_before; progress->bases = p->bases_before;
+    const bool owed = p->base_count > 0 && p->bases_before < (uint64_t)p->base_count;
+    progress->reached = owed ? 0 : 1;
+    const uint64_t nn = owed ? n : 0;                                   // (nothing owed: an empty batch, no candidate taken)
+    DevBuf d_plan, d_flag, d_bases, d_rank, d_bsum, d_idlen, d_idoff, d_cut;
+    for (DevBuf* pb_ : {&d_plan, &d_flag, &d_bases, &d_rank, &d_bsum, &d_idlen, &d_idoff, &d_cut}) { pb_->pooled = true; pb_->pool_stream = s; }   // (per-call temporaries: DevCache, ctx.h)
+    uint64_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};                           // cut[4], rank[n], bsum[n], idoff[n]
+    if (nn) {
+        HIPCHK(ctx, d_plan.ensure(nn * 16 + 16));
+        for (DevBuf* b : {&d_flag, &d_bases, &d_idlen}) HIPCHK(ctx, b->ensure(nn * 8 + 16));
+        for (DevBuf* b : {&d_rank, &d_bsum, &d_idoff}) HIPCHK(ctx, b->ensure((nn + 1) * 8 + 16));
+        HIPCHK(ctx, d_cut.ensure(64));
+        HIPCHK(ctx, ctx->w_scan.ensure(tk::scan_temp_bytes(nn) + 64));
+        HIPCHK(ctx, hipMemsetAsync(d_cut.p, 0, 64, s));
+        const tk::WgsParams W{p->seed, p->dist, p->a, p->b, ctx->total_bases, (uint32_t)nc};
+        HIPCHK(ctx, tk::launch_wgs_plan(W, ctx->d_wgs_sofar.as<uint64_t>(), p->first_candidate, nn, d_plan.as<uint4>(), d_flag.as<uint64_t>(), d_bases.as<uint64_t>(), s));
+        HIPCHK(ctx, tk::launch_scan(d_flag.as<uint64_t>(), d_rank.as<uint64_t>(), nn, ctx->w_scan.p, ctx->w_scan.cap, s));
+        HIPCHK(ctx, tk::launch_scan(d_bases.as<uint64_t>(), d_bsum.as<uint64_t>(), nn, ctx->w_scan.p, ctx->w_scan.cap, s));
+        HIPCHK(ctx, tk::launch_wgs_cut(nn, d_plan.as<uint4>(), d_rank.as<uint64_t>(), d_bsum.as<uint64_t>(), ctx->d_wgs_namelen.as<uint32_t>(), p->molecules_before,
+                                       p->bases_before, (uint64_t)p->base_count, d_idlen.as<uint64_t>(), d_cut.as<uint64_t>(), s));
+        HIPCHK(ctx, tk::launch_scan(d_idlen.as<uint64_t>(), d_idoff.as<uint64_t>(), nn, ctx->w_scan.p, ctx->w_scan.cap, s));
+        HIPCHK(ctx, hipMemcpyAsync(h, d_cut.p, 32, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(h + 4, d_rank.as<uint64_t>() + nn, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(h + 5, d_bsum.as<uint64_t>() + nn, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(h + 6, d_idoff.as<uint64_t>() + nn, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+    }
+    const bool reached = h[3] != 0;
+    const uint64_t n_mol = reached ? h[0] : h[4], n_bases = reached ? h[1] : h[5], t_id = h[6];
+    if (t_id >= 0xffffffffull) { ctx->err = "random-wgs: output batch too large (fewer candidates per call)"; return TKSMSEQ_ELIMIT; }
+    std::unique_ptr<tksmseq_batch> b(new tksmseq_batch());
+    b->n_reads = n_mol; b->n_intervals = n_mol; b->n_mods = 0; b->n_literals = 0;
+    HIPCHK(ctx, b->reads.ensure(n_mol * 8 + 64));
+    HIPCHK(ctx, b->intervals.ensure((n_mol + 1) * 16 + 64));
+    HIPCHK(ctx, b->mods.ensure(64));
+    HIPCHK(ctx, b->ids.ensure(n_mol * 8 + 64));
+    HIPCHK(ctx, b->idpool.ensure(t_id + 64));
+    HIPCHK(ctx, b->literals.ensure(64));
+    HIPCHK(ctx, b->litpool.ensure(64));
+    if (n_mol) {
+        tk::MolOut O{b->reads.as<uint32_t>(), b->intervals.as<uint32_t>(), b->mods.as<uint32_t>(), b->ids.as<uint32_t>(), b->idpool.as<uint8_t>()};
+        HIPCHK(ctx, tk::launch_wgs_write(nn, d_plan.as<uint4>(), d_rank.as<uint64_t>(), d_idlen.as<uint64_t>(), d_idoff.as<uint64_t>(), ctx->d_wgs_nameoff.as<uint32_t>(),
+                                         ctx->d_wgs_namelen.as<uint32_t>(), ctx->d_wgs_names.as<uint8_t>(), p->molecules_before, O, s));
+    }
+    HIPCHK(ctx, hipMemsetAsync(b->intervals.as<uint32_t>() + 4 * n_mol, 0, 16, s));      // the interval after the last carries n_mods (0)
+    if ((rc = finalize_device_batch(ctx, b.get()))) return rc;
+    if (nn) {
+        progress->next_candidate = p->first_candidate + (reached ? h[2] : nn);
+        progress->molecules = p->molecules_before + n_mol; progress->bases = p->bases_before + n_bases;
+        progress->reached = reached ? 1 : 0;
+    }
+    *out = b.release();
+    return TKSMSEQ_OK;
 }
 
 int tksmseq_batch_to_mdf_text(tksmseq_ctx* ctx, const tksmseq_batch* b, char** text, uint64_t* len) {

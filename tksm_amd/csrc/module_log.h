@@ -1,6 +1,7 @@
 // module_log.h -- what the tksm modules here share: --verbosity / --log-file (src/module.h:95-122, src/util.h:94-120) and the
 // --devices list.
 #pragma once
+#include <cctype>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdint>
@@ -65,6 +66,31 @@ inline bool parse_device_list(const char* v, std::vector<int>& out) {
         if (!*e) return true;
         q = e + 1;
     }
+}
+
+// --frag-len-dist "NAME A [B]" of random-wgs, one argument, space separated (parse_dist_str + validate_arguments, src/random_wgs.cpp:63-74,
+// :116-125; A and B may be decimals here).  0: ok (dist = TKSMSEQ_WGS_*), 1: "Invalid fragment length distribution", 2: "... parameters"
+// (a <= 0, b < 0 as the reference; uniform with b < a and non-finite values, for which std:: is undefined).  A number that is missing
+// or does not parse reads as 0, as the reference's stream extraction leaves it.
+inline int parse_frag_len_dist(const std::string& text, int& dist, double& a, double& b) {
+    std::vector<std::string> tok;
+    size_t i = 0;
+    while (i < text.size()) {
+        while (i < text.size() && isspace((unsigned char)text[i])) i++;
+        size_t j = i;
+        while (j < text.size() && !isspace((unsigned char)text[j])) j++;
+        if (j > i) tok.push_back(text.substr(i, j - i));
+        i = j;
+    }
+    static const char* names[4] = {"normal", "uniform", "lognormal", "exponential"};   // TKSMSEQ_WGS_NORMAL .. _EXPONENTIAL
+    dist = -1; a = 0.0; b = 0.0;
+    for (int d = 0; d < 4 && !tok.empty(); d++) if (tok[0] == names[d]) dist = d;
+    if (dist < 0) return 1;
+    auto num = [](const std::string& t) { char* e = nullptr; const double v = strtod(t.c_str(), &e); return (e == t.c_str() || *e) ? 0.0 : v; };
+    if (tok.size() > 1) a = num(tok[1]);
+    if (tok.size() > 2 && dist != 3) b = num(tok[2]);
+    if (!(a > 0.0) || b < 0.0 || a != a || b != b || a - a != 0.0 || b - b != 0.0 || (dist == 1 && b < a)) return 2;
+    return 0;
 }
 
 // molecules a piece of MDF text holds once depth is unrolled = reads Seq makes of it: the depth column of every molecule header

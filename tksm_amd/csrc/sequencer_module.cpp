@@ -64,6 +64,12 @@ struct Args {
     int trc_n = 0;
     tksmseq_trc_params trc{};
     std::string trc_kde;
+    // chained random-wgs (src/random_wgs.cpp:24-229) in place of -i: the molecules are made on the device of the context that sequences them
+    bool wgs_on = false, wgs_have_dist = false, wgs_have_bc = false, wgs_have_depth = false;
+    std::string wgs_dist;
+    long long wgs_base_count = 0; double wgs_depth = 0.0;
+    uint64_t wgs_batch = 524288;                           // candidates per batch
+    tksmseq_wgs_params wgs{};
 };
 
 const char* OPTION_DESTS[] = {"help", "input", "references", "badread", "perfect", "skip_qual_compute", "output_format",
@@ -79,7 +85,9 @@ void usage(FILE* f) {
             "                [--log-file F]\n"
             "                [--pcr-cycles C --pcr-molecule-count N (--pcr-preset X | --pcr-error-rate E --pcr-efficiency F)]\n"
             "                [--truncate-normal MU,SIGMA | --truncate-lognormal MU,SIGMA | --truncate-kde-model M.json\n"
-            "                 [--truncate-always-end] [--truncate-kde-models-length]]\n");
+            "                 [--truncate-always-end] [--truncate-kde-models-length]]\n"
+            "       sequence -r REFERENCES --wgs-frag-len-dist \"NAME A [B]\" (--wgs-base-count N | --wgs-depth D) [--wgs-batch-molecules M]\n"
+            "                (no -i: whole-genome fragments made on the device; the other options as above)\n");
 }
 
 // one gzip member (RFC 1952) holding d[0..n): members simply follow each other in a .gz file, so batches -- and pieces of
@@ -230,7 +238,8 @@ const OptSpec LONG_OPTS[] = {
     {"--batch-bytes", true}, {"--in-flight", true}, {"--gzip", true}, {"--pcr-cycles", true}, {"--pcr-molecule-count", true}, {"--pcr-error-rate", true},
     {"--pcr-efficiency", true}, {"--pcr-preset", true}, {"--pcr-slice-molecules", true}, {"--truncate-normal", true},
     {"--truncate-lognormal", true}, {"--truncate-kde-model", true}, {"--truncate-always-end", false},
-    {"--truncate-kde-models-length", false}, {"--verbosity", true}, {"--log-file", true}};
+    {"--truncate-kde-models-length", false}, {"--wgs-frag-len-dist", true}, {"--wgs-base-count", true}, {"--wgs-depth", true},
+    {"--wgs-batch-molecules", true}, {"--verbosity", true}, {"--log-file", true}};
 const char SHORT_WITH_VALUE[] = "iroOts";
 
 int normalise_args(int argc, char** argv, std::vector<std::string>& out, std::vector<char>& glued) {
@@ -334,6 +343,16 @@ class Sequencer_module::impl {
             else if (o == "--truncate-kde-model") { if (!(v = need(i))) return 2; a.trc_kde = v; a.trc.mode = TKSMSEQ_TRC_KDE; a.trc_n++; }
             else if (o == "--truncate-always-end") a.trc.always_end = 1;
             else if (o == "--truncate-kde-models-length") a.trc.kde_models_length = 1;
+            else if (o == "--wgs-frag-len-dist") { if (!(v = need(i))) return 2; a.wgs_dist = v; a.wgs_have_dist = true; }
+            else if (o == "--wgs-base-count") { if (!(v = need(i))) return 2; a.wgs_base_count = atoll(v); a.wgs_have_bc = true; }
+            else if (o == "--wgs-depth") { if (!(v = need(i))) return 2; a.wgs_depth = atof(v); a.wgs_have_depth = true; }
+            else if (o == "--wgs-batch-molecules") {
+                if (!(v = need(i))) return 2;
+                char* e = nullptr;
+                a.wgs_batch = strtoull(v, &e, 10);
+                if (e == v || *e || a.wgs_batch < 1 || a.wgs_batch > (1ull << 28)) { usage(stderr); fprintf(stderr, "sequence: error: argument --wgs-batch-molecules: expected an integer between 1 and 268435456, got '%s'\n", v); return 2; }
+                a.wgs_on = true;
+            }
             else if (o == "--verbosity") { if (!(v = need(i))) return 2; a.verbosity = v; }
             else if (o == "--log-file") { if (!(v = need(i))) return 2; a.log_file = v; }
             else { usage(stderr); fprintf(stderr, "sequence: error: unrecognized arguments: %s\n", argv[i]); return 2; }
@@ -351,7 +370,12 @@ public:
         if (rc) return rc;
         if (a.help) { usage(stdout); return 0; }
         if (a.list) { for (const char* d : OPTION_DESTS) printf("%s\n", d); return 0; }
-        if (a.input.empty()) { usage(stderr); fprintf(stderr, "sequence: error: the following arguments are required: -i/--input\n"); return 2; }
+        a.wgs_on = a.wgs_on || a.wgs_have_dist || a.wgs_have_bc || a.wgs_have_depth;
+        if (a.wgs_on && !a.input.empty()) { usage(stderr); fprintf(stderr, "sequence: error: argument -i/--input: not allowed with the --wgs-* options (the molecules are made on the device)\n"); return 2; }
+        if (a.wgs_on && (a.pcr_have_cycles || a.pcr_have_count || a.pcr_have_er || a.pcr_have_ef || !a.pcr_preset.empty() || a.trc_n)) {
+            usage(stderr); fprintf(stderr, "sequence: error: the --wgs-* options cannot be combined with --pcr-* / --truncate-*\n"); return 2;
+        }
+        if (a.input.empty() && !a.wgs_on) { usage(stderr); fprintf(stderr, "sequence: error: the following arguments are required: -i/--input\n"); return 2; }
         // py/sequence.py:134-164
         double idv[3]; int nid = 0; bool bad = false;
         {
@@ -393,6 +417,18 @@ public:
             }
             if (missing) return 1;
             a.pcr.seed = (uint64_t)a.seed;
+        }
+        if (a.wgs_on) {
+            // validate_arguments of the module (src/random_wgs.cpp:95-127)
+            int missing = 0;
+            if (a.references.empty()) { fprintf(stderr, "reference is required!\n"); missing++; }
+            if (!a.wgs_have_dist) { fprintf(stderr, "frag-len-dist is required!\n"); missing++; }
+            if (missing) return 1;
+            if (!a.wgs_have_bc && !a.wgs_have_depth) return die("Either base-count or depth is required!");
+            int dist = 0;
+            const int bad_dist = tkmod::parse_frag_len_dist(a.wgs_dist, dist, a.wgs.a, a.wgs.b);
+            if (bad_dist) return die(bad_dist == 1 ? "Invalid fragment length distribution" : "Invalid fragment length distribution parameters");
+            a.wgs.dist = dist; a.wgs.seed = (uint64_t)a.seed;
         }
         if (a.gzip != "host" && a.gzip != "device") return die("Error: --gzip must be 'host' or 'device', got '" + a.gzip + "'");
         if (a.trc_n > 1) return die("Only one of kde-model, normal or lognormal is allowed!");
@@ -505,16 +541,22 @@ public:
         log.log(Logger::INFO, "%d device group(s) x %d contexts in flight, %d parser(s) per group with %d host thread(s) each", n_groups, per_group,
                 parsers_per_group, a.threads);
 
-        FILE* in = fopen(a.input.c_str(), "rb");
-        if (!in) { destroy_all(); return die("Error: cannot open " + a.input); }
+        if (a.wgs_on) {
+            uint64_t ref_length = 0;
+            tksmseq_reference_info(workers[0]->ctx, nullptr, &ref_length, nullptr);
+            a.wgs.base_count = a.wgs_have_bc ? (int64_t)a.wgs_base_count : (int64_t)(a.wgs_depth * (double)ref_length);      // src/random_wgs.cpp:169-176
+            log.log(Logger::INFO, "Reference length: %llu; whole-genome fragments for %lld bases", (unsigned long long)ref_length, (long long)a.wgs.base_count);
+        }
+        FILE* in = a.wgs_on ? nullptr : fopen(a.input.c_str(), "rb");
+        if (!in && !a.wgs_on) { destroy_all(); return die("Error: cannot open " + a.input); }
         // the input is read through its descriptor: a pipe (Snakemake's `tksm ... | tksm sequence -i /dev/stdin`, Snakefile:283-305) may stay
         // open with nothing to read while a worker has already failed -- the reader polls it and gives up then, instead of sleeping in a
         // read() until the producer closes
-        const int in_fd = fileno(in);
+        const int in_fd = in ? fileno(in) : -1;
         bool in_regular = false;
-        { struct stat st_in; in_regular = fstat(in_fd, &st_in) == 0 && S_ISREG(st_in.st_mode); }
-        if (!a.badread.empty() && !wb.open(a.badread)) { fclose(in); destroy_all(); return die("Error: cannot open " + a.badread); }
-        if (!a.perfect.empty() && !wp.open(a.perfect)) { fclose(in); wb.close(); destroy_all(); return die("Error: cannot open " + a.perfect); }
+        { struct stat st_in; in_regular = in && fstat(in_fd, &st_in) == 0 && S_ISREG(st_in.st_mode); }
+        if (!a.badread.empty() && !wb.open(a.badread)) { if (in) fclose(in); destroy_all(); return die("Error: cannot open " + a.badread); }
+        if (!a.perfect.empty() && !wp.open(a.perfect)) { if (in) fclose(in); wb.close(); destroy_all(); return die("Error: cannot open " + a.perfect); }
         wb.bgzf = wb.gz && gzip_device; wp.bgzf = wp.gz && gzip_device;
         ChunkQueue queue;
         queue.cap = (size_t)n_workers;
@@ -562,14 +604,50 @@ public:
         uint64_t total_reads = 0;
 
         std::vector<tksmseq_batch*> templates((size_t)n_groups, nullptr);        // chained PCR: the whole input, one batch per device group
+        // chained random-wgs: the only state that is serial across batches (guarded by wgs_m): next candidate, molecules and bases so far,
+        // next batch number.  A maker thread takes it, makes its batch on its own context (milliseconds next to the sequencing of a batch)
+        // and hands it back; the batch numbers keep the writers' order, and a read's global index is its molecule's index.
+        std::mutex wgs_m; tksmseq_wgs_progress wgs_st{}; uint64_t wgs_seq = 0; bool wgs_done = a.wgs_on && a.wgs.base_count <= 0;
         auto parse_ahead = [&](int pi) {
             tksmseq_ctx* pc = pctx[(size_t)pi];
             ParsedQueue& out = *pq[(size_t)(pi / parsers_per_group)];
             for (;;) {
                 Chunk c;
                 uint64_t ticket;
+                Parsed pr;
+                if (a.wgs_on) {
+                    // (the group's hand-over ticket is taken together with the batch number: tickets and numbers rise together)
+                    std::lock_guard<std::mutex> l(out.take_m);
+                    std::unique_lock<std::mutex> l2(wgs_m);
+                    if (wgs_done || failed) break;
+                    const auto t_make = now();
+                    tksmseq_wgs_params q = a.wgs;
+                    q.first_candidate = wgs_st.next_candidate; q.n_candidates = a.wgs_batch; q.molecules_before = wgs_st.molecules; q.bases_before = wgs_st.bases;
+                    tksmseq_wgs_progress np{};
+                    if (tksmseq_wgs(pc, &q, &pr.b, &np)) { set_error(tksmseq_last_error(pc)); break; }
+                    tksmseq_batch_info(pr.b, &pr.n_reads, nullptr, nullptr);
+                    if (!pr.n_reads && !np.reached) {
+                        tksmseq_batch_free(pc, pr.b);
+                        set_error("none of " + std::to_string(a.wgs_batch) + " candidate fragments has a base (fragment length distribution '" + a.wgs_dist + "'): giving up");
+                        break;
+                    }
+                    pr.seq = wgs_seq++; pr.first_read = wgs_st.molecules;
+                    wgs_st = np;
+                    if (np.reached) wgs_done = true;
+                    ticket = out.taken++;
+                    l2.unlock();                                              // (the other groups make their batches while this one waits for room)
+                    add_clk(0, t_make);
+                    if (verbose2) fprintf(stderr, "[sequence] batch %llu maker %d: %llu molecules made in %.3f s at %.3f s\n", (unsigned long long)pr.seq, pi, (unsigned long long)pr.n_reads,
+                                          std::chrono::duration<double>(now() - t_make).count(), std::chrono::duration<double>(now() - t_start).count());
+                    std::unique_lock<std::mutex> lo(out.order_m);
+                    out.order_cv.wait(lo, [&] { return out.handed == ticket; });
+                    if (!out.push(pr)) tksmseq_batch_free(pc, pr.b);         // (closed after an error)
+                    out.handed++;
+                    out.order_cv.notify_all();
+                    continue;
+                }
                 { std::lock_guard<std::mutex> l(out.take_m); if (!queue.pop(c)) break; ticket = out.taken++; }
-                Parsed pr; pr.seq = c.seq; pr.first_read = c.first_read; pr.n_reads = c.n_reads;
+                pr.seq = c.seq; pr.first_read = c.first_read; pr.n_reads = c.n_reads;
                 bool ok = !failed;
                 if (ok) {
                     const auto t_parse = now();
@@ -870,6 +948,7 @@ public:
             if (!failed) emit_slice(u0, nt, acc);                   // the last slice (the only, empty one of an input without molecules)
             eof = true; have = 0;
         }
+        if (a.wgs_on) { eof = true; have = 0; }                       // (nothing to read: the parser threads make the batches)
         while ((!eof || have) && !failed) {
             // fill up to batch_bytes, then cut at the last molecule header so a batch holds whole molecules
             const auto t_read = now();
@@ -895,10 +974,11 @@ public:
             have -= cut;
             scan_floor = have ? have - 1 : 0;                       // (the cut was the last boundary: the rest holds none)
         }
-        { std::lock_guard<std::mutex> l(done_m); n_batches = seq; reader_done = true; }
+        if (!a.wgs_on) { std::lock_guard<std::mutex> l(done_m); n_batches = seq; reader_done = true; }
         queue.close();
         done_cv.notify_all();
         for (auto& t : parsers) t.join();
+        if (a.wgs_on) { seq = wgs_seq; { std::lock_guard<std::mutex> l(done_m); n_batches = seq; reader_done = true; } done_cv.notify_all(); }
         for (auto& q2 : pq) q2->close();                                                           // (the workers take what is still queued)
         for (auto& t : threads) t.join();
         for (auto& W : workers) { { std::lock_guard<std::mutex> l(W->m); W->jobs_closed = true; } W->cv.notify_all(); }
@@ -934,7 +1014,7 @@ public:
             if (W->wctx) { tksmseq_device_free(W->wctx, W->stage[0]); tksmseq_device_free(W->wctx, W->stage[1]); tksmseq_destroy(W->wctx); W->wctx = nullptr; }
         }
         const auto t_close = now();
-        fclose(in);
+        if (in) fclose(in);
         if ((!wb.close() || !wp.close()) && !status) { status = 1; fprintf(stderr, "Error: write failed\n"); }
         const auto t_destroy = now();
         destroy_all();

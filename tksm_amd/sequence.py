@@ -152,6 +152,11 @@ class Sequencer:
             self._chk(self._lib.tksmseq_reference_add_contig(self._ctx, name.encode(),
                                                              C.cast(buf, C.c_void_p) if buf is not None else None, len(b), 0))
 
+    def declare_contig(self, name, length):
+        """a contig known by name and length only, as `<reference>.fai` lists it (tksmseq_reference_declare_contig): enough for wgs()
+        and to_mdf_text(); run() on such a context fails"""
+        self._chk(self._lib.tksmseq_reference_declare_contig(self._ctx, name.encode(), int(length)))
+
     def contig_id(self, name):
         return self._lib.tksmseq_reference_contig_id(self._ctx, name.encode())
 
@@ -330,6 +335,25 @@ class Sequencer:
         self._chk(self._lib.tksmseq_flip(self._ctx, batch._h, C.byref(q), C.byref(h)))
         return Batch(self, h)
 
+    # ---- random-wgs: whole-genome fragments made on the device
+    def wgs(self, dist, a, b=0, base_count=None, depth=None, seed=42, first_candidate=0, n_candidates=1 << 20, state=None):
+        """The loop of RWGS_module::run (src/random_wgs.cpp:181-207) for candidates [first_candidate, first_candidate + n_candidates)
+        of a run (tksmseq_wgs): dist "normal" | "uniform" | "lognormal" | "exponential" with parameters a, b; base_count, or depth
+        (base_count = int(depth * reference length)); state = (molecules, bases) emitted by the calls before this one.  Returns
+        (batch, state): state = {"next_candidate", "molecules", "bases", "reached"} -- pass first_candidate=state["next_candidate"],
+        state=(state["molecules"], state["bases"]) to the next call until reached."""
+        if dist not in L.WGS_DISTS:
+            raise ValueError("Invalid fragment length distribution")
+        if (base_count is None) == (depth is None):
+            raise ValueError("Either base-count or depth is required!" if base_count is None else "base_count and depth exclude each other")
+        if base_count is None:
+            base_count = int(float(depth) * float(self.reference_info()["total_bases"]))
+        mols, bases = state if state is not None else (0, 0)
+        p = L.WgsParams(seed, L.WGS_DISTS[dist], 0, float(a), float(b), int(base_count), first_candidate, n_candidates, mols, bases)
+        h, pr = C.c_void_p(), L.WgsProgress()
+        self._chk(self._lib.tksmseq_wgs(self._ctx, C.byref(p), C.byref(h), C.byref(pr)))
+        return Batch(self, h), {"next_candidate": pr.next_candidate, "molecules": pr.molecules, "bases": pr.bases, "reached": bool(pr.reached)}
+
     def to_mdf_text(self, batch):
         """molecule_descriptor::operator<< of every molecule (src/interval.h:898-905)."""
         t, n = C.c_void_p(), C.c_uint64()
@@ -409,6 +433,13 @@ class Sequencer:
         self._chk(self._lib.tksmseq_interleave_records(self._ctx, n, sp, op, npr, C.c_void_p(dst_ptr), dst_capacity,
                                                        C.byref(out)))
         return out.value
+
+
+def random_wgs_main(argv):
+    """`tksm random-wgs ...` (src/tksm.cpp); argv[0] == "random-wgs"."""
+    lib = L.load()
+    arr = (C.c_char_p * len(argv))(*[a.encode() for a in argv])
+    return lib.tksmseq_random_wgs_main(len(argv), arr)
 
 
 def sequence_main(argv):
