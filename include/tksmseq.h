@@ -428,6 +428,39 @@ typedef struct {
 } tksmseq_flip_params;
 int tksmseq_flip(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_flip_params* params, tksmseq_batch** out);
 
+/* ---- tail-noise: random and hairpin noise appended on the device ----------------------------------------------------------------------
+ * tksmseq_append_noise replaces NoiseAdder::operator() (src/append_noise.cpp:83-128; module AppendNoise_module :131-229) -- not to be
+ * confused with the Badread tail-noise MODEL of tksmseq_load_tail_model.  Molecule i (depth-unrolled, like every segment edit; the
+ * reference's module reads without unrolling and gives all copies one draw) draws a noise length L from normal(mu, sigma) or
+ * lognormal(mu, sigma) = exp of the normal, keyed by (seed, first_molecule_index + i), clamped in double to the int range (NaN: 0) and
+ * truncated toward zero; L <= 0 leaves the molecule as it is.
+ *   random mode: one literal of L letters on the plus strand is appended, each letter uniform over the positions of `alphabet` (a
+ *     repeated letter is that much more likely);
+ *   palindromic mode: the segments are walked from the last to the first, each copied with its strand toggled and its substitutions,
+ *     until the copied bases are strictly above L; the last copy is then cut back to L bases in all (original on the plus strand:
+ *     end -= extra, on the minus strand: start += extra; a total that equals L copies the next segment and cuts it to nothing).  Every
+ *     base of the hairpin (min(L, molecule size) bases) then gets, with probability error_rate, a substitution by a letter of the
+ *     alphabet.  Any error rate runs: <= 0 adds nothing, >= 1 substitutes every base.  The substitutions of a new segment are written
+ *     sorted by position, a copied one before a new one at the same position.
+ * Deviations from the reference: the copied substitutions of the cut copy are re-based to the kept range and those outside it dropped
+ * (the reference keeps them at positions that no longer exist); a copy cut to length 0 is not written; depth-unrolled input.
+ * TKSMSEQ_EINVAL: an empty alphabet, a non-finite mu, sigma <= 0 or non-finite, a NaN error rate, an unknown distribution (undefined
+ * behaviour or an exit in the reference); TKSMSEQ_ELIMIT: in random mode a drawn L above 2^20 (the message names the molecule). */
+#define TKSMSEQ_NOISE_NORMAL 0
+#define TKSMSEQ_NOISE_LOGNORMAL 1
+typedef struct {
+    uint64_t seed;
+    uint64_t first_molecule_index;
+    int32_t dist;                    /* TKSMSEQ_NOISE_* (--length-dist NAME,MU,SIGMA) */
+    int32_t palindromic;             /* --palindromic */
+    double mu, sigma;
+    double error_rate;               /* --error-rate (0.5), palindromic mode */
+    const char* alphabet;            /* --alphabet ("AGTC") */
+    int32_t flags;                   /* TKSMSEQ_MOL_NO_COMMENTS or 0 */
+    int32_t reserved;
+} tksmseq_noise_params;
+int tksmseq_append_noise(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_noise_params* params, tksmseq_batch** out);
+
 /* ---- random-wgs: whole-genome fragments made on the device ---------------------------------------------------------------------------
  * tksmseq_wgs replaces the loop of RWGS_module::run (src/random_wgs.cpp:181-207; position_dist / frag_length_dist / strand_dist, the
  * contig look-up :190-194, the clip to the contig end :195-198, the molecule :200-204, the stop rule :188, :205).  There is no input
@@ -491,6 +524,9 @@ int tksmseq_flip_main(int argc, char** argv);
  * --depth, the reference's messages and exit codes; the contig table from <reference>.fai (from the FASTA itself when that is missing);
  * MDF text out, streamed in batches of --batch-molecules candidates over --devices. */
 int tksmseq_random_wgs_main(int argc, char** argv);
+/* `tksm tail-noise` (AppendNoise_module src/append_noise.cpp:131-229): -i, -o, --length-dist NAME,MU,SIGMA, --alphabet, --palindromic,
+ * --error-rate with the reference's messages and exit codes; streamed in batches of --batch-bytes over --devices like `tksm polyA`. */
+int tksmseq_tail_noise_main(int argc, char** argv);
 int tksmseq_sequence_main(int argc, char** argv);
 
 #ifdef __cplusplus

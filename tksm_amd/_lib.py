@@ -97,6 +97,16 @@ WGS_NORMAL, WGS_UNIFORM, WGS_LOGNORMAL, WGS_EXPONENTIAL = 0, 1, 2, 3
 WGS_DISTS = {"normal": WGS_NORMAL, "uniform": WGS_UNIFORM, "lognormal": WGS_LOGNORMAL, "exponential": WGS_EXPONENTIAL}
 MOL_NO_COMMENTS = 1
 
+
+class NoiseParams(C.Structure):              # tksmseq_noise_params
+    _fields_ = [("seed", C.c_uint64), ("first_molecule_index", C.c_uint64), ("dist", C.c_int32), ("palindromic", C.c_int32),
+                ("mu", C.c_double), ("sigma", C.c_double), ("error_rate", C.c_double), ("alphabet", C.c_char_p), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+NOISE_NORMAL, NOISE_LOGNORMAL = 0, 1
+NOISE_DISTS = {"normal": NOISE_NORMAL, "lognormal": NOISE_LOGNORMAL}
+
 SYMBOLS = [
     "tksmseq_create", "tksmseq_destroy", "tksmseq_last_error", "tksmseq_version", "tksmseq_set_stream",
     "tksmseq_synchronize", "tksmseq_reference_add_fasta", "tksmseq_reference_add_contig",
@@ -114,6 +124,7 @@ SYMBOLS = [
     "tksmseq_result_gzip", "tksmseq_gzip_device", "tksmseq_gzip_download_range", "tksmseq_gzip_download_offsets",
     "tksmseq_gzip_copy_device", "tksmseq_gzip_eof",
     "tksmseq_reference_declare_contig", "tksmseq_wgs", "tksmseq_random_wgs_main",
+    "tksmseq_append_noise", "tksmseq_tail_noise_main",
 ]
 
 _lib = None
@@ -193,6 +204,8 @@ def load():
         "tksmseq_reference_declare_contig": (C.c_int, [vp, C.c_char_p, u64]),
         "tksmseq_wgs": (C.c_int, [vp, P(WgsParams), P(vp), P(WgsProgress)]),
         "tksmseq_random_wgs_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
+        "tksmseq_append_noise": (C.c_int, [vp, vp, P(NoiseParams), P(vp)]),
+        "tksmseq_tail_noise_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

@@ -114,4 +114,34 @@ hipError_t launch_wgs_cut(uint64_t n, const uint4* plan, const uint64_t* rank, c
 hipError_t launch_wgs_write(uint64_t n, const uint4* plan, const uint64_t* rank, const uint64_t* idlen, const uint64_t* id_off, const uint32_t* name_off,
                             const uint32_t* name_len, const uint8_t* names, uint64_t mols_before, const MolOut& o, hipStream_t s);
 
+// tail-noise (src/append_noise.cpp:83-128, NoiseAdder::operator()): a noise length L per molecule from normal / lognormal(mu, sigma);
+// random mode appends a literal of L letters of the alphabet, palindromic mode appends the molecule's last segments again, strands
+// toggled, the last copy cut so that the hairpin has min(L, molecule size) bases, then a Bernoulli(error_rate) substitution per hairpin
+// base.  The plan is one lane per molecule; the per-base work is spread: letters over a flat grid of 4-letter Philox blocks, hairpin
+// bases over the 64 lanes of one wave per molecule (k_pal_count / k_pal_write).  See mdf_kernels.hip.
+constexpr int NOISE_MAX_LEN = 1 << 20;      // random mode: letters of one literal (the limit polyA and tag have)
+enum { NOISE_NORMAL = 0, NOISE_LOGNORMAL = 1 };
+struct NoiseParams {
+    uint64_t seed;
+    int dist;                             // NOISE_*
+    double mu, sigma, error_rate;
+    const uint8_t* alphabet;              // [k] (device); repeated letters weight the draw
+    uint32_t k;
+};
+// random mode (plan != null is the palindromic one): len[r] = L (0 for L <= 0), nblk[r] = ceil(L / 4), *over = the smallest r whose
+// L is above NOISE_MAX_LEN (its len is 0; the caller sets *over to ~0 first).  Palindromic mode: plan[r] = {segments copied (the cut
+// one included; 0: the molecule stays as it is), bases cut off the last copy, hairpin bases H = min(L, molecule size), 0}.
+hipError_t launch_noise_plan(const MolView& m, const NoiseParams& p, uint64_t first_index, uint32_t* len, uint64_t* nblk, unsigned long long* over,
+                             uint4* plan, hipStream_t s);
+// blk_off: exclusive scan of nblk ([n + 1]), n_blocks its total.  Molecule r with L > 0 gets literal lit_base + r = L letters at
+// pool_base + 4 x blk_off[r] and post[r] = that literal; post (all EDIT_NONE) and the new entries of lits (zero) are set by the caller.
+hipError_t launch_noise_fill(uint64_t n, uint64_t n_blocks, const NoiseParams& p, uint64_t first_index, const uint32_t* len, const uint64_t* blk_off,
+                             uint32_t lit_base, uint64_t pool_base, uint64_t* lits, uint8_t* pool, uint32_t* post, hipStream_t s);
+// palindromic mode, after launch_edit_count / launch_edit_write without literals or flip: the count ADDS the hairpin's segments and
+// substitutions to n_ivls / n_mods, the write puts them behind the molecule's own (ivl_off / mod_off: scans of the sums)
+hipError_t launch_pal_count(const MolView& m, const NoiseParams& p, uint64_t first_index, const uint4* plan, uint64_t* n_ivls, uint64_t* n_mods,
+                            hipStream_t s);
+hipError_t launch_pal_write(const MolView& m, const NoiseParams& p, uint64_t first_index, const uint4* plan, const uint64_t* ivl_off,
+                            const uint64_t* mod_off, const MolOut& o, hipStream_t s);
+
 }  // namespace tk

@@ -12,7 +12,8 @@
 //   SingleCellBarcoder::run      src/scb.cpp:57-80        append the CB barcode of the header comment
 //   flip_molecule                src/interval.h:908-920   reverse the segment order, toggle every strand
 //   RWGS_module::run             src/random_wgs.cpp:181-207 whole-genome fragments: position, length and strand draws, no input
-// Integer / byte work, one LANE per molecule: the tables of a molecule are a few dozen bytes, the work per molecule is a short
+//   NoiseAdder::operator()       src/append_noise.cpp:83-128 tail noise: a random literal, or the last segments again as a hairpin
+// Integer / byte work, one LANE per molecule (tail-noise alone spreads its per-base work: one wave per molecule, or a flat grid): the tables of a molecule are a few dozen bytes, the work per molecule is a short
 // serial walk (tree of copies; list of segments).  The reference draws from a sequential Mersenne Twister; here every
 // decision has its own Philox counter (template molecule, path of copy cycles, purpose), so the result does not depend on
 // the order molecules are processed in, and the CPU oracle (oracle/mdf_ops_oracle.py) reproduces it bit for bit.
@@ -24,7 +25,8 @@ namespace tk {
 
 struct Ph4m { uint32_t x, y, z, w; };
 enum { ST_PCR_PICK = 16, ST_PCR_EMIT = 17, ST_PCR_CHILD = 18, ST_PCR_MUT = 19, ST_TRC_LEN = 24, ST_TRC_SIDE = 25,
-       ST_PLA_LEN = 26, ST_TAG5 = 27, ST_TAG3 = 28, ST_FLIP = 29, ST_WGS_POS = 32, ST_WGS_LEN = 33, ST_WGS_STRAND = 34 };
+       ST_PLA_LEN = 26, ST_TAG5 = 27, ST_TAG3 = 28, ST_FLIP = 29, ST_WGS_POS = 32, ST_WGS_LEN = 33, ST_WGS_STRAND = 34,
+       ST_NOISE_LEN = 40, ST_NOISE_SEQ = 41, ST_NOISE_ERR = 42 };
 
 DEV Ph4m philox_raw(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
@@ -652,6 +654,208 @@ __global__ void k_wgs_write(uint64_t n, const uint4* __restrict__ plan, const ui
 }
 
 // ------------------------------------------------------------------------------------------------
+// tail-noise (src/append_noise.cpp:83-128).  k_noise_plan: one lane per molecule draws the noise length L (Box-Muller on block 0 of
+// ST_NOISE_LEN, exp for the lognormal; clamped in double, NaN -> 0, toward zero) and, for the palindromic mode, walks the segment sizes
+// from the last one backwards until their sum is strictly above L (:93-107).
+// Random mode (:118-126): letter j of molecule g is alphabet[umulhi(word j, k)], word j = component j % 4 of block j / 4 of
+// ST_NOISE_SEQ -- the tag rule.  k_noise_fill is a FLAT grid, one lane per 4-letter Philox block of the whole batch, the owner found by
+// binary search in the scan of the block counts: lengths vary from molecule to molecule (lognormal: by orders of magnitude), so a wave
+// per molecule would idle most lanes on a 50-letter literal (13 blocks) and serialise a 10^6-letter one; the flat grid's work is even
+// whatever the lengths are, at the price of ~21 probes of a table that stays in L2.  The literal then goes through k_edit_count /
+// k_edit_write like an ambiguous tag.
+// Palindromic mode: k_edit_count / k_edit_write size and write the molecule itself; k_pal_count / k_pal_write, ONE WAVE PER MOLECULE,
+// add the hairpin behind it.  Lanes stride over the bases of a new segment 64 at a time; base t of the hairpin (t counts over the new
+// segments in the order they are appended) draws components (0, 1) of block t / 2 of ST_NOISE_ERR when t is even, (2, 3) when odd:
+// u01(first) < error_rate puts alphabet[umulhi(second, k)] at that position of its segment.  New substitutions are counted with ballot +
+// popcount; the write pass recomputes the draws and places a new substitution at (running count) + (its rank in the ballot) + (copied
+// substitutions at or before its position), a copied one at (its stable rank among the copied) + (new ones before its position): the
+// segment's list comes out sorted by position, a copied substitution before a new one at the same position.  The copied substitutions
+// of the cut copy are re-based to the kept range and those outside dropped (einterval::truncate); a copy cut to nothing is not written.
+// ------------------------------------------------------------------------------------------------
+DEV int noise_length(const NoiseParams& P, uint64_t g) {
+    const Ph4m w = philox_mol(P.seed, g, ST_NOISE_LEN, 0);
+    const double v = P.mu + P.sigma * box_muller(w.x, w.y);
+    return wgs_to_int(P.dist == NOISE_LOGNORMAL ? exp(v) : v);
+}
+
+__global__ void k_noise_plan(MolView M, NoiseParams P, uint64_t first_index, uint32_t* __restrict__ len, uint64_t* __restrict__ nblk,
+                             unsigned long long* __restrict__ over, uint4* __restrict__ plan) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= M.B.n_reads) return;
+    const int L = noise_length(P, first_index + r);
+    if (!plan) {
+        uint32_t l = L > 0 ? (uint32_t)L : 0u;
+        if (l > (uint32_t)NOISE_MAX_LEN) { atomicMin(over, (unsigned long long)r); l = 0u; }
+        len[r] = l; nblk[r] = (l + 3u) >> 2;
+        return;
+    }
+    uint32_t ncopy = 0, extra = 0;
+    unsigned long long total = 0ull;
+    if (L > 0) {
+        const uint32_t ib = M.B.reads[2 * r], ic = M.B.reads[2 * r + 1];
+        for (uint32_t q = 0; q < ic; q++) {
+            total += seg_size(M.B.intervals + 4ull * (ib + ic - 1 - q));
+            ncopy++;
+            if (total > (unsigned long long)L) { extra = (uint32_t)(total - (unsigned long long)L); break; }
+        }
+    }
+    plan[r] = make_uint4(ncopy, extra, (uint32_t)(total - extra), 0u);
+}
+
+__global__ void k_noise_fill(uint64_t n, uint64_t n_blocks, NoiseParams P, uint64_t first_index, const uint32_t* __restrict__ len,
+                             const uint64_t* __restrict__ blk_off, uint32_t lit_base, uint64_t pool_base, uint64_t* __restrict__ lits,
+                             uint8_t* __restrict__ pool, uint32_t* __restrict__ post) {
+    const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n_blocks) return;
+    uint64_t lo = 0, hi = n;                                          // the owner: the last r with blk_off[r] <= b (blk_off[n] = n_blocks > b)
+    while (lo + 1 < hi) { const uint64_t mid = (lo + hi) >> 1; if (blk_off[mid] <= b) lo = mid; else hi = mid; }
+    const uint64_t r = lo, at = pool_base + 4ull * blk_off[r];
+    const uint32_t jb = (uint32_t)(b - blk_off[r]), L = len[r];
+    if (jb == 0u) {
+        const uint32_t li = lit_base + (uint32_t)r;
+        lits[2ull * li] = at; lits[2ull * li + 1] = L;
+        post[r] = li;
+    }
+    const Ph4m w = philox_mol(P.seed, first_index + r, ST_NOISE_SEQ, jb);
+    const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const uint32_t j = 4u * jb + (uint32_t)c;
+        if (j < L) pool[at + j] = P.alphabet[__umulhi(ws[c], P.k)];
+    }
+}
+
+// copy q (0: of the last segment) of the hairpin of a molecule with plan pl
+struct PalSeg {
+    const uint32_t* iv;
+    uint32_t nsz, fx, mb, me;             // bases of the copy; first forward offset kept (substitutions are re-based by it); the original's substitutions
+    bool cut;
+};
+DEV PalSeg pal_seg(const BatchView& B, uint32_t ib, uint32_t ic, uint32_t q, const uint4& pl) {
+    PalSeg s;
+    s.iv = B.intervals + 4ull * (ib + ic - 1 - q);
+    const uint32_t sz = seg_size(s.iv);
+    s.cut = q + 1 == pl.x && pl.y > 0u;
+    s.nsz = s.cut ? sz - pl.y : sz;
+    s.fx = (s.cut && (s.iv[3] >> 31)) ? pl.y : 0u;                    // original on the plus strand: end -= extra; on the minus strand: start += extra
+    s.mb = s.iv[3] & 0x7fffffffu; s.me = s.iv[7] & 0x7fffffffu;
+    return s;
+}
+DEV bool pal_kept(const PalSeg& s, uint32_t p) { return !s.cut || (p >= s.fx && p - s.fx < s.nsz); }
+DEV uint32_t pal_kept_count(const BatchView& B, const PalSeg& s, uint32_t lane) {
+    if (!s.cut) return s.me - s.mb;
+    uint32_t n = 0;
+    for (uint32_t m0 = s.mb; m0 < s.me; m0 += 64u) {
+        const uint32_t m = m0 + lane;
+        n += (uint32_t)__popcll(__ballot(m < s.me && pal_kept(s, B.mods[2ull * m])));
+    }
+    return n;
+}
+DEV bool noise_hit(const NoiseParams& P, uint64_t g, uint32_t t, uint32_t& pick) {
+    const Ph4m w = philox_mol(P.seed, g, ST_NOISE_ERR, t >> 1);
+    pick = __umulhi((t & 1u) ? w.w : w.y, P.k);
+    return u01((t & 1u) ? w.z : w.x) < P.error_rate;
+}
+
+__global__ void __launch_bounds__(256) k_pal_count(MolView M, NoiseParams P, uint64_t first_index, const uint4* __restrict__ plan,
+                                                   uint64_t* __restrict__ n_ivls, uint64_t* __restrict__ n_mods) {
+    const uint64_t r = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (r >= M.B.n_reads) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint4 pl = plan[r];
+    if (pl.x == 0u) return;
+    const BatchView& B = M.B;
+    const uint32_t ib = B.reads[2 * r], ic = B.reads[2 * r + 1];
+    const uint64_t g = first_index + r;
+    const bool draws = P.error_rate > 0.0;                            // (<= 0: no draw is below it)
+    uint32_t t0 = 0, nseg = 0;
+    uint64_t nm = 0;
+    for (uint32_t q = 0; q < pl.x; q++) {
+        const PalSeg s = pal_seg(B, ib, ic, q, pl);
+        if (s.cut && s.nsz == 0u) continue;
+        nseg++;
+        nm += pal_kept_count(B, s, lane);
+        if (draws)
+            for (uint64_t c0 = 0; c0 < s.nsz; c0 += 64u) {
+                const uint64_t j = c0 + lane;
+                uint32_t pick;
+                nm += (uint64_t)__popcll(__ballot(j < s.nsz && noise_hit(P, g, t0 + (uint32_t)j, pick)));
+            }
+        t0 += s.nsz;
+    }
+    if (lane == 0u) { n_ivls[r] += nseg; n_mods[r] += nm; }
+}
+
+__global__ void __launch_bounds__(256) k_pal_write(MolView M, NoiseParams P, uint64_t first_index, const uint4* __restrict__ plan,
+                                                   const uint64_t* __restrict__ ivl_off, const uint64_t* __restrict__ mod_off, MolOut O) {
+    const uint64_t r = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (r >= M.B.n_reads) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint4 pl = plan[r];
+    if (pl.x == 0u) return;
+    const BatchView& B = M.B;
+    const uint32_t ib = B.reads[2 * r], ic = B.reads[2 * r + 1];
+    const uint64_t g = first_index + r;
+    const bool draws = P.error_rate > 0.0;
+    uint64_t io = ivl_off[r] + ic, mo = mod_off[r] + mol_mods(B, (uint32_t)r);      // behind what k_edit_write wrote
+    uint32_t t0 = 0;
+    for (uint32_t q = 0; q < pl.x; q++) {
+        const PalSeg s = pal_seg(B, ib, ic, q, pl);
+        if (s.cut && s.nsz == 0u) continue;
+        if (lane == 0u) {
+            const bool minus = s.iv[3] >> 31;
+            uint32_t* ov = O.intervals + 4ull * io;
+            ov[0] = s.iv[0];
+            ov[1] = s.iv[1] + s.fx;
+            ov[2] = (s.cut && !minus) ? s.iv[2] - pl.y : s.iv[2];
+            ov[3] = (uint32_t)mo | (minus ? 0u : 0x80000000u);        // strand toggled
+        }
+        io++;
+        const uint32_t kept = pal_kept_count(B, s, lane);
+        // stable rank of the copied substitution m among the kept ones, by re-based position
+        auto srank = [&](uint32_t m, uint32_t pr) {
+            uint32_t k = 0;
+            for (uint32_t x = s.mb; x < s.me; x++) {
+                const uint32_t px = B.mods[2ull * x];
+                if (pal_kept(s, px)) k += (px - s.fx < pr || (px - s.fx == pr && x < m)) ? 1u : 0u;
+            }
+            return k;
+        };
+        uint32_t n_new = 0;
+        uint64_t c0 = 0;
+        for (; c0 < s.nsz; c0 += 64u) {
+            const uint64_t j = c0 + lane;
+            uint32_t pick = 0;
+            const bool hit = draws && j < s.nsz && noise_hit(P, g, t0 + (uint32_t)j, pick);
+            const unsigned long long mask = __ballot(hit);
+            if (hit) {
+                uint32_t before = 0;                                  // copied substitutions at or before position j
+                for (uint32_t x = s.mb; x < s.me; x++) { const uint32_t px = B.mods[2ull * x]; before += (pal_kept(s, px) && px - s.fx <= (uint32_t)j) ? 1u : 0u; }
+                const uint64_t at = mo + n_new + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull)) + before;
+                O.mods[2 * at] = (uint32_t)j; O.mods[2 * at + 1] = P.alphabet[pick];
+            }
+            for (uint32_t m = s.mb + lane; m < s.me; m += 64u) {       // copied substitutions whose position falls into this run of 64
+                const uint32_t p = B.mods[2ull * m];
+                if (!pal_kept(s, p)) continue;
+                const uint32_t pr = p - s.fx;
+                if (pr < c0 || pr >= c0 + 64u) continue;
+                const uint64_t at = mo + srank(m, pr) + n_new + (uint32_t)__popcll(mask & ((1ull << (pr - (uint32_t)c0)) - 1ull));
+                O.mods[2 * at] = pr; O.mods[2 * at + 1] = B.mods[2ull * m + 1];
+            }
+            n_new += (uint32_t)__popcll(mask);
+        }
+        for (uint32_t m = s.mb + lane; m < s.me; m += 64u) {           // positions beyond the segment (an uncut copy keeps them, as the reference does)
+            const uint32_t p = B.mods[2ull * m];
+            if (!pal_kept(s, p) || p - s.fx < c0) continue;
+            const uint64_t at = mo + srank(m, p - s.fx) + n_new;
+            O.mods[2 * at] = p - s.fx; O.mods[2 * at + 1] = B.mods[2ull * m + 1];
+        }
+        mo += kept + n_new;
+        t0 += s.nsz;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
 static inline unsigned nblk(uint64_t n) { return (unsigned)((n + 127) / 128); }
@@ -730,6 +934,33 @@ hipError_t launch_wgs_write(uint64_t n, const uint4* plan, const uint64_t* rank,
                             const uint32_t* name_len, const uint8_t* names, uint64_t mols_before, const MolOut& o, hipStream_t s) {
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(k_wgs_write, dim3(nblk(n)), dim3(128), 0, s, n, plan, rank, idlen, id_off, name_off, name_len, names, mols_before, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_noise_plan(const MolView& m, const NoiseParams& p, uint64_t first_index, uint32_t* len, uint64_t* n_blk, unsigned long long* over,
+                             uint4* plan, hipStream_t s) {
+    if (!m.B.n_reads) return hipSuccess;
+    hipLaunchKernelGGL(k_noise_plan, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, p, first_index, len, n_blk, over, plan);
+    return hipGetLastError();
+}
+hipError_t launch_noise_fill(uint64_t n, uint64_t n_blocks, const NoiseParams& p, uint64_t first_index, const uint32_t* len, const uint64_t* blk_off,
+                             uint32_t lit_base, uint64_t pool_base, uint64_t* lits, uint8_t* pool, uint32_t* post, hipStream_t s) {
+    if (!n || !n_blocks) return hipSuccess;
+    hipLaunchKernelGGL(k_noise_fill, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, s, n, n_blocks, p, first_index, len, blk_off, lit_base, pool_base,
+                       lits, pool, post);
+    return hipGetLastError();
+}
+// one wave per molecule: 4 molecules per block of 256
+hipError_t launch_pal_count(const MolView& m, const NoiseParams& p, uint64_t first_index, const uint4* plan, uint64_t* n_ivls, uint64_t* n_mods,
+                            hipStream_t s) {
+    if (!m.B.n_reads) return hipSuccess;
+    hipLaunchKernelGGL(k_pal_count, dim3((unsigned)((m.B.n_reads + 3) / 4)), dim3(256), 0, s, m, p, first_index, plan, n_ivls, n_mods);
+    return hipGetLastError();
+}
+hipError_t launch_pal_write(const MolView& m, const NoiseParams& p, uint64_t first_index, const uint4* plan, const uint64_t* ivl_off,
+                            const uint64_t* mod_off, const MolOut& o, hipStream_t s) {
+    if (!m.B.n_reads) return hipSuccess;
+    hipLaunchKernelGGL(k_pal_write, dim3((unsigned)((m.B.n_reads + 3) / 4)), dim3(256), 0, s, m, p, first_index, plan, ivl_off, mod_off, o);
     return hipGetLastError();
 }
 

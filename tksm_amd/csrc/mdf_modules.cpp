@@ -1,5 +1,5 @@
-// mdf_modules.cpp -- the `tksm pcr`, `truncate`, `polyA`, `tag`, `scb` and `flip` modules on top of the C-ABI (MDF file in, MDF file out),
-// and `random-wgs` (no input: MDF file out).
+// mdf_modules.cpp -- the `tksm pcr`, `truncate`, `polyA`, `tag`, `scb`, `flip` and `tail-noise` modules on top of the C-ABI (MDF file in, MDF
+// file out), and `random-wgs` (no input: MDF file out).
 //
 // Mirrors (file:line into vpc-ccg/tksm):
 //   PCR_module::impl        src/pcr.cpp:91-260       flags -i -o --molecule-count --cycles --error-rate --efficiency -x/--preset,
@@ -12,6 +12,7 @@
 //   SingleCellBarcoder      src/scb.cpp:14-92        --keep-meta-barcodes
 //   StrandMan_module        src/strand_man.cpp:20-124 -p/--flip-probability (outside [0, 1]: logged, not refused)
 //   RWGS_module             src/random_wgs.cpp:24-229 -r/--reference, --frag-len-dist "NAME A [B]", -o, --base-count | --depth
+//   AppendNoise_module      src/append_noise.cpp:131-229 --length-dist NAME,MU,SIGMA, --alphabet, --palindromic, --error-rate
 //   utility flags           src/module.h:75-104      -s/--seed (default 42), --verbosity, --log-file, -h
 // All stream: `truncate` and the four segment edits read the input in batches of whole molecules (--batch-bytes), `pcr` amplifies its templates in slices
 // of about --slice-molecules output molecules (tksmseq_pcr_params::template_begin / _end); the pieces go round the entries of
@@ -530,6 +531,68 @@ extern "C" int tksmseq_flip_main(int argc0, char** argv0) {
         tksmseq_flip_params q = p;
         q.first_molecule_index = first;
         return tksmseq_flip(ctx, in, &q, out);
+    });
+}
+
+extern "C" int tksmseq_tail_noise_main(int argc0, char** argv0) {
+    std::vector<std::string> arg_store; std::vector<char*> arg_ptrs;
+    tkmod::split_equals(argc0, argv0, arg_store, arg_ptrs);
+    const int argc = (int)arg_ptrs.size(); char** const argv = arg_ptrs.data();
+    Common c;
+    tksmseq_noise_params p{};
+    p.error_rate = 0.5;
+    std::string alphabet = "AGTC", dist_text;
+    bool have_dist = false;
+    for (int i = 1; i < argc; i++) {
+        const int k = common_flag(argc, argv, i, c);
+        if (k < 0) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; }
+        if (k) continue;
+        const std::string o = argv[i];
+        const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
+        if (o == "--length-dist" && v) { dist_text = v; have_dist = true; i++; }
+        else if (o == "--alphabet" && v) { alphabet = v; i++; }
+        else if (o == "--error-rate" && v) { p.error_rate = atof(v); i++; }
+        else if (o == "--palindromic") {
+            p.palindromic = 1;
+            // (cxxopts' boolean: --palindromic=true|false)
+            if (v && (!strcmp(v, "true") || !strcmp(v, "false"))) p.palindromic = !strcmp(argv[++i], "true");
+        } else { fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1; }
+    }
+    static const char* help =
+        "Append Noise module\nusage: tail-noise -i INPUT -o OUTPUT --length-dist NAME,MU,SIGMA [--alphabet AGTC] [--palindromic] [--error-rate 0.5] [-s SEED]\n"
+        "                  [--devices D[,D...]] [--batch-bytes B] [--verbosity L] [--log-file F]\n"
+        "NAME: normal | lognormal.  Random noise: a literal of that many letters of the alphabet (a repeated letter is more likely) behind every\n"
+        "molecule; --palindromic: the molecule's last bases again as a hairpin, each substituted with probability --error-rate\n";
+    if (c.help) { printf("%s", help); return 0; }
+    // validate_arguments (src/append_noise.cpp:174-190)
+    int missing = 0;
+    if (c.input.empty()) { fprintf(stderr, "input is required!\n"); missing++; }
+    if (c.output.empty()) { fprintf(stderr, "output is required!\n"); missing++; }
+    if (!have_dist) { fprintf(stderr, "length-dist is required!\n"); missing++; }
+    if (missing) { fprintf(stderr, "%s\n", help); return 1; }
+    // DistVisitor::get_dist (:26-45): the name first; the reference throws on a list without three fields or a field that is no number
+    {
+        std::vector<std::string> f;
+        size_t a = 0;
+        for (;;) { const size_t e = dist_text.find(',', a); f.push_back(dist_text.substr(a, e == std::string::npos ? e : e - a)); if (e == std::string::npos) break; a = e + 1; }
+        if (f[0] == "normal") p.dist = TKSMSEQ_NOISE_NORMAL;
+        else if (f[0] == "lognormal") p.dist = TKSMSEQ_NOISE_LOGNORMAL;
+        else { fprintf(stderr, "Distribution not implemented!\n"); return 1; }
+        std::vector<double> d;
+        if (f.size() != 3 || !parse_doubles((f[1] + "," + f[2]).c_str(), d) || d.size() != 2) { fprintf(stderr, "length-dist needs NAME,MU,SIGMA (got '%s')\n", dist_text.c_str()); return 1; }
+        p.mu = d[0]; p.sigma = d[1];
+    }
+    // (what the std:: distributions leave undefined: refused before any work, with the library's messages)
+    if (!std::isfinite(p.mu) || !std::isfinite(p.sigma) || !(p.sigma > 0.0)) { fprintf(stderr, "Error: tail-noise: mu must be finite, sigma finite and positive\n"); return 1; }
+    if (alphabet.empty()) { fprintf(stderr, "Error: tail-noise: the alphabet is empty\n"); return 1; }
+    if (std::isnan(p.error_rate)) { fprintf(stderr, "Error: tail-noise: the error rate is not a number\n"); return 1; }
+    Logger log;
+    if (!open_log(c, "tail-noise", log)) return 1;
+    p.seed = (uint64_t)c.seed; p.alphabet = alphabet.c_str();
+    return stream_transform(c, log, "tail-noise", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, uint64_t first, tksmseq_batch** out) {
+        tksmseq_noise_params q = p;
+        q.first_molecule_index = first;
+        return tksmseq_append_noise(ctx, in, &q, out);
     });
 }
 

@@ -3,6 +3,7 @@
 //   tksmseq_truncate       src/truncate.cpp:23-65, :77-227, :322-351, :362-404
 //   tksmseq_polya / _tag / _scb / _flip   src/polyA.cpp:133-148, src/tag.cpp:70-113, src/scb.cpp:57-80, src/interval.h:908-920
 //   tksmseq_wgs            src/random_wgs.cpp:181-207 (no input: the molecules are made on the device)
+//   tksmseq_append_noise   src/append_noise.cpp:83-128 (tail-noise: a random literal or a hairpin behind every molecule)
 //   tksmseq_batch_to_mdf_text   molecule_descriptor::operator<<, src/interval.h:898-905 (+ dump_comment :880-890)
 // The molecule tables stay on the device from one transform to the next and into tksmseq_run; only sizes, per-read lengths
 // (which the host needs to size and order a Seq batch) and, for the text writer, the tables themselves come back.
@@ -473,7 +474,10 @@ static int edit_literals(tksmseq_ctx* ctx, const tksmseq_batch* in, tksmseq_batc
 
 // count, scan, allocate, write: every molecule of `in` (unrolled) with literal pre[r] in front of and post[r] behind its segments, which
 // are reversed and strand-toggled where flip[r] (device arrays; null: none of that kind).  b's literal table is already complete.
-static int edit_apply(tksmseq_ctx* ctx, const tksmseq_batch* in, const uint32_t* pre, const uint32_t* post, const uint8_t* flip, tksmseq_batch* b) {
+// pal: the palindromic tail noise of tksmseq_append_noise, whose kernels add a hairpin behind each molecule to the counts and to the tables.
+struct PalHook { tk::NoiseParams P; uint64_t first; const uint4* plan; };
+static int edit_apply(tksmseq_ctx* ctx, const tksmseq_batch* in, const uint32_t* pre, const uint32_t* post, const uint8_t* flip, tksmseq_batch* b,
+                      const PalHook* pal = nullptr) {
     hipStream_t s = ctx->stream;
     const uint64_t n = in->n_reads;
     tk::MolView M{view_of(in), in->d_dup.p ? in->d_dup.as<uint32_t>() : nullptr, in->n_intervals, in->n_mods, nullptr, n};
@@ -481,6 +485,7 @@ static int edit_apply(tksmseq_ctx* ctx, const tksmseq_batch* in, const uint32_t*
     for (DevBuf* pb_ : {&n_ivl, &n_mod, &n_idl, &o_ivl, &o_mod, &o_id}) { pb_->pooled = true; pb_->pool_stream = s; }   // (per-call temporaries: DevCache, ctx.h)
     for (DevBuf* x : {&n_ivl, &n_mod, &n_idl}) HIPCHK(ctx, x->ensure(n * 8 + 16));
     HIPCHK(ctx, tk::launch_edit_count(M, pre, post, n_ivl.as<uint64_t>(), n_mod.as<uint64_t>(), n_idl.as<uint64_t>(), s));
+    if (pal) HIPCHK(ctx, tk::launch_pal_count(M, pal->P, pal->first, pal->plan, n_ivl.as<uint64_t>(), n_mod.as<uint64_t>(), s));
     uint64_t t_ivl = 0, t_mod = 0, t_id = 0;
     int rc;
     if ((rc = scan_to(ctx, n_ivl, o_ivl, n, &t_ivl)) || (rc = scan_to(ctx, n_mod, o_mod, n, &t_mod)) || (rc = scan_to(ctx, n_idl, o_id, n, &t_id))) return rc;
@@ -493,6 +498,7 @@ static int edit_apply(tksmseq_ctx* ctx, const tksmseq_batch* in, const uint32_t*
     HIPCHK(ctx, b->idpool.ensure(t_id + 64));
     tk::MolOut O{b->reads.as<uint32_t>(), b->intervals.as<uint32_t>(), b->mods.as<uint32_t>(), b->ids.as<uint32_t>(), b->idpool.as<uint8_t>()};
     HIPCHK(ctx, tk::launch_edit_write(M, pre, post, flip, b->literals.as<uint64_t>(), o_ivl.as<uint64_t>(), o_mod.as<uint64_t>(), o_id.as<uint64_t>(), O, s));
+    if (pal) HIPCHK(ctx, tk::launch_pal_write(M, pal->P, pal->first, pal->plan, o_ivl.as<uint64_t>(), o_mod.as<uint64_t>(), O, s));
     const uint32_t sentinel[4] = {0u, 0u, 0u, (uint32_t)t_mod};
     HIPCHK(ctx, hipMemcpyAsync(b->intervals.as<uint32_t>() + 4 * t_ivl, sentinel, 16, hipMemcpyHostToDevice, s));
     HIPCHK(ctx, hipStreamSynchronize(s));                    // (sentinel and the callers' host tables are read by now)
@@ -692,6 +698,65 @@ int tksmseq_flip(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_flip_p
     HIPCHK(ctx, d_flip.ensure(n + 16));
     HIPCHK(ctx, tk::launch_flip_plan(n, p->seed, p->flip_probability, p->first_molecule_index, d_flip.as<uint8_t>(), s));
     if ((rc = edit_apply(ctx, in, nullptr, nullptr, d_flip.as<uint8_t>(), b.get()))) return rc;
+    edit_comments(in, b.get(), p->flags);
+    return edit_finish(ctx, b, out);
+}
+
+// ---- tail-noise ------------------------------------------------------------------------------------------------------------------
+int tksmseq_append_noise(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_noise_params* p, tksmseq_batch** out) {
+    if (!ctx || !in || !p || !out) return TKSMSEQ_EINVAL;
+    *out = nullptr;
+    // what the reference leaves undefined (an empty alphabet: uniform_int_distribution(0, -1); sigma <= 0) or exits on (the name)
+    if (p->dist != TKSMSEQ_NOISE_NORMAL && p->dist != TKSMSEQ_NOISE_LOGNORMAL) { ctx->err = "Distribution not implemented!"; return TKSMSEQ_EINVAL; }
+    if (!p->alphabet || !*p->alphabet) { ctx->err = "tail-noise: the alphabet is empty"; return TKSMSEQ_EINVAL; }
+    if (!std::isfinite(p->mu) || !std::isfinite(p->sigma) || !(p->sigma > 0.0)) { ctx->err = "tail-noise: mu must be finite, sigma finite and positive"; return TKSMSEQ_EINVAL; }
+    if (std::isnan(p->error_rate)) { ctx->err = "tail-noise: the error rate is not a number"; return TKSMSEQ_EINVAL; }
+    const size_t k = strlen(p->alphabet);
+    if (k > (size_t)tk::NOISE_MAX_LEN) { ctx->err = "tail-noise: alphabets longer than 1048576 letters are not supported"; return TKSMSEQ_ELIMIT; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint64_t n = in->n_reads;
+    DevBuf d_alpha, d_plan, d_len, d_nblk, d_off, d_over, d_post;
+    for (DevBuf* pb_ : {&d_alpha, &d_plan, &d_len, &d_nblk, &d_off, &d_over, &d_post}) { pb_->pooled = true; pb_->pool_stream = s; }   // (per-call temporaries: DevCache, ctx.h)
+    HIPCHK(ctx, d_alpha.ensure(k + 16));
+    HIPCHK(ctx, hipMemcpyAsync(d_alpha.p, p->alphabet, k, hipMemcpyHostToDevice, s));
+    const tk::NoiseParams P{p->seed, p->dist == TKSMSEQ_NOISE_LOGNORMAL ? tk::NOISE_LOGNORMAL : tk::NOISE_NORMAL, p->mu, p->sigma, p->error_rate,
+                            d_alpha.as<uint8_t>(), (uint32_t)k};
+    tk::MolView M{view_of(in), in->d_dup.p ? in->d_dup.as<uint32_t>() : nullptr, in->n_intervals, in->n_mods, nullptr, n};
+    std::unique_ptr<tksmseq_batch> b(new tksmseq_batch());
+    int rc;
+    if (p->palindromic) {
+        if ((rc = copy_literals(ctx, in, b.get()))) return rc;
+        HIPCHK(ctx, d_plan.ensure(n * 16 + 16));
+        HIPCHK(ctx, tk::launch_noise_plan(M, P, p->first_molecule_index, nullptr, nullptr, nullptr, d_plan.as<uint4>(), s));
+        const PalHook pal{P, p->first_molecule_index, d_plan.as<uint4>()};
+        if ((rc = edit_apply(ctx, in, nullptr, nullptr, nullptr, b.get(), &pal))) return rc;
+    } else {
+        HIPCHK(ctx, d_len.ensure(n * 4 + 16));
+        HIPCHK(ctx, d_nblk.ensure(n * 8 + 16));
+        HIPCHK(ctx, d_over.ensure(64));
+        HIPCHK(ctx, hipMemsetAsync(d_over.p, 0xff, 8, s));
+        HIPCHK(ctx, tk::launch_noise_plan(M, P, p->first_molecule_index, d_len.as<uint32_t>(), d_nblk.as<uint64_t>(), d_over.as<unsigned long long>(), nullptr, s));
+        uint64_t n_blocks = 0;
+        if ((rc = scan_to(ctx, d_nblk, d_off, n, &n_blocks))) return rc;
+        unsigned long long over = ~0ull;
+        HIPCHK(ctx, hipMemcpy(&over, d_over.p, 8, hipMemcpyDeviceToHost));
+        if (over != ~0ull) {
+            ctx->err = "tail-noise: the noise length drawn for molecule " + molecule_id(ctx, in, over) + " is above 1048576 (not supported)";
+            return TKSMSEQ_ELIMIT;
+        }
+        if (n_blocks >= (1ull << 30)) { ctx->err = "tail-noise: more than 4 GB of noise letters in one batch (split the input)"; return TKSMSEQ_ELIMIT; }
+        uint32_t lit_base = 0; uint64_t pool_base = 0;
+        if ((rc = edit_literals(ctx, in, b.get(), n, 4 * n_blocks, lit_base, pool_base))) return rc;
+        HIPCHK(ctx, d_post.ensure(n * 4 + 16));
+        if (n) {
+            HIPCHK(ctx, hipMemsetAsync(d_post.p, 0xff, n * 4, s));                                   // EDIT_NONE
+            HIPCHK(ctx, hipMemsetAsync(b->literals.as<uint64_t>() + 2ull * lit_base, 0, n * 16, s));   // (molecules without noise: an empty entry nobody names)
+        }
+        HIPCHK(ctx, tk::launch_noise_fill(n, n_blocks, P, p->first_molecule_index, d_len.as<uint32_t>(), d_off.as<uint64_t>(), lit_base, pool_base,
+                                          b->literals.as<uint64_t>(), b->litpool.as<uint8_t>(), d_post.as<uint32_t>(), s));
+        if ((rc = edit_apply(ctx, in, nullptr, d_post.as<uint32_t>(), nullptr, b.get()))) return rc;
+    }
     edit_comments(in, b.get(), p->flags);
     return edit_finish(ctx, b, out);
 }

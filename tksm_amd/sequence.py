@@ -335,6 +335,18 @@ class Sequencer:
         self._chk(self._lib.tksmseq_flip(self._ctx, batch._h, C.byref(q), C.byref(h)))
         return Batch(self, h)
 
+    def append_noise(self, batch, dist, mu, sigma, *, palindromic=False, error_rate=0.5, alphabet="AGTC", seed=42, first=0, comments=True):
+        """NoiseAdder::operator() (src/append_noise.cpp:83-128) on the device: a noise length from dist "normal" | "lognormal" (mu, sigma)
+        per molecule; a random literal over `alphabet` behind the molecule, or (palindromic) its last segments again, strands toggled,
+        with a substitution per hairpin base at error_rate.  first: index of the batch's first molecule in the whole input."""
+        if dist not in L.NOISE_DISTS:
+            raise ValueError("Distribution not implemented!")
+        p = L.NoiseParams(seed, first, L.NOISE_DISTS[dist], 1 if palindromic else 0, float(mu), float(sigma), float(error_rate),
+                          str(alphabet).encode(), 0 if comments else L.MOL_NO_COMMENTS, 0)
+        h = C.c_void_p()
+        self._chk(self._lib.tksmseq_append_noise(self._ctx, batch._h, C.byref(p), C.byref(h)))
+        return Batch(self, h)
+
     # ---- random-wgs: whole-genome fragments made on the device
     def wgs(self, dist, a, b=0, base_count=None, depth=None, seed=42, first_candidate=0, n_candidates=1 << 20, state=None):
         """The loop of RWGS_module::run (src/random_wgs.cpp:181-207) for candidates [first_candidate, first_candidate + n_candidates)
