@@ -34,7 +34,7 @@ inline unsigned& alloc_calls() { static thread_local unsigned v = 0; return v; }
 // the temporaries of PCR / truncation.  hipFree waits until the whole device is idle -- every stream of every context: ~100 ms while
 // three batches are in flight -- and a streaming run frees (and allocates) such buffers once per batch: the workers of `tksm sequence`
 // spent a third of their cycle in tksmseq_batch_free (profiles/r04_e2e_stream.log).  A pooled buffer goes back to the cache instead
-// (after the stream that used it has drained -- the caller's duty, see DevBuf::pool_stream) and the next request of about its size takes
+// (after the stream that used it has drained -- see DevBuf::pool_stream for who drains) and the next request of about its size takes
 // it.  Bounded: beyond CACHE_LIMIT bytes per device a block is really freed; everything is freed when the last context goes.
 struct DevCache {
     static constexpr int MAX_DEV = 16;
@@ -84,9 +84,10 @@ struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
     bool owned = true;                     // false: a view of another context's buffer (tksmseq_clone), read-only
-    // pooled: allocations come from / go back to DevCache.  Whoever lets go of a pooled buffer must know that no queued work still
-    // uses it: pool_stream, if set, is drained first (the temporaries of a call); the tables of a batch are released by
-    // tksmseq_batch_free, which drains the stream of the context that ran the batch.
+    // pooled: allocations come from / go back to DevCache, and no queued work may still use a block that goes back.  With pool_stream set
+    // the buffer sees to that itself: release() drains that stream first (TmpBuf, the temporaries of a call).  The tables of a batch carry
+    // no stream; whoever deletes a batch drains the stream of the context that ran it first: tksmseq_batch_free for a finished batch,
+    // OutBatch (mdf_ops.cpp) for one still under construction when a transform returns an error.
     bool pooled = false;
     hipStream_t pool_stream = nullptr;
     int dev = -1;
@@ -131,6 +132,11 @@ struct DevBuf {
         return hipSuccess;
     }
     template <class T> T* as() const { return (T*)p; }
+};
+
+// a temporary of one call: from DevCache, and back to it once the stream the call works on has drained
+struct TmpBuf : DevBuf {
+    explicit TmpBuf(hipStream_t s) { pooled = true; pool_stream = s; }
 };
 
 struct tksmseq_batch {

@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -80,6 +81,25 @@ int common_flag(int argc, char** argv, int& i, Common& c) {
     return 0;
 }
 
+// The argument loop of every module: "--flag=value" split in two, then own(o, v) for each argument o with the one behind it (v, or null) --
+// the module's own flags, which come first (random-wgs refuses some of the common ones) -- then the common flags.  The texts are cxxopts'.
+enum { NOT_MINE = 0, TOOK_FLAG = 1, TOOK_VALUE = 2, REFUSED = -1 /* own() has said why */, NO_SUCH = -2, MALFORMED = -3 };
+template <class Own>
+bool parse_args(int argc0, char** argv0, Common& c, Own own) {
+    std::vector<std::string> arg_store; std::vector<char*> arg_ptrs;
+    tkmod::split_equals(argc0, argv0, arg_store, arg_ptrs);
+    const int argc = (int)arg_ptrs.size(); char** const argv = arg_ptrs.data();
+    for (int i = 1; i < argc; i++) {
+        int k = own(std::string(argv[i]), i + 1 < argc ? argv[i + 1] : nullptr);
+        if (k == TOOK_VALUE) i++;
+        if (k == NOT_MINE) { const int f = common_flag(argc, argv, i, c); k = f > 0 ? TOOK_FLAG : f < 0 ? MALFORMED : NO_SUCH; }   // (advances i itself)
+        if (k == MALFORMED) fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]);
+        if (k == NO_SUCH) fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]);
+        if (k < 0) return false;
+    }
+    return true;
+}
+
 bool open_log(const Common& c, const char* module, Logger& log) {
     log.module = module;
     const int lv = Logger::parse(c.verbosity);
@@ -104,13 +124,16 @@ struct OrderedOut {
     void fail() { std::lock_guard<std::mutex> l(m); failed = true; cv.notify_all(); }
 };
 
-struct Piece { uint64_t seq = 0, first = 0, begin = 0, end = 0; std::vector<char> text; };   // truncate: text + first molecule index; pcr: template slice
+// truncate: text + first molecule index; pcr: template slice; error: set by a work() that fails for a reason of its own (not the library's)
+struct Piece { uint64_t seq = 0, first = 0, begin = 0, end = 0; std::vector<char> text; std::string error; };
 
 // The common engine: `n_ctx` worker threads (two per entry of --devices), each with a context of its own; prepare() runs once per
 // context (pcr: parse the templates), pieces come from next_piece() (serialised), work() turns one into a batch, whose MDF text is
-// written in piece order.
+// written in piece order.  serial_work: work() runs under next_piece()'s lock as well (random-wgs: a batch starts where the one before it
+// ended; only the text is made in parallel).  summary(): what the closing log line says between the molecule count and the time.
 template <class Prepare, class Next, class Work>
-int run_pieces(const Common& c, Logger& log, const char* what, Prepare prepare, Next next_piece, Work work) {
+int run_pieces(const Common& c, Logger& log, const char* what, Prepare prepare, Next next_piece, Work work, bool serial_work = false,
+               std::function<std::string()> summary = nullptr) {
     OrderedOut out;
     out.f = fopen(c.output.c_str(), "wb");
     if (!out.f) { fprintf(stderr, "Error: cannot write %s\n", c.output.c_str()); return 1; }
@@ -128,12 +151,17 @@ int run_pieces(const Common& c, Logger& log, const char* what, Prepare prepare, 
         if (!prepare(ctx, &state)) set_error(tksmseq_last_error(ctx));
         while (!failed) {
             Piece p;
-            { std::lock_guard<std::mutex> l(next_m); if (failed || !next_piece(p)) break; }
             tksmseq_batch* b = nullptr;
             char* text = nullptr; uint64_t len = 0;
-            int rc = work(ctx, state, p, &b);
+            int rc;
+            {
+                std::unique_lock<std::mutex> l(next_m);
+                if (failed || !next_piece(p)) break;
+                if (!serial_work) l.unlock();
+                rc = work(ctx, state, p, &b);
+            }
             if (!rc) rc = tksmseq_batch_to_mdf_text(ctx, b, &text, &len);
-            if (rc) set_error(std::string(what) + ": " + tksmseq_last_error(ctx));
+            if (rc) set_error(std::string(what) + ": " + (p.error.empty() ? tksmseq_last_error(ctx) : p.error.c_str()));
             else {
                 uint64_t n = 0;
                 tksmseq_batch_info(b, &n, nullptr, nullptr);
@@ -153,15 +181,17 @@ int run_pieces(const Common& c, Logger& log, const char* what, Prepare prepare, 
     const bool close_ok = fclose(out.f) == 0;
     if (failed) { fprintf(stderr, "Error: %s\n", first_error.c_str()); return 1; }
     if (!close_ok || out.failed) { fprintf(stderr, "Error: cannot write %s\n", c.output.c_str()); return 1; }
-    log.log(Logger::INFO, "%s: %llu molecules written in %.2f s (%d device group(s))", what, (unsigned long long)molecules.load(),
+    log.log(Logger::INFO, "%s: %llu molecules%s written in %.2f s (%d device group(s))", what, (unsigned long long)molecules.load(), summary ? summary().c_str() : "",
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), (int)c.devices.size());
     return 0;
 }
 
-// A stream transform (truncate, polyA, tag, scb, flip): the input in pieces of whole molecules, op(ctx, batch, index of its first
-// molecule, out) on each, the outputs written in input order.
-template <class Op>
-int stream_transform(const Common& c, Logger& log, const char* what, Op op) {
+// A stream transform (truncate, polyA, tag, scb, flip, tail-noise): the input in pieces of whole molecules, fn(ctx, batch, parameters, out)
+// on each -- the parameters are p with the index of the piece's first molecule in p.*first_index (null: fn numbers nothing) -- and the
+// outputs written in input order.
+template <class P>
+int stream_transform(const Common& c, Logger& log, const char* what, const P& p, int (*fn)(tksmseq_ctx*, const tksmseq_batch*, const P*, tksmseq_batch**),
+                     uint64_t P::*first_index = &P::first_molecule_index) {
     // a reader thread of its own cuts the input into pieces of whole molecules and numbers them (input order), a few pieces ahead of the
     // workers: what the engine serialises is a pop from this queue, not the read + scan of a piece.  Its state lives on the heap and is
     // shared with the thread: after an error the module returns without waiting for a reader that may sit in a read() on a pipe nobody
@@ -207,7 +237,9 @@ int stream_transform(const Common& c, Logger& log, const char* what, Op op) {
         tksmseq_batch* in = nullptr;
         int rc = tksmseq_molecules_from_mdf_text(ctx, pc.text.data(), pc.text.size(), &in);
         if (rc) return rc;
-        rc = op(ctx, in, pc.first, out);
+        P q = p;
+        if (first_index) q.*first_index = pc.first;
+        rc = fn(ctx, in, &q, out);
         tksmseq_batch_free(ctx, in);
         return rc;
     };
@@ -222,27 +254,20 @@ int stream_transform(const Common& c, Logger& log, const char* what, Op op) {
 
 }  // namespace
 
-extern "C" int tksmseq_pcr_main(int argc0, char** argv0) {
-    std::vector<std::string> arg_store; std::vector<char*> arg_ptrs;
-    tkmod::split_equals(argc0, argv0, arg_store, arg_ptrs);
-    const int argc = (int)arg_ptrs.size(); char** const argv = arg_ptrs.data();
+extern "C" int tksmseq_pcr_main(int argc, char** argv) {
     Common c;
     bool have_count = false, have_cycles = false, have_er = false, have_ef = false;
     std::string preset;
     tksmseq_pcr_params p{};
-    for (int i = 1; i < argc; i++) {
-        const int k = common_flag(argc, argv, i, c);
-        if (k < 0) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; }
-        if (k) continue;
-        const std::string o = argv[i];
-        const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
-        if (o == "--molecule-count" && v) { p.target_count = strtoull(v, nullptr, 10); have_count = true; i++; }
-        else if (o == "--cycles" && v) { p.cycles = atoi(v); have_cycles = true; i++; }
-        else if (o == "--error-rate" && v) { p.error_rate = atof(v); have_er = true; i++; }
-        else if (o == "--efficiency" && v) { p.efficiency = atof(v); have_ef = true; i++; }
-        else if ((o == "-x" || o == "--preset") && v) { preset = v; i++; }
-        else { fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1; }
-    }
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            if (o == "--molecule-count" && v) { p.target_count = strtoull(v, nullptr, 10); have_count = true; }
+            else if (o == "--cycles" && v) { p.cycles = atoi(v); have_cycles = true; }
+            else if (o == "--error-rate" && v) { p.error_rate = atof(v); have_er = true; }
+            else if (o == "--efficiency" && v) { p.efficiency = atof(v); have_ef = true; }
+            else if ((o == "-x" || o == "--preset") && v) preset = v;
+            else return NOT_MINE;
+            return TOOK_VALUE;
+        })) return 1;
     if (c.help) { printf("PCR amplification module\nusage: pcr -i INPUT -o OUTPUT --molecule-count N --cycles C [-x PRESET | --error-rate E --efficiency F] [-s SEED]\n"
                          "           [--devices D[,D...]] [--slice-molecules N] [--verbosity L] [--log-file F]\n"); return 0; }
     int missing = 0;
@@ -309,28 +334,23 @@ extern "C" int tksmseq_pcr_main(int argc0, char** argv0) {
     return run_pieces(c, log, "PCR", prepare, next_piece, work);
 }
 
-extern "C" int tksmseq_truncate_main(int argc0, char** argv0) {
-    std::vector<std::string> arg_store; std::vector<char*> arg_ptrs;
-    tkmod::split_equals(argc0, argv0, arg_store, arg_ptrs);
-    const int argc = (int)arg_ptrs.size(); char** const argv = arg_ptrs.data();
+extern "C" int tksmseq_truncate_main(int argc, char** argv) {
     Common c;
     tksmseq_trc_params p{};
     std::string kde;
     int n_dist = 0;
     auto two = [](const char* v, double& a, double& b) { char* e = nullptr; a = strtod(v, &e); if (!e || *e != ',') return false; b = strtod(e + 1, &e); return e && !*e; };
-    for (int i = 1; i < argc; i++) {
-        const int k = common_flag(argc, argv, i, c);
-        if (k < 0) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; }
-        if (k) continue;
-        const std::string o = argv[i];
-        const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
-        if (o == "--kde-model" && v) { kde = v; n_dist++; i++; }
-        else if (o == "--always-end") p.always_end = 1;
-        else if (o == "--kde-models-length") p.kde_models_length = 1;
-        else if (o == "--normal" && v) { if (!two(v, p.mu, p.sigma)) { fprintf(stderr, "--normal needs mu,sigma\n"); return 1; } p.mode = TKSMSEQ_TRC_NORMAL; n_dist++; i++; }
-        else if (o == "--lognormal" && v) { if (!two(v, p.mu, p.sigma)) { fprintf(stderr, "--lognormal needs mu,sigma\n"); return 1; } p.mode = TKSMSEQ_TRC_LOGNORMAL; n_dist++; i++; }
-        else { fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1; }
-    }
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            if (o == "--always-end") { p.always_end = 1; return TOOK_FLAG; }
+            if (o == "--kde-models-length") { p.kde_models_length = 1; return TOOK_FLAG; }
+            if (o == "--kde-model" && v) kde = v;
+            else if ((o == "--normal" || o == "--lognormal") && v) {
+                if (!two(v, p.mu, p.sigma)) { fprintf(stderr, "%s needs mu,sigma\n", o.c_str()); return REFUSED; }
+                p.mode = o == "--normal" ? TKSMSEQ_TRC_NORMAL : TKSMSEQ_TRC_LOGNORMAL;
+            } else return NOT_MINE;
+            n_dist++;
+            return TOOK_VALUE;
+        })) return 1;
     if (c.help) { printf("Truncate module\nusage: truncate -i INPUT -o OUTPUT (--kde-model M.json [--always-end] [--kde-models-length] | --normal MU,SIGMA | --lognormal MU,SIGMA) [-s SEED]\n"
                          "                [--devices D[,D...]] [--batch-bytes B] [--verbosity L] [--log-file F]\n"); return 0; }
     int missing = 0;
@@ -343,11 +363,7 @@ extern "C" int tksmseq_truncate_main(int argc0, char** argv0) {
     if (!open_log(c, "truncate", log)) return 1;
     if (!kde.empty()) { p.mode = TKSMSEQ_TRC_KDE; p.kde_model_path = kde.c_str(); }
     p.seed = (uint64_t)c.seed;
-    return stream_transform(c, log, "truncate", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, uint64_t first, tksmseq_batch** out) {
-        tksmseq_trc_params q = p;
-        q.first_molecule_index = first;
-        return tksmseq_truncate(ctx, in, &q, out);
-    });
+    return stream_transform(c, log, "truncate", p, tksmseq_truncate);
 }
 
 // comma-separated doubles (cxxopts' vector<double>); false on a malformed list
@@ -364,10 +380,7 @@ static bool parse_doubles(const char* v, std::vector<double>& out) {
     }
 }
 
-extern "C" int tksmseq_polya_main(int argc0, char** argv0) {
-    std::vector<std::string> arg_store; std::vector<char*> arg_ptrs;
-    tkmod::split_equals(argc0, argv0, arg_store, arg_ptrs);
-    const int argc = (int)arg_ptrs.size(); char** const argv = arg_ptrs.data();
+extern "C" int tksmseq_polya_main(int argc, char** argv) {
     Common c;
     tksmseq_polya_params p{};
     p.min_length = 0; p.max_length = 5000;
@@ -375,19 +388,15 @@ extern "C" int tksmseq_polya_main(int argc0, char** argv0) {
     static const char* titles[4] = {"Gamma", "Poisson", "Weibull", "Normal"};
     std::vector<double> vals[4];
     int count[4] = {0, 0, 0, 0};
-    for (int i = 1; i < argc; i++) {
-        const int k = common_flag(argc, argv, i, c);
-        if (k < 0) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; }
-        if (k) continue;
-        const std::string o = argv[i];
-        const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
-        int d = -1;
-        for (int q = 0; q < 4; q++) if (o == std::string("--") + names[q]) d = q;
-        if (d >= 0 && v) { if (!parse_doubles(v, vals[d])) { fprintf(stderr, "Option '%s' needs a comma-separated list of numbers\n", o.c_str()); return 1; } count[d]++; i++; }
-        else if (o == "--min-length" && v) { p.min_length = atoi(v); i++; }
-        else if (o == "--max-length" && v) { p.max_length = atoi(v); i++; }
-        else { fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1; }
-    }
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            int d = -1;
+            for (int q = 0; q < 4; q++) if (o == std::string("--") + names[q]) d = q;
+            if (d >= 0 && v) { if (!parse_doubles(v, vals[d])) { fprintf(stderr, "Option '%s' needs a comma-separated list of numbers\n", o.c_str()); return REFUSED; } count[d]++; }
+            else if (o == "--min-length" && v) p.min_length = atoi(v);
+            else if (o == "--max-length" && v) p.max_length = atoi(v);
+            else return NOT_MINE;
+            return TOOK_VALUE;
+        })) return 1;
     if (c.help) { printf("polyA module: adds polyA tails to molecules with given size distribution\n"
                          "usage: polyA -i INPUT -o OUTPUT (--gamma A,B | --poisson L | --weibull A,B | --normal MU,SIGMA) [--min-length N] [--max-length N]\n"
                          "             [-s SEED] [--devices D[,D...]] [--batch-bytes B] [--verbosity L] [--log-file F]\n"); return 0; }
@@ -419,29 +428,18 @@ extern "C" int tksmseq_polya_main(int argc0, char** argv0) {
     Logger log;
     if (!open_log(c, "polyA", log)) return 1;
     p.seed = (uint64_t)c.seed;
-    return stream_transform(c, log, "polyA", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, uint64_t first, tksmseq_batch** out) {
-        tksmseq_polya_params q = p;
-        q.first_molecule_index = first;
-        return tksmseq_polya(ctx, in, &q, out);
-    });
+    return stream_transform(c, log, "polyA", p, tksmseq_polya);
 }
 
-extern "C" int tksmseq_tag_main(int argc0, char** argv0) {
-    std::vector<std::string> arg_store; std::vector<char*> arg_ptrs;
-    tkmod::split_equals(argc0, argv0, arg_store, arg_ptrs);
-    const int argc = (int)arg_ptrs.size(); char** const argv = arg_ptrs.data();
+extern "C" int tksmseq_tag_main(int argc, char** argv) {
     Common c;
     std::string fmt[2];
-    for (int i = 1; i < argc; i++) {
-        const int k = common_flag(argc, argv, i, c);
-        if (k < 0) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; }
-        if (k) continue;
-        const std::string o = argv[i];
-        const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
-        if ((o == "-5" || o == "--format5") && v) { fmt[0] = v; i++; }
-        else if ((o == "-3" || o == "--format3") && v) { fmt[1] = v; i++; }
-        else { fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1; }
-    }
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            if ((o == "-5" || o == "--format5") && v) fmt[0] = v;
+            else if ((o == "-3" || o == "--format3") && v) fmt[1] = v;
+            else return NOT_MINE;
+            return TOOK_VALUE;
+        })) return 1;
     if (c.help) { printf("TAGging module\nusage: tag -i INPUT -o OUTPUT [-5 FORMAT5] [-3 FORMAT3] [-s SEED]\n"
                          "           [--devices D[,D...]] [--batch-bytes B] [--verbosity L] [--log-file F]\n"
                          "FORMAT: IUPAC letters (ACGTU RYKMSW BDHV N), or a number of N's\n"); return 0; }
@@ -462,30 +460,20 @@ extern "C" int tksmseq_tag_main(int argc0, char** argv0) {
     if (!open_log(c, "tag", log)) return 1;
     tksmseq_tag_params p{};
     p.seed = (uint64_t)c.seed; p.format5 = fmt[0].c_str(); p.format3 = fmt[1].c_str();
-    return stream_transform(c, log, "tag", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, uint64_t first, tksmseq_batch** out) {
-        tksmseq_tag_params q = p;
-        q.first_molecule_index = first;
-        return tksmseq_tag(ctx, in, &q, out);
-    });
+    return stream_transform(c, log, "tag", p, tksmseq_tag);
 }
 
-extern "C" int tksmseq_scb_main(int argc0, char** argv0) {
-    std::vector<std::string> arg_store; std::vector<char*> arg_ptrs;
-    tkmod::split_equals(argc0, argv0, arg_store, arg_ptrs);
-    const int argc = (int)arg_ptrs.size(); char** const argv = arg_ptrs.data();
+// cxxopts' boolean: --flag, or --flag=true|false
+static int bool_flag(const char* v, int32_t& value) {
+    const bool given = v && (!strcmp(v, "true") || !strcmp(v, "false"));
+    value = given ? !strcmp(v, "true") : 1;
+    return given ? TOOK_VALUE : TOOK_FLAG;
+}
+
+extern "C" int tksmseq_scb_main(int argc, char** argv) {
     Common c;
     tksmseq_scb_params p{};
-    for (int i = 1; i < argc; i++) {
-        const int k = common_flag(argc, argv, i, c);
-        if (k < 0) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; }
-        if (k) continue;
-        const std::string o = argv[i];
-        if (o == "--keep-meta-barcodes") {
-            p.keep_meta_barcodes = 1;
-            // (cxxopts' boolean: --keep-meta-barcodes=true|false)
-            if (i + 1 < argc && (!strcmp(argv[i + 1], "true") || !strcmp(argv[i + 1], "false"))) p.keep_meta_barcodes = !strcmp(argv[++i], "true");
-        } else { fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1; }
-    }
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int { return o == "--keep-meta-barcodes" ? bool_flag(v, p.keep_meta_barcodes) : NOT_MINE; })) return 1;
     if (c.help) { printf("Single cell barcode module\nusage: scb -i INPUT -o OUTPUT [--keep-meta-barcodes]\n"
                          "           [--devices D[,D...]] [--batch-bytes B] [--verbosity L] [--log-file F]\n"); return 0; }
     int missing = 0;
@@ -494,27 +482,18 @@ extern "C" int tksmseq_scb_main(int argc0, char** argv0) {
     if (missing) return 1;
     Logger log;
     if (!open_log(c, "scb", log)) return 1;
-    return stream_transform(c, log, "scb", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, uint64_t, tksmseq_batch** out) {
-        return tksmseq_scb(ctx, in, &p, out);
-    });
+    return stream_transform<tksmseq_scb_params>(c, log, "scb", p, tksmseq_scb, nullptr);      // (the barcodes come from the comments: nothing is numbered)
 }
 
-extern "C" int tksmseq_flip_main(int argc0, char** argv0) {
-    std::vector<std::string> arg_store; std::vector<char*> arg_ptrs;
-    tkmod::split_equals(argc0, argv0, arg_store, arg_ptrs);
-    const int argc = (int)arg_ptrs.size(); char** const argv = arg_ptrs.data();
+extern "C" int tksmseq_flip_main(int argc, char** argv) {
     Common c;
     tksmseq_flip_params p{};
     bool have_p = false;
-    for (int i = 1; i < argc; i++) {
-        const int k = common_flag(argc, argv, i, c);
-        if (k < 0) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; }
-        if (k) continue;
-        const std::string o = argv[i];
-        const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
-        if ((o == "-p" || o == "--flip-probability") && v) { p.flip_probability = atof(v); have_p = true; i++; }
-        else { fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1; }
-    }
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            if ((o != "-p" && o != "--flip-probability") || !v) return NOT_MINE;
+            p.flip_probability = atof(v); have_p = true;
+            return TOOK_VALUE;
+        })) return 1;
     if (c.help) { printf("Flip module\nusage: flip -i INPUT -o OUTPUT -p PROBABILITY [-s SEED]\n"
                          "            [--devices D[,D...]] [--batch-bytes B] [--verbosity L] [--log-file F]\n"); return 0; }
     int missing = 0;
@@ -527,37 +506,23 @@ extern "C" int tksmseq_flip_main(int argc0, char** argv0) {
     Logger log;
     if (!open_log(c, "flip", log)) return 1;
     p.seed = (uint64_t)c.seed;
-    return stream_transform(c, log, "flip", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, uint64_t first, tksmseq_batch** out) {
-        tksmseq_flip_params q = p;
-        q.first_molecule_index = first;
-        return tksmseq_flip(ctx, in, &q, out);
-    });
+    return stream_transform(c, log, "flip", p, tksmseq_flip);
 }
 
-extern "C" int tksmseq_tail_noise_main(int argc0, char** argv0) {
-    std::vector<std::string> arg_store; std::vector<char*> arg_ptrs;
-    tkmod::split_equals(argc0, argv0, arg_store, arg_ptrs);
-    const int argc = (int)arg_ptrs.size(); char** const argv = arg_ptrs.data();
+extern "C" int tksmseq_tail_noise_main(int argc, char** argv) {
     Common c;
     tksmseq_noise_params p{};
     p.error_rate = 0.5;
     std::string alphabet = "AGTC", dist_text;
     bool have_dist = false;
-    for (int i = 1; i < argc; i++) {
-        const int k = common_flag(argc, argv, i, c);
-        if (k < 0) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; }
-        if (k) continue;
-        const std::string o = argv[i];
-        const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
-        if (o == "--length-dist" && v) { dist_text = v; have_dist = true; i++; }
-        else if (o == "--alphabet" && v) { alphabet = v; i++; }
-        else if (o == "--error-rate" && v) { p.error_rate = atof(v); i++; }
-        else if (o == "--palindromic") {
-            p.palindromic = 1;
-            // (cxxopts' boolean: --palindromic=true|false)
-            if (v && (!strcmp(v, "true") || !strcmp(v, "false"))) p.palindromic = !strcmp(argv[++i], "true");
-        } else { fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1; }
-    }
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            if (o == "--palindromic") return bool_flag(v, p.palindromic);
+            if (o == "--length-dist" && v) { dist_text = v; have_dist = true; }
+            else if (o == "--alphabet" && v) alphabet = v;
+            else if (o == "--error-rate" && v) p.error_rate = atof(v);
+            else return NOT_MINE;
+            return TOOK_VALUE;
+        })) return 1;
     static const char* help =
         "Append Noise module\nusage: tail-noise -i INPUT -o OUTPUT --length-dist NAME,MU,SIGMA [--alphabet AGTC] [--palindromic] [--error-rate 0.5] [-s SEED]\n"
         "                  [--devices D[,D...]] [--batch-bytes B] [--verbosity L] [--log-file F]\n"
@@ -589,11 +554,7 @@ extern "C" int tksmseq_tail_noise_main(int argc0, char** argv0) {
     Logger log;
     if (!open_log(c, "tail-noise", log)) return 1;
     p.seed = (uint64_t)c.seed; p.alphabet = alphabet.c_str();
-    return stream_transform(c, log, "tail-noise", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, uint64_t first, tksmseq_batch** out) {
-        tksmseq_noise_params q = p;
-        q.first_molecule_index = first;
-        return tksmseq_append_noise(ctx, in, &q, out);
-    });
+    return stream_transform(c, log, "tail-noise", p, tksmseq_append_noise);
 }
 
 // The contig table of random-wgs: names and lengths from <reference>.fai (src/random_wgs.cpp:139-161: the first two columns), or, when
@@ -601,12 +562,8 @@ extern "C" int tksmseq_tail_noise_main(int argc0, char** argv0) {
 static bool wgs_contig_table(const std::string& reference, std::vector<std::pair<std::string, uint64_t>>& table, std::string& err) {
     table.clear();
     const std::string fai = reference + ".fai";
-    if (FILE* f = fopen(fai.c_str(), "rb")) {
-        std::string text;
-        char buf[1 << 16];
-        size_t n;
-        while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
-        fclose(f);
+    std::string text;
+    if (read_file(fai, text)) {
         size_t a = 0;
         while (a < text.size()) {
             size_t e = text.find('\n', a);
@@ -634,30 +591,23 @@ static bool wgs_contig_table(const std::string& reference, std::vector<std::pair
     return true;
 }
 
-extern "C" int tksmseq_random_wgs_main(int argc0, char** argv0) {
-    std::vector<std::string> arg_store; std::vector<char*> arg_ptrs;
-    tkmod::split_equals(argc0, argv0, arg_store, arg_ptrs);
-    const int argc = (int)arg_ptrs.size(); char** const argv = arg_ptrs.data();
+extern "C" int tksmseq_random_wgs_main(int argc, char** argv) {
     Common c;
     std::string reference, dist_text;
     bool have_bc = false, have_depth = false, have_dist = false;
     long long base_count = 0; double depth = 0.0;
     uint64_t batch_molecules = 2000000;
-    for (int i = 1; i < argc; i++) {
-        const std::string o = argv[i];
-        const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
-        // (this module's -r and --batch-molecules first: the common flags know -i and --batch-bytes, which it does not have)
-        if ((o == "-r" || o == "--reference") && v) { reference = v; i++; continue; }
-        if (o == "--frag-len-dist" && v) { dist_text = v; have_dist = true; i++; continue; }
-        if (o == "--base-count" && v) { base_count = atoll(v); have_bc = true; i++; continue; }
-        if (o == "--depth" && v) { depth = atof(v); have_depth = true; i++; continue; }
-        if (o == "--batch-molecules" && v) { batch_molecules = strtoull(v, nullptr, 10); if (batch_molecules < 1 || batch_molecules > (1ull << 28)) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; } i++; continue; }
-        if (o == "-i" || o == "--input" || o == "--batch-bytes" || o == "--slice-molecules") { fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1; }
-        const int k = common_flag(argc, argv, i, c);
-        if (k < 0) { fprintf(stderr, "Option '%s' is missing an argument or has a malformed one\n", argv[i]); return 1; }
-        if (k) continue;
-        fprintf(stderr, "Option '%s' does not exist or is missing an argument\n", argv[i]); return 1;
-    }
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            // (the common flags know -i, --batch-bytes and --slice-molecules, which this module does not have)
+            if (o == "-i" || o == "--input" || o == "--batch-bytes" || o == "--slice-molecules") return NO_SUCH;
+            if ((o == "-r" || o == "--reference") && v) reference = v;
+            else if (o == "--frag-len-dist" && v) { dist_text = v; have_dist = true; }
+            else if (o == "--base-count" && v) { base_count = atoll(v); have_bc = true; }
+            else if (o == "--depth" && v) { depth = atof(v); have_depth = true; }
+            else if (o == "--batch-molecules" && v) { batch_molecules = strtoull(v, nullptr, 10); if (batch_molecules < 1 || batch_molecules > (1ull << 28)) return MALFORMED; }
+            else return NOT_MINE;
+            return TOOK_VALUE;
+        })) return 1;
     static const char* help =
         "Random whole-genome fragments module\nusage: random-wgs -r REFERENCE --frag-len-dist \"NAME A [B]\" -o OUTPUT (--base-count N | --depth D) [-s SEED]\n"
         "                  [--devices D[,D...]] [--batch-molecules M] [--verbosity L] [--log-file F]\n"
@@ -696,61 +646,32 @@ extern "C" int tksmseq_random_wgs_main(int argc0, char** argv0) {
     if (!ref_length) { fprintf(stderr, "Error: the reference has no contigs (or none with a base)\n"); return 1; }
     p.seed = (uint64_t)c.seed;
     p.base_count = have_bc ? (int64_t)base_count : (int64_t)(depth * (double)ref_length);      // (:169-176)
-
-    OrderedOut out;
-    out.f = fopen(c.output.c_str(), "wb");
-    if (!out.f) { fprintf(stderr, "Error: cannot write %s\n", c.output.c_str()); return 1; }
-    const int per_device = 2, n_ctx = (int)c.devices.size() * per_device;
-    std::mutex err_m, gen_m; std::string first_error; std::atomic<bool> failed{false};
-    auto set_error = [&](const std::string& e) { std::lock_guard<std::mutex> l(err_m); if (!failed.exchange(true)) first_error = e; out.fail(); };
-    // the only state that is serial across batches (guarded by gen_m): next candidate, molecules and bases so far, next piece number
+    // the only state that is serial across batches: next candidate, molecules and bases so far, next piece number.  A batch is made under
+    // the engine's lock (serial_work): what it carries over is known once the batch before it has been made (milliseconds)
     tksmseq_wgs_progress st{}; uint64_t next_seq = 0; bool done = p.base_count <= 0;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto worker = [&](int wi) {
-        tksmseq_ctx* ctx = nullptr;
-        if (tksmseq_create(c.devices[(size_t)(wi / per_device)], &ctx)) { set_error(tksmseq_last_error(nullptr)); return; }
-        tksmseq_set_host_threads(ctx, (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency() / (unsigned)std::max(1, n_ctx / 2))));
+    auto prepare = [&](tksmseq_ctx* ctx, void**) -> bool {
         for (auto& t : table)
-            if (tksmseq_reference_declare_contig(ctx, t.first.c_str(), t.second)) { set_error(tksmseq_last_error(ctx)); break; }
-        while (!failed) {
-            tksmseq_batch* b = nullptr;
-            uint64_t seq = 0, n = 0;
-            {
-                // made under the lock: a batch's carried state is known once the batch before it has been made (milliseconds; the text is
-                // formatted outside)
-                std::lock_guard<std::mutex> l(gen_m);
-                if (done || failed) break;
-                tksmseq_wgs_params q = p;
-                q.first_candidate = st.next_candidate; q.n_candidates = batch_molecules; q.molecules_before = st.molecules; q.bases_before = st.bases;
-                tksmseq_wgs_progress pr{};
-                if (tksmseq_wgs(ctx, &q, &b, &pr)) { set_error(std::string("random-wgs: ") + tksmseq_last_error(ctx)); break; }
-                tksmseq_batch_info(b, &n, nullptr, nullptr);
-                if (!n && !pr.reached) {
-                    tksmseq_batch_free(ctx, b);
-                    set_error("random-wgs: none of " + std::to_string(batch_molecules) + " candidate fragments has a base (fragment length distribution '" + dist_text + "'): giving up");
-                    break;
-                }
-                st = pr; seq = next_seq++;
-                if (pr.reached) done = true;
-            }
-            char* text = nullptr; uint64_t len = 0;
-            if (tksmseq_batch_to_mdf_text(ctx, b, &text, &len)) set_error(std::string("random-wgs: ") + tksmseq_last_error(ctx));
-            else {
-                log.log(Logger::DEBUG, "piece %llu: %llu molecules, %.1f MB of text (context %d)", (unsigned long long)seq, (unsigned long long)n, len / 1e6, wi);
-                if (!out.put(seq, text, len) && !failed) set_error("cannot write " + c.output);
-            }
-            tksmseq_text_free(text);
-            tksmseq_batch_free(ctx, b);
-        }
-        tksmseq_destroy(ctx);
+            if (tksmseq_reference_declare_contig(ctx, t.first.c_str(), t.second)) return false;
+        return true;
     };
-    std::vector<std::thread> th;
-    for (int w = 0; w < n_ctx; w++) th.emplace_back(worker, w);
-    for (auto& t : th) t.join();
-    const bool close_ok = fclose(out.f) == 0;
-    if (failed) { fprintf(stderr, "Error: %s\n", first_error.c_str()); return 1; }
-    if (!close_ok || out.failed) { fprintf(stderr, "Error: cannot write %s\n", c.output.c_str()); return 1; }
-    log.log(Logger::INFO, "random-wgs: %llu molecules, %llu bases from %llu candidates written in %.2f s (%d device group(s))", (unsigned long long)st.molecules,
-            (unsigned long long)st.bases, (unsigned long long)st.next_candidate, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), (int)c.devices.size());
-    return 0;
+    auto next_piece = [&](Piece& pc) -> bool { pc.seq = next_seq; return !done; };
+    auto work = [&](tksmseq_ctx* ctx, void*, Piece& pc, tksmseq_batch** out) -> int {
+        tksmseq_wgs_params q = p;
+        q.first_candidate = st.next_candidate; q.n_candidates = batch_molecules; q.molecules_before = st.molecules; q.bases_before = st.bases;
+        tksmseq_wgs_progress pr{};
+        const int rc = tksmseq_wgs(ctx, &q, out, &pr);
+        if (rc) return rc;
+        uint64_t n = 0;
+        tksmseq_batch_info(*out, &n, nullptr, nullptr);
+        if (!n && !pr.reached) {
+            pc.error = "none of " + std::to_string(batch_molecules) + " candidate fragments has a base (fragment length distribution '" + dist_text + "'): giving up";
+            return 1;
+        }
+        st = pr; next_seq++;
+        if (pr.reached) done = true;
+        return 0;
+    };
+    return run_pieces(c, log, "random-wgs", prepare, next_piece, work, true, [&] {
+        return ", " + std::to_string(st.bases) + " bases from " + std::to_string(st.next_candidate) + " candidates";
+    });
 }

@@ -37,22 +37,24 @@ tk::BatchView view_of(const tksmseq_batch* b) {
                          b->litpool.as<uint8_t>(), b->ids.as<uint32_t>(), b->idpool.as<uint8_t>(), b->n_reads, (uint32_t)b->n_literals};
 }
 
-int scan_to(tksmseq_ctx* ctx, DevBuf& in, DevBuf& out, uint64_t n, uint64_t* total) {
+// every (unrolled) molecule of a batch, or the n_kept of them that `keep` lists (a device array)
+tk::MolView mol_view(const tksmseq_batch* in, const uint32_t* keep, uint64_t n_kept) {
+    return tk::MolView{view_of(in), in->d_dup.p ? in->d_dup.as<uint32_t>() : nullptr, in->n_intervals, in->n_mods, keep, n_kept};
+}
+tk::MolView mol_view(const tksmseq_batch* in) { return mol_view(in, nullptr, in->n_reads); }
+
+// exclusive scan of in[0, n) into out[0, n], queued; the total is out[n], *total once the stream has drained
+int scan_async(tksmseq_ctx* ctx, DevBuf& in, DevBuf& out, uint64_t n, uint64_t* total) {
     HIPCHK(ctx, out.ensure((n + 1) * 8 + 16));
     HIPCHK(ctx, ctx->w_scan.ensure(tk::scan_temp_bytes(n) + 64));
     HIPCHK(ctx, tk::launch_scan(in.as<uint64_t>(), out.as<uint64_t>(), n, ctx->w_scan.p, ctx->w_scan.cap, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(total, out.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return TKSMSEQ_OK;
 }
-
-// literals (contigs whose name is their sequence) are shared by reference: the output batch gets its own copy of the tables
-int copy_literals(tksmseq_ctx* ctx, const tksmseq_batch* in, tksmseq_batch* out) {
-    out->n_literals = in->n_literals;
-    HIPCHK(ctx, out->literals.ensure(in->n_literals * 16 + 64));
-    HIPCHK(ctx, out->litpool.ensure(in->litpool.cap + 64));
-    if (in->n_literals) HIPCHK(ctx, hipMemcpyAsync(out->literals.p, in->literals.p, in->n_literals * 16, hipMemcpyDeviceToDevice, ctx->stream));
-    if (in->litpool.cap) HIPCHK(ctx, hipMemcpyAsync(out->litpool.p, in->litpool.p, in->litpool.cap, hipMemcpyDeviceToDevice, ctx->stream));
+int scan_to(tksmseq_ctx* ctx, DevBuf& in, DevBuf& out, uint64_t n, uint64_t* total) {
+    const int rc = scan_async(ctx, in, out, n, total);
+    if (rc) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return TKSMSEQ_OK;
 }
 
@@ -128,6 +130,114 @@ std::string fmt_double(double v) {
     r = std::to_chars(buf, buf + sizeof buf, v, std::chars_format::fixed);
     return std::string(buf, r.ptr);
 }
+
+// one more header comment behind b's: its (offset, length) entry and its bytes.  who / hint: for the message of the 4 GB limit
+int append_comment(tksmseq_ctx* ctx, tksmseq_batch* b, const std::string& c, const char* who, const char* hint = "split the input") {
+    if (b->h_comment_pool.size() + c.size() >= 0xffffffffull) {
+        ctx->err = std::string(who) + ": more than 4 GB of header comments in one batch (" + hint + ")";
+        return TKSMSEQ_ELIMIT;
+    }
+    b->h_comments.push_back((uint32_t)b->h_comment_pool.size()); b->h_comments.push_back((uint32_t)c.size());
+    b->h_comment_pool.insert(b->h_comment_pool.end(), c.begin(), c.end());
+    return TKSMSEQ_OK;
+}
+
+// Host copies of a batch's device tables.  fetch() copies the chosen groups and returns when the context's stream has drained (so it
+// covers copies the caller has queued before it, too).
+struct HostTables {
+    enum { SEGMENTS = 1, MODS = 2, IDS = 4 };      // reads, intervals and literals | substitutions | ids and their pool
+    std::vector<uint32_t> reads, ivs, mods, ids;
+    std::vector<uint64_t> lits;
+    std::vector<char> lpool, idpool;
+    int fetch(tksmseq_ctx* ctx, const tksmseq_batch* b, int what) {
+        hipError_t e = hipSuccess;
+        auto get = [&](auto& v, const DevBuf& d, size_t count) {
+            v.resize(count);
+            if (count && e == hipSuccess) e = hipMemcpyAsync(v.data(), d.p, count * sizeof v[0], hipMemcpyDeviceToHost, ctx->stream);
+        };
+        if (what & SEGMENTS) { get(reads, b->reads, 2 * b->n_reads); get(ivs, b->intervals, 4 * (b->n_intervals + 1)); get(lits, b->literals, 2 * b->n_literals); get(lpool, b->litpool, b->litpool.cap); }
+        if (what & MODS) get(mods, b->mods, 2 * b->n_mods);
+        if (what & IDS) { get(ids, b->ids, 2 * b->n_reads); get(idpool, b->idpool, b->idpool.cap); }
+        const hipError_t drained = hipStreamSynchronize(ctx->stream);      // (after a failed copy as well: the ones before it write into the vectors)
+        if (e == hipSuccess) e = drained;
+        if (e != hipSuccess) { ctx->err = std::string("copying a batch's tables to the host: ") + hipGetErrorString(e); return TKSMSEQ_EDEVICE; }
+        return TKSMSEQ_OK;
+    }
+    // an interval's contig as the MDF text names it: the literal itself, or the reference's name
+    void append_contig(const tksmseq_ctx* ctx, uint32_t c, std::string& out) const {
+        if (c >> 31) { const size_t li = c & 0x7fffffffu; out.append(lpool.data() + lits[2 * li], (size_t)lits[2 * li + 1]); }
+        else out += ctx->contig_names[c];
+    }
+};
+
+// ---- the output batch of a transform ---------------------------------------------------------------------------------------------
+// What pcr, truncate, the segment edits and random-wgs share: scan the per-molecule counts, check the size limits, allocate the five
+// tables, and -- after the caller's write kernels -- write the sentinel interval, finalize and hand the batch over.
+// The rule for device memory: nothing goes back to DevCache while work queued on the context's stream may still touch it.  A TmpBuf
+// drains the stream itself when it lets go; the tables of the batch under construction carry no stream, so the destructor here drains
+// before they go, on every exit that has not handed the batch over.  Neither depends on the order in which a caller declares them.
+struct OutBatch {
+    tksmseq_ctx* ctx;
+    std::unique_ptr<tksmseq_batch> b{new tksmseq_batch()};
+    TmpBuf o_ivl, o_mod, o_id;                      // where every molecule's intervals, substitutions and id bytes start (scan())
+    uint64_t t_ivl = 0, t_mod = 0, t_id = 0;        // ... and how many there are in all
+    uint32_t sentinel[4] = {0u, 0u, 0u, 0u};        // (lives as long as its queued copy may)
+    explicit OutBatch(tksmseq_ctx* c) : ctx(c), o_ivl(c->stream), o_mod(c->stream), o_id(c->stream) {}
+    ~OutBatch() { if (b) (void)hipStreamSynchronize(ctx->stream); }
+    tksmseq_batch* get() const { return b.get(); }
+    tksmseq_batch* operator->() const { return b.get(); }
+    tk::MolOut tables() const { return tk::MolOut{b->reads.as<uint32_t>(), b->intervals.as<uint32_t>(), b->mods.as<uint32_t>(), b->ids.as<uint32_t>(), b->idpool.as<uint8_t>()}; }
+
+    // Literals (contigs whose name is their sequence) are shared by reference, so the batch gets its own table: the entries and the pool of
+    // `in` (the pool copied whole, its capacity; in null: none), then room for n_new entries and new_bytes pool bytes behind them, which
+    // start at lit_base / pool_base.
+    uint32_t lit_base = 0; uint64_t pool_base = 0;
+    int literals(const tksmseq_batch* in, uint64_t n_new = 0, uint64_t new_bytes = 0) {
+        lit_base = in ? (uint32_t)in->n_literals : 0u; pool_base = in ? in->litpool.cap : 0;
+        if (lit_base + n_new >= 0x80000000ull) { ctx->err = "more than 2^31 literals in one batch (split the input)"; return TKSMSEQ_ELIMIT; }
+        b->n_literals = lit_base + n_new;
+        HIPCHK(ctx, b->literals.ensure(b->n_literals * 16 + 64));
+        HIPCHK(ctx, b->litpool.ensure(pool_base + new_bytes + 64));
+        if (lit_base) HIPCHK(ctx, hipMemcpyAsync(b->literals.p, in->literals.p, lit_base * 16ull, hipMemcpyDeviceToDevice, ctx->stream));
+        if (pool_base) HIPCHK(ctx, hipMemcpyAsync(b->litpool.p, in->litpool.p, pool_base, hipMemcpyDeviceToDevice, ctx->stream));
+        return TKSMSEQ_OK;
+    }
+    // the three counts of each of n molecules (device arrays) -> offsets and totals; one synchronisation
+    int scan(DevBuf& n_ivl, DevBuf& n_mod, DevBuf& n_idl, uint64_t n) {
+        int rc;
+        if ((rc = scan_async(ctx, n_ivl, o_ivl, n, &t_ivl)) || (rc = scan_async(ctx, n_mod, o_mod, n, &t_mod)) || (rc = scan_async(ctx, n_idl, o_id, n, &t_id))) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return TKSMSEQ_OK;
+    }
+    // The size limits of a batch: read, interval and id offsets are 32-bit, and an interval keeps its strand in bit 31 of its substitution
+    // index.  who: the caller's prefix of the message.
+    int limits(uint64_t n, const char* who, const char* hint) {
+        if (n >= 0xffffffffull) { ctx->err = std::string(who) + "more than 2^32 output molecules in one call"; return TKSMSEQ_ELIMIT; }
+        if (t_ivl >= 0x7fffffffull || t_mod >= 0x7fffffffull || t_id >= 0xffffffffull) { ctx->err = std::string(who) + "output batch too large (" + hint + ")"; return TKSMSEQ_ELIMIT; }
+        return TKSMSEQ_OK;
+    }
+    // the tables of n molecules with t_ivl intervals (and the sentinel behind them), t_mod substitutions and t_id id bytes
+    int alloc(uint64_t n, const char* who, const char* hint = "split the input") {
+        const int rc = limits(n, who, hint);
+        if (rc) return rc;
+        b->n_reads = n; b->n_intervals = t_ivl; b->n_mods = t_mod;
+        HIPCHK(ctx, b->reads.ensure(n * 8 + 64));
+        HIPCHK(ctx, b->intervals.ensure((t_ivl + 1) * 16 + 64));
+        HIPCHK(ctx, b->mods.ensure(t_mod * 8 + 64));
+        HIPCHK(ctx, b->ids.ensure(n * 8 + 64));
+        HIPCHK(ctx, b->idpool.ensure(t_id + 64));
+        return TKSMSEQ_OK;
+    }
+    // after the write kernels: the interval behind the last carries n_mods; lengths, order and sizing; *out owns the batch from here
+    int finish(tksmseq_batch** out) {
+        sentinel[3] = (uint32_t)t_mod;
+        HIPCHK(ctx, hipMemcpyAsync(b->intervals.as<uint32_t>() + 4 * t_ivl, sentinel, 16, hipMemcpyHostToDevice, ctx->stream));
+        const int rc = finalize_device_batch(ctx, b.get());
+        if (rc) return rc;
+        *out = b.release();
+        return TKSMSEQ_OK;
+    }
+};
 
 }  // namespace
 
@@ -230,10 +340,9 @@ int tksmseq_pcr_template_counts(tksmseq_ctx* ctx, const tksmseq_batch* in, const
     whole.template_begin = whole.template_end = 0;
     int rc = pcr_setup(ctx, in, &whole, keep, n_kept, P);
     if (rc) return rc;
-    DevBuf d_keep, d_cnt, d_status;
-    for (DevBuf* pb_ : {&d_keep, &d_cnt, &d_status}) { pb_->pooled = true; pb_->pool_stream = s; }   // (per-call temporaries: DevCache, ctx.h)
+    TmpBuf d_keep(s), d_cnt(s), d_status(s);
     if (!keep.empty()) { HIPCHK(ctx, d_keep.ensure(n_kept * 4 + 16)); HIPCHK(ctx, hipMemcpyAsync(d_keep.p, keep.data(), n_kept * 4, hipMemcpyHostToDevice, s)); }
-    tk::MolView M{view_of(in), in->d_dup.p ? in->d_dup.as<uint32_t>() : nullptr, in->n_intervals, in->n_mods, keep.empty() ? nullptr : d_keep.as<uint32_t>(), n_kept};
+    const tk::MolView M = mol_view(in, keep.empty() ? nullptr : d_keep.as<uint32_t>(), n_kept);
     HIPCHK(ctx, d_cnt.ensure(n_kept * 8 + 16));
     HIPCHK(ctx, d_status.ensure(64));
     HIPCHK(ctx, hipMemsetAsync(d_status.p, 0, 64, s));
@@ -257,69 +366,46 @@ int tksmseq_pcr(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_pcr_par
     std::vector<uint32_t> keep;
     uint64_t n_kept = 0;
     tk::PcrParams P{};
-    {
-        const int rc0 = pcr_setup(ctx, in, p, keep, n_kept, P);
-        if (rc0) return rc0;
-    }
-
-    DevBuf d_keep, d_cnt, d_off, d_status, n_mol, n_mask, n_ivl, n_mod, n_idl, o_ivl, o_mod, o_id;
-    for (DevBuf* pb_ : {&d_keep, &d_cnt, &d_off, &d_status, &n_mol, &n_mask, &n_ivl, &n_mod, &n_idl, &o_ivl, &o_mod, &o_id}) { pb_->pooled = true; pb_->pool_stream = s; }   // (per-call temporaries: DevCache, ctx.h)
+    int rc = pcr_setup(ctx, in, p, keep, n_kept, P);
+    if (rc) return rc;
+    OutBatch b(ctx);
+    TmpBuf d_keep(s), d_cnt(s), d_off(s), d_status(s), n_mol(s), n_mask(s), n_ivl(s), n_mod(s), n_idl(s);
     if (!keep.empty()) { HIPCHK(ctx, d_keep.ensure(n_kept * 4 + 16)); HIPCHK(ctx, hipMemcpyAsync(d_keep.p, keep.data(), n_kept * 4, hipMemcpyHostToDevice, s)); }
-    tk::MolView M{view_of(in), in->d_dup.p ? in->d_dup.as<uint32_t>() : nullptr, in->n_intervals, in->n_mods,
-                  keep.empty() ? nullptr : d_keep.as<uint32_t>(), n_kept};
+    const tk::MolView M = mol_view(in, keep.empty() ? nullptr : d_keep.as<uint32_t>(), n_kept);
     HIPCHK(ctx, d_cnt.ensure(n_kept * 8 + 16));
     HIPCHK(ctx, d_status.ensure(64));
     HIPCHK(ctx, hipMemsetAsync(d_status.p, 0, 64, s));
     HIPCHK(ctx, tk::launch_pcr_count(M, P, d_cnt.as<uint64_t>(), d_status.as<uint32_t>(), s));
     uint64_t n_nodes = 0;
-    int rc = scan_to(ctx, d_cnt, d_off, n_kept, &n_nodes);
-    if (rc) return rc;
+    if ((rc = scan_to(ctx, d_cnt, d_off, n_kept, &n_nodes))) return rc;
     uint32_t st = 0;
     HIPCHK(ctx, hipMemcpy(&st, d_status.p, 4, hipMemcpyDeviceToHost));
     if (st & 1u) { ctx->err = "PCR: more than " + std::to_string(tk::PCR_MAX_MUT) + " substitutions per copy (error rate x molecule length) are not supported"; return TKSMSEQ_ELIMIT; }
-    if (n_nodes >= 0xffffffffull) { ctx->err = "PCR: more than 2^32 output molecules in one call"; return TKSMSEQ_ELIMIT; }
+    if ((rc = b.limits(n_nodes, "PCR: ", "split the input"))) return rc;          // (before anything is sized by it)
     HIPCHK(ctx, n_mol.ensure(n_nodes * 4 + 16));
-    for (DevBuf* b : {&n_mask, &n_ivl, &n_mod, &n_idl}) HIPCHK(ctx, b->ensure(n_nodes * 8 + 16));
+    for (DevBuf* x : {&n_mask, &n_ivl, &n_mod, &n_idl}) HIPCHK(ctx, x->ensure(n_nodes * 8 + 16));
     HIPCHK(ctx, tk::launch_pcr_list(M, P, d_off.as<uint64_t>(), n_mol.as<uint32_t>(), n_mask.as<uint64_t>(), n_ivl.as<uint64_t>(), n_mod.as<uint64_t>(),
                                     n_idl.as<uint64_t>(), s));
-    uint64_t t_ivl = 0, t_mod = 0, t_id = 0;
-    if ((rc = scan_to(ctx, n_ivl, o_ivl, n_nodes, &t_ivl)) || (rc = scan_to(ctx, n_mod, o_mod, n_nodes, &t_mod)) || (rc = scan_to(ctx, n_idl, o_id, n_nodes, &t_id))) return rc;
-    if (t_ivl >= 0x7fffffffull || t_mod >= 0x7fffffffull || t_id >= 0xffffffffull) { ctx->err = "PCR: output batch too large (split the input)"; return TKSMSEQ_ELIMIT; }
-    std::unique_ptr<tksmseq_batch> b(new tksmseq_batch());
-    b->n_reads = n_nodes; b->n_intervals = t_ivl; b->n_mods = t_mod;
-    HIPCHK(ctx, b->reads.ensure(n_nodes * 8 + 64));
-    HIPCHK(ctx, b->intervals.ensure((t_ivl + 1) * 16 + 64));
-    HIPCHK(ctx, b->mods.ensure(t_mod * 8 + 64));
-    HIPCHK(ctx, b->ids.ensure(n_nodes * 8 + 64));
-    HIPCHK(ctx, b->idpool.ensure(t_id + 64));
-    if ((rc = copy_literals(ctx, in, b.get()))) return rc;
-    tk::MolOut O{b->reads.as<uint32_t>(), b->intervals.as<uint32_t>(), b->mods.as<uint32_t>(), b->ids.as<uint32_t>(), b->idpool.as<uint8_t>()};
-    HIPCHK(ctx, tk::launch_pcr_write(M, P, n_nodes, n_mol.as<uint32_t>(), n_mask.as<uint64_t>(), o_ivl.as<uint64_t>(), o_mod.as<uint64_t>(),
-                                     o_id.as<uint64_t>(), O, s));
-    const uint32_t sentinel[4] = {0u, 0u, 0u, (uint32_t)t_mod};          // the interval after the last carries n_mods
-    HIPCHK(ctx, hipMemcpyAsync(b->intervals.as<uint32_t>() + 4 * t_ivl, sentinel, 16, hipMemcpyHostToDevice, s));
+    if ((rc = b.scan(n_ivl, n_mod, n_idl, n_nodes)) || (rc = b.alloc(n_nodes, "PCR: ")) || (rc = b.literals(in))) return rc;
+    HIPCHK(ctx, tk::launch_pcr_write(M, P, n_nodes, n_mol.as<uint32_t>(), n_mask.as<uint64_t>(), b.o_ivl.as<uint64_t>(), b.o_mod.as<uint64_t>(),
+                                     b.o_id.as<uint64_t>(), b.tables(), s));
     // comments follow the template (re-serialised the way the reference's reader / writer pair does)
     if (!in->h_comments.empty() && !(p->flags & TKSMSEQ_MOL_NO_COMMENTS)) {
         std::vector<uint32_t> mol(n_nodes);
         HIPCHK(ctx, hipMemcpyAsync(mol.data(), n_mol.p, n_nodes * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipStreamSynchronize(s));
         b->h_comments.reserve(2 * n_nodes);
-        uint32_t last = 0xffffffffu, off = 0, len = 0;
         for (uint64_t j = 0; j < n_nodes; j++) {
             const uint32_t u = mol[j];
-            if (u != last) {
-                const std::string c = normalize_comment(in->h_comment_pool.data() + in->h_comments[2 * (size_t)u], in->h_comments[2 * (size_t)u + 1], {});
-                if (b->h_comment_pool.size() + c.size() >= 0xffffffffull) { ctx->err = "PCR: more than 4 GB of header comments in one batch (use template slices)"; return TKSMSEQ_ELIMIT; }
-                off = (uint32_t)b->h_comment_pool.size(); len = (uint32_t)c.size();
-                b->h_comment_pool.insert(b->h_comment_pool.end(), c.begin(), c.end());
-                last = u;
-            }
-            b->h_comments.push_back(off); b->h_comments.push_back(len);
+            if (j && u == mol[j - 1]) {                                   // (a further copy of the same template: its entry again)
+                const size_t k = b->h_comments.size();
+                const uint32_t off = b->h_comments[k - 2], len = b->h_comments[k - 1];
+                b->h_comments.push_back(off); b->h_comments.push_back(len);
+            } else if ((rc = append_comment(ctx, b.get(), normalize_comment(in->h_comment_pool.data() + in->h_comments[2 * (size_t)u], in->h_comments[2 * (size_t)u + 1], {}),
+                                            "PCR", "use template slices"))) return rc;
         }
     }
-    if ((rc = finalize_device_batch(ctx, b.get()))) return rc;
-    *out = b.release();
-    return TKSMSEQ_OK;
+    return b.finish(out);
 }
 
 int tksmseq_truncate(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_trc_params* p, tksmseq_batch** out) {
@@ -331,8 +417,7 @@ int tksmseq_truncate(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_tr
     tk::TrcParams T{};
     T.seed = p->seed; T.mode = p->mode; T.mu = p->mu; T.sigma = p->sigma; T.min_len = 100;      // truncate()'s default min_val
     T.always_end = p->always_end ? 1 : 0; T.models_length = p->kde_models_length ? 1 : 0;
-    DevBuf d_x, d_y, d_cdf, d_rn, d_sl, d_sc;
-    for (DevBuf* pb_ : {&d_x, &d_y, &d_cdf, &d_rn, &d_sl, &d_sc}) { pb_->pooled = true; pb_->pool_stream = s; }   // (per-call temporaries: DevCache, ctx.h)
+    TmpBuf d_x(s), d_y(s), d_cdf(s), d_rn(s), d_sl(s), d_sc(s);
     TrcModelHost tm;
     auto upv = [&](DevBuf& b, const void* src, size_t bytes) -> int {
         HIPCHK(ctx, b.ensure(bytes + 64));
@@ -352,47 +437,29 @@ int tksmseq_truncate(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_tr
         T.slab = d_sl.as<double>(); T.scdf = d_sc.as<double>();
     } else if (p->mode != TKSMSEQ_TRC_NORMAL && p->mode != TKSMSEQ_TRC_LOGNORMAL) { ctx->err = "truncate: unknown mode"; return TKSMSEQ_EINVAL; }
     else if (!std::isfinite(p->mu) || !std::isfinite(p->sigma)) { ctx->err = "truncate: mu and sigma must be finite"; return TKSMSEQ_EINVAL; }
-    tk::MolView M{view_of(in), in->d_dup.p ? in->d_dup.as<uint32_t>() : nullptr, in->n_intervals, in->n_mods, nullptr, n};
-    DevBuf kf, kt, tl, ts, n_ivl, n_mod, n_idl, o_ivl, o_mod, o_id;
-    for (DevBuf* pb_ : {&kf, &kt, &tl, &ts, &n_ivl, &n_mod, &n_idl, &o_ivl, &o_mod, &o_id}) { pb_->pooled = true; pb_->pool_stream = s; }   // (per-call temporaries: DevCache, ctx.h)
+    const tk::MolView M = mol_view(in);
+    OutBatch b(ctx);
+    TmpBuf kf(s), kt(s), tl(s), ts(s), n_ivl(s), n_mod(s), n_idl(s);
     HIPCHK(ctx, kf.ensure(n * 4 + 16)); HIPCHK(ctx, kt.ensure(n * 4 + 16));
-    for (DevBuf* b : {&tl, &ts, &n_ivl, &n_mod, &n_idl}) HIPCHK(ctx, b->ensure(n * 8 + 16));
+    for (DevBuf* x : {&tl, &ts, &n_ivl, &n_mod, &n_idl}) HIPCHK(ctx, x->ensure(n * 8 + 16));
     HIPCHK(ctx, tk::launch_trc_plan(M, T, p->first_molecule_index, kf.as<uint32_t>(), kt.as<uint32_t>(), tl.as<double>(), ts.as<double>(),
                                     n_ivl.as<uint64_t>(), n_mod.as<uint64_t>(), n_idl.as<uint64_t>(), s));
-    uint64_t t_ivl = 0, t_mod = 0, t_id = 0;
-    if ((rc = scan_to(ctx, n_ivl, o_ivl, n, &t_ivl)) || (rc = scan_to(ctx, n_mod, o_mod, n, &t_mod)) || (rc = scan_to(ctx, n_idl, o_id, n, &t_id))) return rc;
-    std::unique_ptr<tksmseq_batch> b(new tksmseq_batch());
-    b->n_reads = n; b->n_intervals = t_ivl; b->n_mods = t_mod;
-    HIPCHK(ctx, b->reads.ensure(n * 8 + 64));
-    HIPCHK(ctx, b->intervals.ensure((t_ivl + 1) * 16 + 64));
-    HIPCHK(ctx, b->mods.ensure(t_mod * 8 + 64));
-    HIPCHK(ctx, b->ids.ensure(n * 8 + 64));
-    HIPCHK(ctx, b->idpool.ensure(t_id + 64));
-    if ((rc = copy_literals(ctx, in, b.get()))) return rc;
-    tk::MolOut O{b->reads.as<uint32_t>(), b->intervals.as<uint32_t>(), b->mods.as<uint32_t>(), b->ids.as<uint32_t>(), b->idpool.as<uint8_t>()};
-    HIPCHK(ctx, tk::launch_trc_write(M, kf.as<uint32_t>(), kt.as<uint32_t>(), o_ivl.as<uint64_t>(), o_mod.as<uint64_t>(), o_id.as<uint64_t>(), O, s));
-    const uint32_t sentinel[4] = {0u, 0u, 0u, (uint32_t)t_mod};
-    HIPCHK(ctx, hipMemcpyAsync(b->intervals.as<uint32_t>() + 4 * t_ivl, sentinel, 16, hipMemcpyHostToDevice, s));
+    // (a truncated batch is no larger than its input, so the limits cannot trip here: checked all the same, like every other output)
+    if ((rc = b.scan(n_ivl, n_mod, n_idl, n)) || (rc = b.alloc(n, "truncate: ")) || (rc = b.literals(in))) return rc;
+    HIPCHK(ctx, tk::launch_trc_write(M, kf.as<uint32_t>(), kt.as<uint32_t>(), b.o_ivl.as<uint64_t>(), b.o_mod.as<uint64_t>(), b.o_id.as<uint64_t>(), b.tables(), s));
     // comments: the template's, plus truncated=chr:start-end,... for what was cut away and (KDE mode) TR=<length>,<3' share>
     // (src/truncate.cpp:54-60, :343).  Needs the input tables on the host.
     if (!in->h_comments.empty() && !(p->flags & TKSMSEQ_MOL_NO_COMMENTS)) {
-        std::vector<uint32_t> reads(2 * n), ivs(4 * (in->n_intervals + 1)), hkf(n), hkt(n);
+        HostTables H;
+        std::vector<uint32_t> hkf(n), hkt(n);
         std::vector<double> htl(n), hts(n);
-        std::vector<uint64_t> lits(2 * in->n_literals);
-        std::vector<char> lpool(in->litpool.cap);
-        HIPCHK(ctx, hipMemcpyAsync(reads.data(), in->reads.p, n * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(ivs.data(), in->intervals.p, (in->n_intervals + 1) * 16, hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipMemcpyAsync(hkf.data(), kf.p, n * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipMemcpyAsync(hkt.data(), kt.p, n * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipMemcpyAsync(htl.data(), tl.p, n * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipMemcpyAsync(hts.data(), ts.p, n * 8, hipMemcpyDeviceToHost, s));
-        if (in->n_literals) HIPCHK(ctx, hipMemcpyAsync(lits.data(), in->literals.p, in->n_literals * 16, hipMemcpyDeviceToHost, s));
-        if (!lpool.empty()) HIPCHK(ctx, hipMemcpyAsync(lpool.data(), in->litpool.p, lpool.size(), hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        auto chr_of = [&](uint32_t c) -> std::string {
-            if (c >> 31) { const uint32_t li = c & 0x7fffffffu; return std::string(lpool.data() + lits[2 * (size_t)li], (size_t)lits[2 * (size_t)li + 1]); }
-            return ctx->contig_names[c];
-        };
+        if ((rc = H.fetch(ctx, in, HostTables::SEGMENTS))) return rc;          // (drains the stream: the four copies above as well)
+        const auto &reads = H.reads, &ivs = H.ivs;
+        auto chr_of = [&](uint32_t c) -> std::string { std::string name; H.append_contig(ctx, c, name); return name; };
         for (uint64_t r = 0; r < n; r++) {
             std::vector<std::pair<std::string, std::string>> extra;
             const int w0 = (int)(hkf[r] & 0x7fffffffu), w1 = (int)(hkt[r] & 0x7fffffffu);
@@ -443,79 +510,39 @@ int tksmseq_truncate(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_tr
                 char sr[32]; snprintf(sr, sizeof sr, "%.2f", hts[r]);
                 extra.push_back({"TR", fmt_double(htl[r]) + "," + sr});
             }
-            const std::string cmt = normalize_comment(in->h_comment_pool.data() + in->h_comments[2 * r], in->h_comments[2 * r + 1], extra);
-            if (b->h_comment_pool.size() + cmt.size() >= 0xffffffffull) { ctx->err = "truncate: more than 4 GB of header comments in one batch (split the input)"; return TKSMSEQ_ELIMIT; }
-            b->h_comments.push_back((uint32_t)b->h_comment_pool.size()); b->h_comments.push_back((uint32_t)cmt.size());
-            b->h_comment_pool.insert(b->h_comment_pool.end(), cmt.begin(), cmt.end());
+            if ((rc = append_comment(ctx, b.get(), normalize_comment(in->h_comment_pool.data() + in->h_comments[2 * r], in->h_comments[2 * r + 1], extra), "truncate"))) return rc;
         }
     }
-    if ((rc = finalize_device_batch(ctx, b.get()))) return rc;
-    *out = b.release();
-    return TKSMSEQ_OK;
+    return b.finish(out);
 }
 
 // ---- segment edits: polyA, tag, scb, flip ----------------------------------------------------------------------------------------
-// The output's literal table: the input's entries and pool (the pool copied whole, its capacity), then n_new entries and new_bytes
-// pool bytes behind them; lit_base / pool_base: where the new ones start.
-static int edit_literals(tksmseq_ctx* ctx, const tksmseq_batch* in, tksmseq_batch* b, uint64_t n_new, uint64_t new_bytes, uint32_t& lit_base,
-                         uint64_t& pool_base) {
-    const uint64_t nl = in->n_literals + n_new;
-    if (nl >= 0x80000000ull) { ctx->err = "more than 2^31 literals in one batch (split the input)"; return TKSMSEQ_ELIMIT; }
-    hipStream_t s = ctx->stream;
-    b->n_literals = nl;
-    pool_base = in->litpool.cap;
-    lit_base = (uint32_t)in->n_literals;
-    HIPCHK(ctx, b->literals.ensure(nl * 16 + 64));
-    HIPCHK(ctx, b->litpool.ensure(pool_base + new_bytes + 64));
-    if (in->n_literals) HIPCHK(ctx, hipMemcpyAsync(b->literals.p, in->literals.p, in->n_literals * 16, hipMemcpyDeviceToDevice, s));
-    if (in->litpool.cap) HIPCHK(ctx, hipMemcpyAsync(b->litpool.p, in->litpool.p, in->litpool.cap, hipMemcpyDeviceToDevice, s));
-    return TKSMSEQ_OK;
-}
-
 // count, scan, allocate, write: every molecule of `in` (unrolled) with literal pre[r] in front of and post[r] behind its segments, which
-// are reversed and strand-toggled where flip[r] (device arrays; null: none of that kind).  b's literal table is already complete.
+// are reversed and strand-toggled where flip[r] (device arrays; null: none of that kind).  b's literal table is already complete, and
+// the caller's host tables must live until b.finish(), which drains the stream.
 // pal: the palindromic tail noise of tksmseq_append_noise, whose kernels add a hairpin behind each molecule to the counts and to the tables.
 struct PalHook { tk::NoiseParams P; uint64_t first; const uint4* plan; };
-static int edit_apply(tksmseq_ctx* ctx, const tksmseq_batch* in, const uint32_t* pre, const uint32_t* post, const uint8_t* flip, tksmseq_batch* b,
+static int edit_apply(tksmseq_ctx* ctx, const tksmseq_batch* in, const uint32_t* pre, const uint32_t* post, const uint8_t* flip, OutBatch& b,
                       const PalHook* pal = nullptr) {
     hipStream_t s = ctx->stream;
     const uint64_t n = in->n_reads;
-    tk::MolView M{view_of(in), in->d_dup.p ? in->d_dup.as<uint32_t>() : nullptr, in->n_intervals, in->n_mods, nullptr, n};
-    DevBuf n_ivl, n_mod, n_idl, o_ivl, o_mod, o_id;
-    for (DevBuf* pb_ : {&n_ivl, &n_mod, &n_idl, &o_ivl, &o_mod, &o_id}) { pb_->pooled = true; pb_->pool_stream = s; }   // (per-call temporaries: DevCache, ctx.h)
+    const tk::MolView M = mol_view(in);
+    TmpBuf n_ivl(s), n_mod(s), n_idl(s);
     for (DevBuf* x : {&n_ivl, &n_mod, &n_idl}) HIPCHK(ctx, x->ensure(n * 8 + 16));
     HIPCHK(ctx, tk::launch_edit_count(M, pre, post, n_ivl.as<uint64_t>(), n_mod.as<uint64_t>(), n_idl.as<uint64_t>(), s));
     if (pal) HIPCHK(ctx, tk::launch_pal_count(M, pal->P, pal->first, pal->plan, n_ivl.as<uint64_t>(), n_mod.as<uint64_t>(), s));
-    uint64_t t_ivl = 0, t_mod = 0, t_id = 0;
     int rc;
-    if ((rc = scan_to(ctx, n_ivl, o_ivl, n, &t_ivl)) || (rc = scan_to(ctx, n_mod, o_mod, n, &t_mod)) || (rc = scan_to(ctx, n_idl, o_id, n, &t_id))) return rc;
-    if (t_ivl >= 0x7fffffffull || t_mod >= 0x7fffffffull || t_id >= 0xffffffffull) { ctx->err = "output batch too large (split the input)"; return TKSMSEQ_ELIMIT; }
-    b->n_reads = n; b->n_intervals = t_ivl; b->n_mods = t_mod;
-    HIPCHK(ctx, b->reads.ensure(n * 8 + 64));
-    HIPCHK(ctx, b->intervals.ensure((t_ivl + 1) * 16 + 64));
-    HIPCHK(ctx, b->mods.ensure(t_mod * 8 + 64));
-    HIPCHK(ctx, b->ids.ensure(n * 8 + 64));
-    HIPCHK(ctx, b->idpool.ensure(t_id + 64));
-    tk::MolOut O{b->reads.as<uint32_t>(), b->intervals.as<uint32_t>(), b->mods.as<uint32_t>(), b->ids.as<uint32_t>(), b->idpool.as<uint8_t>()};
-    HIPCHK(ctx, tk::launch_edit_write(M, pre, post, flip, b->literals.as<uint64_t>(), o_ivl.as<uint64_t>(), o_mod.as<uint64_t>(), o_id.as<uint64_t>(), O, s));
-    if (pal) HIPCHK(ctx, tk::launch_pal_write(M, pal->P, pal->first, pal->plan, o_ivl.as<uint64_t>(), o_mod.as<uint64_t>(), O, s));
-    const uint32_t sentinel[4] = {0u, 0u, 0u, (uint32_t)t_mod};
-    HIPCHK(ctx, hipMemcpyAsync(b->intervals.as<uint32_t>() + 4 * t_ivl, sentinel, 16, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));                    // (sentinel and the callers' host tables are read by now)
+    if ((rc = b.scan(n_ivl, n_mod, n_idl, n)) || (rc = b.alloc(n, ""))) return rc;
+    const tk::MolOut O = b.tables();
+    HIPCHK(ctx, tk::launch_edit_write(M, pre, post, flip, b->literals.as<uint64_t>(), b.o_ivl.as<uint64_t>(), b.o_mod.as<uint64_t>(), b.o_id.as<uint64_t>(), O, s));
+    if (pal) HIPCHK(ctx, tk::launch_pal_write(M, pal->P, pal->first, pal->plan, b.o_ivl.as<uint64_t>(), b.o_mod.as<uint64_t>(), O, s));
     return TKSMSEQ_OK;
 }
 
 // comments unchanged (the writer re-serialises them, normalize_comment)
-static void edit_comments(const tksmseq_batch* in, tksmseq_batch* b, int32_t flags) {
+static void edit_comments(const tksmseq_batch* in, OutBatch& b, int32_t flags) {
     if (flags & TKSMSEQ_MOL_NO_COMMENTS) return;
     b->h_comments = in->h_comments; b->h_comment_pool = in->h_comment_pool;
-}
-
-static int edit_finish(tksmseq_ctx* ctx, std::unique_ptr<tksmseq_batch>& b, tksmseq_batch** out) {
-    const int rc = finalize_device_batch(ctx, b.get());
-    if (rc) return rc;
-    *out = b.release();
-    return TKSMSEQ_OK;
 }
 
 int tksmseq_polya(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_polya_params* p, tksmseq_batch** out) {
@@ -536,25 +563,23 @@ int tksmseq_polya(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_polya
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const uint64_t n = in->n_reads, L = (uint64_t)p->max_length;
-    std::unique_ptr<tksmseq_batch> b(new tksmseq_batch());
-    uint32_t lit_base = 0; uint64_t pool_base = 0;
-    int rc = edit_literals(ctx, in, b.get(), L, L, lit_base, pool_base);
+    OutBatch b(ctx);
+    int rc = b.literals(in, L, L);
     if (rc) return rc;
-    // literal lit_base + k is "A" x (k + 1): all of them at the start of one run of max_length 'A's
+    // literal b.lit_base + k is "A" x (k + 1): all of them at the start of one run of max_length 'A's
     std::vector<uint64_t> ent(2 * L);
-    for (uint64_t k = 0; k < L; k++) { ent[2 * k] = pool_base; ent[2 * k + 1] = k + 1; }
+    for (uint64_t k = 0; k < L; k++) { ent[2 * k] = b.pool_base; ent[2 * k + 1] = k + 1; }
     if (L) {
-        HIPCHK(ctx, hipMemcpyAsync(b->literals.as<uint64_t>() + 2ull * lit_base, ent.data(), L * 16, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemsetAsync(b->litpool.as<uint8_t>() + pool_base, 'A', L, s));
+        HIPCHK(ctx, hipMemcpyAsync(b->literals.as<uint64_t>() + 2ull * b.lit_base, ent.data(), L * 16, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemsetAsync(b->litpool.as<uint8_t>() + b.pool_base, 'A', L, s));
     }
-    DevBuf d_post;
-    d_post.pooled = true; d_post.pool_stream = s;
+    TmpBuf d_post(s);
     HIPCHK(ctx, d_post.ensure(n * 4 + 16));
-    tk::PlaParams P{p->seed, p->dist, p->a, p->b, p->min_length, p->max_length, lit_base};
+    tk::PlaParams P{p->seed, p->dist, p->a, p->b, p->min_length, p->max_length, b.lit_base};
     HIPCHK(ctx, tk::launch_pla_plan(n, P, p->first_molecule_index, d_post.as<uint32_t>(), s));
-    if ((rc = edit_apply(ctx, in, nullptr, d_post.as<uint32_t>(), nullptr, b.get()))) return rc;
-    edit_comments(in, b.get(), p->flags);
-    return edit_finish(ctx, b, out);
+    if ((rc = edit_apply(ctx, in, nullptr, d_post.as<uint32_t>(), nullptr, b))) return rc;
+    edit_comments(in, b, p->flags);
+    return b.finish(out);
 }
 
 // fmt2seq's table (src/util.h:62-80): number of choices of a letter, 0 if the table does not know it
@@ -585,15 +610,13 @@ int tksmseq_tag(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_tag_par
     uint64_t n_new = 0, bytes = 0;
     for (int e = 0; e < 2; e++)
         if (!fmt[e].empty()) { n_new += amb[e] ? n : 1; bytes += (amb[e] ? n : 1) * fmt[e].size(); }
-    std::unique_ptr<tksmseq_batch> b(new tksmseq_batch());
-    uint32_t lit_base = 0; uint64_t pool_base = 0;
-    int rc = edit_literals(ctx, in, b.get(), n_new, bytes, lit_base, pool_base);
+    OutBatch b(ctx);
+    int rc = b.literals(in, n_new, bytes);
     if (rc) return rc;
-    DevBuf d_fmt[2], d_pre, d_post;
-    for (DevBuf* pb_ : {&d_fmt[0], &d_fmt[1], &d_pre, &d_post}) { pb_->pooled = true; pb_->pool_stream = s; }
+    TmpBuf d_fmt[2] = {TmpBuf(s), TmpBuf(s)}, d_pre(s), d_post(s);
     tk::TagParams T{};
     T.seed = p->seed;
-    uint64_t li = lit_base, off = pool_base;
+    uint64_t li = b.lit_base, off = b.pool_base;
     uint64_t ent[2][2];
     for (int e = 0; e < 2; e++) {
         tk::TagEnd& E = T.end[e];
@@ -613,18 +636,16 @@ int tksmseq_tag(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_tag_par
     HIPCHK(ctx, d_post.ensure(n * 4 + 16));
     HIPCHK(ctx, tk::launch_tag_plan(n, T, p->first_molecule_index, d_pre.as<uint32_t>(), d_post.as<uint32_t>(), b->literals.as<uint64_t>(),
                                     b->litpool.as<uint8_t>(), s));
-    if ((rc = edit_apply(ctx, in, d_pre.as<uint32_t>(), d_post.as<uint32_t>(), nullptr, b.get()))) return rc;
-    edit_comments(in, b.get(), p->flags);
-    return edit_finish(ctx, b, out);
+    if ((rc = edit_apply(ctx, in, d_pre.as<uint32_t>(), d_post.as<uint32_t>(), nullptr, b))) return rc;
+    edit_comments(in, b, p->flags);
+    return b.finish(out);
 }
 
 // id of molecule r as the writer prints it (with the unroll suffix), for error messages
 static std::string molecule_id(tksmseq_ctx* ctx, const tksmseq_batch* in, uint64_t r) {
-    uint32_t e[2] = {0, 0};
-    std::string id;
-    if (hipMemcpy(e, in->ids.as<uint32_t>() + 2 * r, 8, hipMemcpyDeviceToHost) != hipSuccess) return "#" + std::to_string(r);
-    id.resize(e[1]);
-    if (e[1] && hipMemcpy(&id[0], in->idpool.as<uint8_t>() + e[0], e[1], hipMemcpyDeviceToHost) != hipSuccess) return "#" + std::to_string(r);
+    HostTables H;
+    if (H.fetch(ctx, in, HostTables::IDS)) return "#" + std::to_string(r);
+    std::string id(H.idpool.data() + H.ids[2 * r], H.ids[2 * r + 1]);
     if (!in->h_dup.empty() && (in->h_dup[r] >> 31)) id += "_" + std::to_string(in->h_dup[r] & 0x7fffffffu);
     return id;
 }
@@ -637,7 +658,7 @@ int tksmseq_scb(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_scb_par
     const uint64_t n = in->n_reads;
     if (n && in->h_comments.empty()) { ctx->err = "scb: the batch carries no header comments (CB barcodes)"; return TKSMSEQ_EINVAL; }
     // the host resolves the barcodes (get_comment("CB")[0]) in one pass and de-duplicates them into literals
-    std::unique_ptr<tksmseq_batch> b(new tksmseq_batch());
+    OutBatch b(ctx);
     const bool want_comments = !(p->flags & TKSMSEQ_MOL_NO_COMMENTS);
     std::vector<uint32_t> post(n);
     std::unordered_map<std::string, uint32_t> index;
@@ -661,27 +682,23 @@ int tksmseq_scb(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_scb_par
         }
         if (want_comments) {
             if (!p->keep_meta_barcodes) meta.erase(it);
-            const std::string c = dump_meta(meta);
-            if (b->h_comment_pool.size() + c.size() >= 0xffffffffull) { ctx->err = "scb: more than 4 GB of header comments in one batch (split the input)"; return TKSMSEQ_ELIMIT; }
-            b->h_comments.push_back((uint32_t)b->h_comment_pool.size()); b->h_comments.push_back((uint32_t)c.size());
-            b->h_comment_pool.insert(b->h_comment_pool.end(), c.begin(), c.end());
+            const int rc = append_comment(ctx, b.get(), dump_meta(meta), "scb");
+            if (rc) return rc;
         }
     }
-    uint32_t lit_base = 0; uint64_t pool_base = 0;
-    int rc = edit_literals(ctx, in, b.get(), index.size(), bytes.size(), lit_base, pool_base);
+    int rc = b.literals(in, index.size(), bytes.size());
     if (rc) return rc;
-    for (uint64_t r = 0; r < n; r++) if (post[r] != tk::EDIT_NONE) post[r] += lit_base;
-    for (size_t k = 0; k < ent.size(); k += 2) ent[k] += pool_base;
+    for (uint64_t r = 0; r < n; r++) if (post[r] != tk::EDIT_NONE) post[r] += b.lit_base;
+    for (size_t k = 0; k < ent.size(); k += 2) ent[k] += b.pool_base;
     if (!ent.empty()) {
-        HIPCHK(ctx, hipMemcpyAsync(b->literals.as<uint64_t>() + 2ull * lit_base, ent.data(), ent.size() * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(b->litpool.as<uint8_t>() + pool_base, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(b->literals.as<uint64_t>() + 2ull * b.lit_base, ent.data(), ent.size() * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(b->litpool.as<uint8_t>() + b.pool_base, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s));
     }
-    DevBuf d_post;
-    d_post.pooled = true; d_post.pool_stream = s;
+    TmpBuf d_post(s);
     HIPCHK(ctx, d_post.ensure(n * 4 + 16));
     if (n) HIPCHK(ctx, hipMemcpyAsync(d_post.p, post.data(), n * 4, hipMemcpyHostToDevice, s));
-    if ((rc = edit_apply(ctx, in, nullptr, d_post.as<uint32_t>(), nullptr, b.get()))) return rc;
-    return edit_finish(ctx, b, out);
+    if ((rc = edit_apply(ctx, in, nullptr, d_post.as<uint32_t>(), nullptr, b))) return rc;
+    return b.finish(out);
 }
 
 int tksmseq_flip(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_flip_params* p, tksmseq_batch** out) {
@@ -690,16 +707,15 @@ int tksmseq_flip(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_flip_p
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const uint64_t n = in->n_reads;
-    std::unique_ptr<tksmseq_batch> b(new tksmseq_batch());
-    int rc = copy_literals(ctx, in, b.get());
+    OutBatch b(ctx);
+    int rc = b.literals(in);
     if (rc) return rc;
-    DevBuf d_flip;
-    d_flip.pooled = true; d_flip.pool_stream = s;
+    TmpBuf d_flip(s);
     HIPCHK(ctx, d_flip.ensure(n + 16));
     HIPCHK(ctx, tk::launch_flip_plan(n, p->seed, p->flip_probability, p->first_molecule_index, d_flip.as<uint8_t>(), s));
-    if ((rc = edit_apply(ctx, in, nullptr, nullptr, d_flip.as<uint8_t>(), b.get()))) return rc;
-    edit_comments(in, b.get(), p->flags);
-    return edit_finish(ctx, b, out);
+    if ((rc = edit_apply(ctx, in, nullptr, nullptr, d_flip.as<uint8_t>(), b))) return rc;
+    edit_comments(in, b, p->flags);
+    return b.finish(out);
 }
 
 // ---- tail-noise ------------------------------------------------------------------------------------------------------------------
@@ -716,21 +732,20 @@ int tksmseq_append_noise(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmse
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const uint64_t n = in->n_reads;
-    DevBuf d_alpha, d_plan, d_len, d_nblk, d_off, d_over, d_post;
-    for (DevBuf* pb_ : {&d_alpha, &d_plan, &d_len, &d_nblk, &d_off, &d_over, &d_post}) { pb_->pooled = true; pb_->pool_stream = s; }   // (per-call temporaries: DevCache, ctx.h)
+    TmpBuf d_alpha(s), d_plan(s), d_len(s), d_nblk(s), d_off(s), d_over(s), d_post(s);
     HIPCHK(ctx, d_alpha.ensure(k + 16));
     HIPCHK(ctx, hipMemcpyAsync(d_alpha.p, p->alphabet, k, hipMemcpyHostToDevice, s));
     const tk::NoiseParams P{p->seed, p->dist == TKSMSEQ_NOISE_LOGNORMAL ? tk::NOISE_LOGNORMAL : tk::NOISE_NORMAL, p->mu, p->sigma, p->error_rate,
                             d_alpha.as<uint8_t>(), (uint32_t)k};
-    tk::MolView M{view_of(in), in->d_dup.p ? in->d_dup.as<uint32_t>() : nullptr, in->n_intervals, in->n_mods, nullptr, n};
-    std::unique_ptr<tksmseq_batch> b(new tksmseq_batch());
+    const tk::MolView M = mol_view(in);
+    OutBatch b(ctx);
     int rc;
     if (p->palindromic) {
-        if ((rc = copy_literals(ctx, in, b.get()))) return rc;
+        if ((rc = b.literals(in))) return rc;
         HIPCHK(ctx, d_plan.ensure(n * 16 + 16));
         HIPCHK(ctx, tk::launch_noise_plan(M, P, p->first_molecule_index, nullptr, nullptr, nullptr, d_plan.as<uint4>(), s));
         const PalHook pal{P, p->first_molecule_index, d_plan.as<uint4>()};
-        if ((rc = edit_apply(ctx, in, nullptr, nullptr, nullptr, b.get(), &pal))) return rc;
+        if ((rc = edit_apply(ctx, in, nullptr, nullptr, nullptr, b, &pal))) return rc;
     } else {
         HIPCHK(ctx, d_len.ensure(n * 4 + 16));
         HIPCHK(ctx, d_nblk.ensure(n * 8 + 16));
@@ -746,19 +761,18 @@ int tksmseq_append_noise(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmse
             return TKSMSEQ_ELIMIT;
         }
         if (n_blocks >= (1ull << 30)) { ctx->err = "tail-noise: more than 4 GB of noise letters in one batch (split the input)"; return TKSMSEQ_ELIMIT; }
-        uint32_t lit_base = 0; uint64_t pool_base = 0;
-        if ((rc = edit_literals(ctx, in, b.get(), n, 4 * n_blocks, lit_base, pool_base))) return rc;
+        if ((rc = b.literals(in, n, 4 * n_blocks))) return rc;
         HIPCHK(ctx, d_post.ensure(n * 4 + 16));
         if (n) {
             HIPCHK(ctx, hipMemsetAsync(d_post.p, 0xff, n * 4, s));                                   // EDIT_NONE
-            HIPCHK(ctx, hipMemsetAsync(b->literals.as<uint64_t>() + 2ull * lit_base, 0, n * 16, s));   // (molecules without noise: an empty entry nobody names)
+            HIPCHK(ctx, hipMemsetAsync(b->literals.as<uint64_t>() + 2ull * b.lit_base, 0, n * 16, s));   // (molecules without noise: an empty entry nobody names)
         }
-        HIPCHK(ctx, tk::launch_noise_fill(n, n_blocks, P, p->first_molecule_index, d_len.as<uint32_t>(), d_off.as<uint64_t>(), lit_base, pool_base,
+        HIPCHK(ctx, tk::launch_noise_fill(n, n_blocks, P, p->first_molecule_index, d_len.as<uint32_t>(), d_off.as<uint64_t>(), b.lit_base, b.pool_base,
                                           b->literals.as<uint64_t>(), b->litpool.as<uint8_t>(), d_post.as<uint32_t>(), s));
-        if ((rc = edit_apply(ctx, in, nullptr, d_post.as<uint32_t>(), nullptr, b.get()))) return rc;
+        if ((rc = edit_apply(ctx, in, nullptr, d_post.as<uint32_t>(), nullptr, b))) return rc;
     }
-    edit_comments(in, b.get(), p->flags);
-    return edit_finish(ctx, b, out);
+    edit_comments(in, b, p->flags);
+    return b.finish(out);
 }
 
 // ---- random-wgs ------------------------------------------------------------------------------------------------------------------
@@ -811,8 +825,7 @@ int tksmseq_wgs(tksmseq_ctx* ctx, const tksmseq_wgs_params* p, tksmseq_batch** o
     const bool owed = p->base_count > 0 && p->bases_before < (uint64_t)p->base_count;
     progress->reached = owed ? 0 : 1;
     const uint64_t nn = owed ? n : 0;                                   // (nothing owed: an empty batch, no candidate taken)
-    DevBuf d_plan, d_flag, d_bases, d_rank, d_bsum, d_idlen, d_idoff, d_cut;
-    for (DevBuf* pb_ : {&d_plan, &d_flag, &d_bases, &d_rank, &d_bsum, &d_idlen, &d_idoff, &d_cut}) { pb_->pooled = true; pb_->pool_stream = s; }   // (per-call temporaries: DevCache, ctx.h)
+    TmpBuf d_plan(s), d_flag(s), d_bases(s), d_rank(s), d_bsum(s), d_idlen(s), d_idoff(s), d_cut(s);
     uint64_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};                           // cut[4], rank[n], bsum[n], idoff[n]
     if (nn) {
         HIPCHK(ctx, d_plan.ensure(nn * 16 + 16));
@@ -835,30 +848,20 @@ int tksmseq_wgs(tksmseq_ctx* ctx, const tksmseq_wgs_params* p, tksmseq_batch** o
         HIPCHK(ctx, hipStreamSynchronize(s));
     }
     const bool reached = h[3] != 0;
-    const uint64_t n_mol = reached ? h[0] : h[4], n_bases = reached ? h[1] : h[5], t_id = h[6];
-    if (t_id >= 0xffffffffull) { ctx->err = "random-wgs: output batch too large (fewer candidates per call)"; return TKSMSEQ_ELIMIT; }
-    std::unique_ptr<tksmseq_batch> b(new tksmseq_batch());
-    b->n_reads = n_mol; b->n_intervals = n_mol; b->n_mods = 0; b->n_literals = 0;
-    HIPCHK(ctx, b->reads.ensure(n_mol * 8 + 64));
-    HIPCHK(ctx, b->intervals.ensure((n_mol + 1) * 16 + 64));
-    HIPCHK(ctx, b->mods.ensure(64));
-    HIPCHK(ctx, b->ids.ensure(n_mol * 8 + 64));
-    HIPCHK(ctx, b->idpool.ensure(t_id + 64));
-    HIPCHK(ctx, b->literals.ensure(64));
-    HIPCHK(ctx, b->litpool.ensure(64));
-    if (n_mol) {
-        tk::MolOut O{b->reads.as<uint32_t>(), b->intervals.as<uint32_t>(), b->mods.as<uint32_t>(), b->ids.as<uint32_t>(), b->idpool.as<uint8_t>()};
+    const uint64_t n_mol = reached ? h[0] : h[4], n_bases = reached ? h[1] : h[5];
+    // one segment per molecule, no substitutions, no literals (the scans above are this module's own: rank and cut)
+    OutBatch b(ctx);
+    b.t_ivl = n_mol; b.t_mod = 0; b.t_id = h[6];
+    if ((rc = b.alloc(n_mol, "random-wgs: ", "fewer candidates per call")) || (rc = b.literals(nullptr))) return rc;
+    if (n_mol)
         HIPCHK(ctx, tk::launch_wgs_write(nn, d_plan.as<uint4>(), d_rank.as<uint64_t>(), d_idlen.as<uint64_t>(), d_idoff.as<uint64_t>(), ctx->d_wgs_nameoff.as<uint32_t>(),
-                                         ctx->d_wgs_namelen.as<uint32_t>(), ctx->d_wgs_names.as<uint8_t>(), p->molecules_before, O, s));
-    }
-    HIPCHK(ctx, hipMemsetAsync(b->intervals.as<uint32_t>() + 4 * n_mol, 0, 16, s));      // the interval after the last carries n_mods (0)
-    if ((rc = finalize_device_batch(ctx, b.get()))) return rc;
+                                         ctx->d_wgs_namelen.as<uint32_t>(), ctx->d_wgs_names.as<uint8_t>(), p->molecules_before, b.tables(), s));
+    if ((rc = b.finish(out))) return rc;
     if (nn) {
         progress->next_candidate = p->first_candidate + (reached ? h[2] : nn);
         progress->molecules = p->molecules_before + n_mol; progress->bases = p->bases_before + n_bases;
         progress->reached = reached ? 1 : 0;
     }
-    *out = b.release();
     return TKSMSEQ_OK;
 }
 
@@ -866,19 +869,12 @@ int tksmseq_batch_to_mdf_text(tksmseq_ctx* ctx, const tksmseq_batch* b, char** t
     if (!ctx || !b || !text || !len) return TKSMSEQ_EINVAL;
     *text = nullptr; *len = 0;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     const uint64_t n = b->n_reads;
-    std::vector<uint32_t> reads(2 * n), ivs(4 * (b->n_intervals + 1)), mods(2 * b->n_mods), ids(2 * n), dup;
-    std::vector<uint64_t> lits(2 * b->n_literals);
-    std::vector<char> lpool(b->litpool.cap), idpool(b->idpool.cap);
-    HIPCHK(ctx, hipMemcpyAsync(reads.data(), b->reads.p, n * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(ivs.data(), b->intervals.p, (b->n_intervals + 1) * 16, hipMemcpyDeviceToHost, s));
-    if (b->n_mods) HIPCHK(ctx, hipMemcpyAsync(mods.data(), b->mods.p, b->n_mods * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(ids.data(), b->ids.p, n * 8, hipMemcpyDeviceToHost, s));
-    if (b->n_literals) HIPCHK(ctx, hipMemcpyAsync(lits.data(), b->literals.p, b->n_literals * 16, hipMemcpyDeviceToHost, s));
-    if (!lpool.empty()) HIPCHK(ctx, hipMemcpyAsync(lpool.data(), b->litpool.p, lpool.size(), hipMemcpyDeviceToHost, s));
-    if (!idpool.empty()) HIPCHK(ctx, hipMemcpyAsync(idpool.data(), b->idpool.p, idpool.size(), hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
+    HostTables H;
+    const int rc = H.fetch(ctx, b, HostTables::SEGMENTS | HostTables::MODS | HostTables::IDS);
+    if (rc) return rc;
+    const auto &reads = H.reads, &ivs = H.ivs, &mods = H.mods, &ids = H.ids;
+    const auto& idpool = H.idpool;
     // One molecule per read, depth 1: what every C++ module of the reference writes after reading with unroll = true
     // (copies of a depth > 1 molecule are named id_0, id_1, ...: src/mdf.h:97-105).  print_tsv: "+id<TAB>depth<TAB>comment".
     // The reads are formatted in contiguous shares, one per host thread (tksmseq_set_host_threads), and the shares copied into
@@ -900,8 +896,7 @@ int tksmseq_batch_to_mdf_text(tksmseq_ctx* ctx, const tksmseq_batch* b, char** t
             const uint32_t ib = reads[2 * r], ic = reads[2 * r + 1];
             for (uint32_t i = 0; i < ic; i++) {
                 const uint32_t* iv = ivs.data() + 4 * (size_t)(ib + i);
-                if (iv[0] >> 31) { const uint32_t li = iv[0] & 0x7fffffffu; out.append(lpool.data() + lits[2 * (size_t)li], (size_t)lits[2 * (size_t)li + 1]); }
-                else out += ctx->contig_names[iv[0]];
+                H.append_contig(ctx, iv[0], out);
                 out += '\t'; put_u32(out, iv[1]); out += '\t'; put_u32(out, iv[2]); out += '\t';
                 out += (iv[3] >> 31) ? '-' : '+';
                 out += '\t';
