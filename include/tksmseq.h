@@ -17,24 +17,23 @@
  * TKSMSEQ_EDEVICE when no device is usable.
  *
  * Environment.  Results never depend on any of these: they choose between kernel variants that produce the same bytes (the GPU tests
- * use them to reach every variant) or print diagnostics.  Read when a context is created unless noted.
+ * use them to reach every variant) or print diagnostics.  Read when a context is created unless noted.  This list names everything the library reads.
  *   TKSM_MODELS            colon list of model directories searched after the built-in one (src/sequence.cpp:38-52, py/sequence.py:17-31)
  *   TKSMSEQ_BUILTIN_MODELS the built-in model directory (default: models/ next to the library)
  *   TKSMSEQ_VERBOSE=1|2    per-run statistics on stderr (rounds, slow-path reads, full-width redo jobs, alignment fall-backs by reason);
- *                          2: per-batch stage times as well (also read by the CLI)
+ *                          2: per-batch stage times as well (also read by the CLI).  Read at the start of every run
  *   TKSMSEQ_FORCE_SLOW=1   every read through the exact wave-wide kernel (k_simulate) instead of the fast pipeline
  *   TKSMSEQ_SMALL_ALN=N    rounds with at most N alignment jobs store all 64 band rows in one launch (default 131072; 0: always the
  *                          14-row pass + redo list)
- *   TKSMSEQ_SMALL_ROUND=N  (round 1's launch grouping; kept for the tests) rounds below N reads are launched merged (default 16384)
  *   TKSMSEQ_WAVE_LOOP=N    rounds with at most N reads left run the error loop one wave per read (k_loopw; default 16384, 0: never)
  *   TKSMSEQ_TAIL_WAVE=N    once at most N reads are left (and each can have a wave of its own at once) they finish in ONE launch that runs
  *                          every remaining visit of a read on one wave, alignments included (k_loopw<true>; default 4096, 0: never)
- *   TKSMSEQ_LOOP_WL=W      words (16 bases each) of a read's packed fragment that k_loop keeps in LDS per lane (default 64, multiple of 4)
+ *   TKSMSEQ_LOOP_WL=W      words (16 bases each) of a read's packed fragment that k_loop keeps in LDS per lane (default 64, multiple of 4);
+ *                          read once per process, at the first k_loop launch
  *   TKSMSEQ_EARLY_TAIL=N   at most N reads whose length x (1 - target identity) exceeds 4 x the batch's median get their straggler waves at
  *                          round 0, on a stream of their own underneath the regular rounds (default 1024, at most 4096; 0: never)
  *   TKSMSEQ_TAIL_WCAP=C    columns of a window the straggler kernel aligns on its wave (default and maximum 2048; a wider window takes the
  *                          regular route for that visit; the tests force that with a small value)
- *   TKSMSEQ_ALN_LDS_PAD=B  bytes of LDS the 14-row alignment pass asks for without using them: caps its waves per CU (default 0)
  *   TKSMSEQ_HBM_STATE_LEN=L fragments longer than L are edited in HBM by the last visit instead of being staged in LDS (default 2304)
  *   TKSMSEQ_DEFER_LEN=L    reads longer than L wait with their q-score alignment until the regular rounds are over (default 0: all)
  *   TKSMSEQ_BUCKETS=N      length buckets of the last visit's launches (default 16)
@@ -45,6 +44,7 @@
  *                          written) and, summed over the threads of a stage, of parsing, running, device-side staging copies, waiting for
  *                          device-to-host pieces, write calls, waiting for the writer, reading + counting (bench.py's end-to-end leg)
  *   TKSMSEQ_PIECE_BYTES=B  (CLI) size of the page-locked pieces a batch's records pass through (default 64 MB; the tests use 4 KB)
+ *   TKSMSEQ_LIB=NAME       (Python package) file name of the library to load instead of libtksmseq.so, next to it: diagnostic builds
  *   TKSMSEQ_ABLATE=N       only in the diagnostic build (`make ablate`, -DTKSM_ABLATE): timing experiments on the last visit's q-score loop
  *                          (40 - 45, tools/ablate_err.sh) and k_loop's prologue (33)
  *   GPU_MAX_HW_QUEUES      (HIP runtime) the CLI and bench.py set 16 when unset: a hardware queue per context in flight -- INTEGRATION.md

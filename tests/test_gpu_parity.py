@@ -146,7 +146,7 @@ def test_badread_bit_exact_vs_oracle(oracle_models, po, monkeypatch, mean_len, n
     if path == "fast-tail-narrow":
         monkeypatch.setenv("TKSMSEQ_TAIL_WCAP", "700")
     if path in ("fast", "fast-hbm"):
-        monkeypatch.setenv("TKSMSEQ_SMALL_ALN", "0"); monkeypatch.setenv("TKSMSEQ_SMALL_ROUND", "0"); monkeypatch.setenv("TKSMSEQ_TAIL_CUT", "0")
+        monkeypatch.setenv("TKSMSEQ_SMALL_ALN", "0"); monkeypatch.setenv("TKSMSEQ_TAIL_CUT", "0")
         monkeypatch.setenv("TKSMSEQ_WAVE_LOOP", "0")
     if path == "fast-hbm":          # the long-read variant of k_err (fragment state edited in HBM) for every length
         monkeypatch.setenv("TKSMSEQ_HBM_STATE_LEN", "0")
@@ -362,7 +362,7 @@ def test_full_size_properties_and_shard_invariance():
     # 16-row predecessor codes + follow-up passes, k_loopw in the late rounds, the launch grouping and the tail hand-over to the
     # wave-wide kernel do not change a byte
     with pytest.MonkeyPatch.context() as mp:
-        mp.setenv("TKSMSEQ_SMALL_ALN", str(1 << 30)); mp.setenv("TKSMSEQ_SMALL_ROUND", str(1 << 30)); mp.setenv("TKSMSEQ_TAIL_CUT", "0")
+        mp.setenv("TKSMSEQ_SMALL_ALN", str(1 << 30)); mp.setenv("TKSMSEQ_TAIL_CUT", "0")
         mp.setenv("TKSMSEQ_WAVE_LOOP", "0"); mp.setenv("TKSMSEQ_TAIL_WAVE", "0")
         s3 = Sequencer(0)
     setup(s3)
@@ -642,7 +642,7 @@ def test_tail_noise_bit_exact_vs_oracle(oracle_models, po, monkeypatch, path):
     same batch rebuilds the batch's lengths and order; symbols outside ACGT in `bases` take the wave-wide kernel."""
     monkeypatch.setenv("TKSMSEQ_FORCE_SLOW", "1" if path == "slow" else "0")
     if path == "fast":
-        monkeypatch.setenv("TKSMSEQ_SMALL_ALN", "0"); monkeypatch.setenv("TKSMSEQ_SMALL_ROUND", "0"); monkeypatch.setenv("TKSMSEQ_WAVE_LOOP", "0"); monkeypatch.setenv("TKSMSEQ_TAIL_WAVE", "0")
+        monkeypatch.setenv("TKSMSEQ_SMALL_ALN", "0"); monkeypatch.setenv("TKSMSEQ_WAVE_LOOP", "0"); monkeypatch.setenv("TKSMSEQ_TAIL_WAVE", "0")
     import json
     s, ref, rs = _random_genome_seqr()
     s.set_identity(84.0, 99.0, 5.5)
@@ -832,7 +832,7 @@ def test_config3_and_config5_workloads_bit_exact_vs_oracle(seqr, po, oracle_mode
     and --perfect): `pcr` = substitution-heavy molecules as 20 PCR cycles leave them (BASELINE config 5: ~5 substitutions per kb,
     both strands, interval ends), `scrna` = barcode + UMI + polyA literal segments (config 3).  Run as the large rounds of a large
     batch are (k_loop in every round; 16 stored rows per alignment: 5 % of the polyA-tailed jobs go on to the 64-row pass)."""
-    monkeypatch.setenv("TKSMSEQ_SMALL_ALN", "0"); monkeypatch.setenv("TKSMSEQ_SMALL_ROUND", "0"); monkeypatch.setenv("TKSMSEQ_WAVE_LOOP", "0"); monkeypatch.setenv("TKSMSEQ_TAIL_WAVE", "0")
+    monkeypatch.setenv("TKSMSEQ_SMALL_ALN", "0"); monkeypatch.setenv("TKSMSEQ_WAVE_LOOP", "0"); monkeypatch.setenv("TKSMSEQ_TAIL_WAVE", "0")
     from tksm_amd import synthetic
     rs = np.random.RandomState(17)
     lens = [200_000, 150_000]

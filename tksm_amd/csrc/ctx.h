@@ -1,10 +1,11 @@
-// ctx.h -- internal: the context and batch objects behind the opaque handles of include/tksmseq.h (shared by api.cpp and
-// mdf_ops.cpp).
+// ctx.h -- internal: the context and batch objects behind the opaque handles of include/tksmseq.h (shared by api.cpp, run.cpp
+// and mdf_ops.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <chrono>
 
 #include <algorithm>
+#include <cstdlib>
 #include <map>
 #include <mutex>
 #include <string>
@@ -139,6 +140,55 @@ struct TmpBuf : DevBuf {
     explicit TmpBuf(hipStream_t s) { pooled = true; pool_stream = s; }
 };
 
+// page-locked host memory that grows (with as much again as headroom) and goes with its owner
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        release();
+        const hipError_t e = hipHostMalloc(&p, bytes * 2, hipHostMallocDefault);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        cap = bytes * 2;
+        return hipSuccess;
+    }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+    ~PinnedBuf() { release(); }
+    template <class T> T* as() const { return (T*)p; }
+};
+
+// A stream for work that runs underneath a context's main stream, with the two events that order it against the main stream; created
+// on first use.  fork_from(main): what is launched on `stream` next starts after everything queued on main so far; launched(): marks
+// the end of that work; join_into(main): main waits for it.  `used`: set by launched(), cleared by whoever starts a new run.
+struct HelperStream {
+    hipStream_t stream = nullptr;
+    hipEvent_t start = nullptr, done = nullptr;
+    bool used = false;
+    hipError_t fork_from(hipStream_t main) {
+        hipError_t e = stream ? hipSuccess : hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+        for (hipEvent_t* ev : {&start, &done}) if (e == hipSuccess && !*ev) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(start, main);
+        if (e == hipSuccess) e = hipStreamWaitEvent(stream, start, 0);
+        return e;
+    }
+    hipError_t launched() { const hipError_t e = hipEventRecord(done, stream); used = used || e == hipSuccess; return e; }
+    hipError_t wait_done() { return hipEventSynchronize(done); }              // the host waits for the work marked by launched()
+    hipError_t join_into(hipStream_t main) { return hipStreamWaitEvent(main, done, 0); }
+    bool idle() const { return !used || hipEventQuery(done) == hipSuccess; }
+    hipError_t synchronize() { return stream ? hipStreamSynchronize(stream) : hipSuccess; }
+    ~HelperStream() {
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+        for (hipEvent_t ev : {start, done}) if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
+// positions in tksmseq_ctx::last_diag (tksmseq_run_diagnostics): the order in which Sequencer.run_diagnostics (sequence.py) names them
+enum RunDiag {
+    DIAG_ROUNDS, DIAG_EXACT_KERNEL_READS, DIAG_PREDICTED_STRAGGLERS, DIAG_JOBS_14_ROW_ROUNDS, DIAG_JOBS_REDONE_FULL_WIDTH, DIAG_FALLBACKS,
+    DIAG_FALLBACK_REASONS, DIAG_FALLBACKS_QSCORE_JOBS, DIAG_FALLBACKS_LIST_PASS, DIAG_JOBS_ALL_ROUNDS, DIAG_BAND_EXITS,
+    DIAG_WORDS = 16
+};
+
 struct tksmseq_batch {
     uint64_t n_reads = 0, n_intervals = 0, n_mods = 0, n_literals = 0;
     DevBuf reads, intervals, mods, literals, litpool, ids, idpool;
@@ -170,16 +220,9 @@ struct tksmseq_ctx : ContigLookup {
     // wave-wide kernel for the reads that cannot take the fast pipeline, underneath the rounds: a few streams, each with
     // its own slice of the per-wave trace buffer, so that launches for reads found in different rounds overlap
     static constexpr int N_SIDE = 4, SIDE_WAVES = 512;
-    hipStream_t side[N_SIDE] = {};
-    hipEvent_t side_start = nullptr, side_done[N_SIDE] = {};
-    bool side_used[N_SIDE] = {};
-    // predicted stragglers: their straggler-kernel launch runs on a stream of its own from round 0 on (api.cpp)
-    hipStream_t early_stream = nullptr;
-    hipEvent_t early_start = nullptr, early_done = nullptr;
-    // the wide alignment passes on a stream of their own priority (TKSMSEQ_ALN_STREAM_PRIORITY; api.cpp)
-    hipStream_t aln_stream = nullptr;
-    hipEvent_t aln_start = nullptr, aln_done = nullptr;
-    int aln_prio_set = 0, aln_prio = 0;
+    HelperStream side[N_SIDE];
+    // predicted stragglers: their straggler-kernel launch runs on a stream of its own from round 0 on (run.cpp)
+    HelperStream early;
     uint32_t early_tail = 1024;           // at most this many reads (and only from a batch with a long tail of predicted visits); 0: never
     DevBuf f_early;
     bool own_stream = false;
@@ -211,26 +254,23 @@ struct tksmseq_ctx : ContigLookup {
         w_scratch, w_records, w_istats, w_dstats, w_sums, w_fullpool, w_biglist, w_bigscratch, w_bigtrace;
     unsigned long long full_pool_bytes = 1ull << 30;
     // fast Badread pipeline state (see kernels.h FastBuffers)
-    DevBuf f_state, f_frag, f_nb, f_fplanes, f_jmeta[2], f_redo, f_jpopd[2], f_trace, f_tracefull, f_slow, f_defer, f_defercnt, f_frag2, f_row64;
+    DevBuf f_state, f_frag, f_nb, f_fplanes, f_jmeta[2], f_redo, f_jpopd, f_trace, f_tracefull, f_slow, f_defer, f_defercnt, f_frag2, f_row64;
     std::vector<uint32_t> h_row64;        // host copy of the state-row offsets of the current run
     // what the host and the device exchange in every round, in one copy each way: f_round = {job counts of the even rounds,
     // counters, job counts of the odd rounds} -> h_round; h_geo = {prefix, bases, range geometry} -> f_geoall (page-locked)
     DevBuf f_round, f_geoall;
-    uint32_t* h_round = nullptr; size_t h_round_bytes = 0;
-    uint8_t* h_geo = nullptr; size_t h_geo_bytes = 0;
+    PinnedBuf h_round, h_geo;
     bool force_slow = false;
     uint32_t tail_cut = 0;   // > 0: hand the last reads of a batch to the wave-wide kernel (diagnostic)
     int tail_wcap = 2048;                 // columns of a re-estimation window the straggler kernel aligns itself (its LDS holds 2048; smaller: tests)
     uint32_t tail_wave = 4096;            // rounds with at most this many reads left: one launch that runs every remaining visit of a read on a wave of its own (k_loopw<true>); 0: never
     uint32_t wave_loop = 16384;           // rounds with at most this many reads left run the error loop one wave per read (k_loopw)
-    unsigned aln_lds_pad = 0;             // LDS the first alignment pass asks for without using it: caps its waves per CU (kernels.hip launch_aln)
-    uint32_t small_round = 16384, small_aln = 131072;   // rounds with fewer reads are latency-bound: merged launches, full-width alignment
+    uint32_t small_aln = 131072;          // rounds with at most this many alignment jobs are latency-bound: every job with all 64 rows in one launch
     uint32_t n_buckets = 16;
     int defer_len = 0;          // reads longer than this align for their q-scores after the regular rounds, all together
     int hbm_state_len = 2304;   // fragments longer than this are edited in HBM instead of being staged in LDS every round
     std::vector<hipEvent_t> evpool;
-    uint32_t last_rounds = 0, last_slow = 0, last_early = 0;
-    uint32_t last_diag[16] = {};      // tksmseq_run_diagnostics
+    uint32_t last_diag[DIAG_WORDS] = {};  // tksmseq_run_diagnostics, indexed by RunDiag
     void* user_out = nullptr; uint64_t user_out_cap = 0;
     bool timing = false;
     int host_threads = 1;       // host threads for MDF parsing (tksmseq_set_host_threads)
@@ -251,3 +291,6 @@ struct tksmseq_ctx : ContigLookup {
 
 // a batch whose tables were written on the device (PCR, truncation): lengths, sorted order and sizing on the host
 int finalize_device_batch(tksmseq_ctx* ctx, tksmseq_batch* b);
+
+// TKSMSEQ_VERBOSE: 0 when unset, otherwise at least 1
+inline int verbose_level() { const char* v = getenv("TKSMSEQ_VERBOSE"); return v ? std::max(1, atoi(v)) : 0; }

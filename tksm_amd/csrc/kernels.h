@@ -144,6 +144,34 @@ struct RangeGeo {
     uint32_t pad;
 };
 
+// Slots of FastBuffers::counters: 32 words that sit between the two sets of per-range job counts in one buffer, zeroed at the start
+// of a run and copied to the host with every round (run.cpp reads them as cnt[...]; tksmseq_run_diagnostics reports some of them).
+// Plain int enumerators: they index the array next to run-time ints (CNT_EXIT + cause).
+enum Counter {
+    CNT_JOBS = 0,          // host copy only: the jobs of this round, summed over fb.job_cnt (the device never writes it)
+    CNT_DEFERRED = 1,      // reads on defer_list
+    CNT_SLOW = 2,          // reads on slow_list: they take the exact wave-wide kernel
+    CNT_FULL_ROWS = 3,     // rows taken from the full-width pool (trace_full) in this round; k_round_reset zeroes it
+    CNT_EXIT = 4,          // [4 + ExitCause] reads that left the fast pipeline, by cause
+    CNT_REDO_JOBS = 8,     // diagnostics: jobs redone with all 64 rows, summed over the rounds ...
+    CNT_REDO_WAVES = 9,    // ... and the waves they took
+    CNT_REDO_LIST = 10,    // jobs on redo_list in this round; k_round_reset zeroes it
+    CNT_FAIL = 12,         // fused alignment (k_alnf) failures: their number, ...
+    CNT_FAIL_OR = 13,      // ... their reason bits or-ed, ...
+    CNT_FAIL_LAST = 14,    // ... the last one's reason bits ...
+    CNT_FAIL_NM = 15,      // ... and its size: n | m << 16
+    CNT_FAIL_REASON = 16,  // [16 + FailBit] failures with that reason bit set
+    CNT_FAIL_QJOB = 24,    // failures among q-score jobs
+    CNT_FAIL_LIST = 25,    // failures in the pass over redo_list
+    CNT_EARLY_SLOW = 26,   // reads on early_slow
+    CNT_EARLY = 27,        // reads on early_list
+    CNT_WORDS = 32
+};
+// why a read left the fast pipeline: an alignment left the band (in an error loop / in the last visit), a window shift > 15 (likewise)
+enum ExitCause { EXIT_BAND_LOOP = 0, EXIT_SHIFT_LOOP = 1, EXIT_SHIFT_ERR = 2, EXIT_BAND_ERR = 3 };
+// reason bits of a fused alignment's failure: queue / reservoir overflow, shift > 31, shift > 14, end cell, walk
+enum FailBit { FAIL_QUEUE = 0, FAIL_SHIFT31 = 3, FAIL_SHIFT14 = 4, FAIL_END_CELL = 5, FAIL_WALK = 6 };
+
 struct FastBuffers {
     ReadState* state;                 // [n_reads]
     const uint32_t* row64;            // [n_reads + 1] first 64-position block of every read's state rows (ragged; kernels.hip frag_row ...)
@@ -156,11 +184,11 @@ struct FastBuffers {
     uint8_t* job_popd;                // [n_reads][ncap] per read position: op | D-run << 2 (q-score jobs)
     void* trace;                      // predecessor codes of the first alignment pass (14 band rows + the column's shift: 4 bytes per iteration):
                                       // 64-byte lines of 16 iterations, per range [wave][line][lane] (RangeGeo::trace_off / tstride)
-    uint32_t* redo_list;              // jobs whose path left the stored rows of pass 1 (counters[10] of them): 64-row pass
-    void* trace_full;                 // pool of the passes that store all 64 rows (16 bytes per iteration, 4 per line; shift bytes behind them): [wave][full_tg lines][lane]; counters[3] allocates
+    uint32_t* redo_list;              // jobs whose path left the stored rows of pass 1 (counters[CNT_REDO_LIST] of them): 64-row pass
+    void* trace_full;                 // pool of the passes that store all 64 rows (16 bytes per iteration, 4 per line; shift bytes behind them): [wave][full_tg lines][lane]; counters[CNT_FULL_ROWS] allocates
     uint32_t full_rows, full_tg;      // jobs the full-width pool holds (multiple of 64), lines per job (4 columns each)
     uint32_t full_cl;                 // fused alignment (k_alnf): of a job's full_tg lines the first full_cl hold codes, the shift bytes follow, the last one is spare
-    uint32_t* counters;               // [2] reads on the slow list, [3] rows taken from the full-width pool, [4..9] diagnostics, [10] jobs on redo_list
+    uint32_t* counters;               // [CNT_WORDS], see Counter
     uint32_t* job_cnt;                // [n_ranges] jobs of this round per range of rs reads, one counter per 128 B
     uint32_t rs, n_ranges;
     // previous round's job set (double buffered): its jobs are the list of reads that are still running
@@ -175,10 +203,10 @@ struct FastBuffers {
     // predicted stragglers (reads whose length x (1 - target identity) says they need several times the visits of the batch's median
     // read): their error loops run from round 0 on, a wave each, on a side stream underneath the regular rounds
     uint32_t* early_hist;             // [64][256] reads per score bin (k_init; 64 copies against contention), bin = 8 log2(1 + length x (1 - target))
-    uint2* early_list;                // {read, range}; counters[27] counts
-    uint32_t* early_slow;             // early reads that need the exact kernel; counters[26] counts (merged into slow_list after the side kernel)
+    uint2* early_list;                // {read, range}; counters[CNT_EARLY] counts
+    uint32_t* early_slow;             // early reads that need the exact kernel; counters[CNT_EARLY_SLOW] counts (merged into slow_list after the side kernel)
     // reads longer than defer_len wait (stage 3) with their q-score alignment until the regular rounds are over
-    uint2* defer_list;                // [n_reads] {read, range}; counters[1] counts
+    uint2* defer_list;                // [n_reads] {read, range}; counters[CNT_DEFERRED] counts
     uint32_t* defer_cnt;              // [n_ranges] per range, one counter per 128 B
     int defer_len;
 };
@@ -224,7 +252,7 @@ hipError_t launch_round_reset(const FastBuffers& fb, hipStream_t s);
 hipError_t launch_collect_unfinished(const FastBuffers& fb, uint64_t n_reads, hipStream_t s);
 // this round's alignment jobs (ids below n_jobs; per-range counts in fb.job_cnt): windows decoded from the slot codes and aligned, one
 // lane per job.  mode: 0 = the round's jobs are identity re-estimations, 1 = q-score alignments (all jobs of a round have one mode)
-hipError_t launch_alnf(const SimParams& p, const FastBuffers& fb, const SimBuffers& o, uint32_t n_jobs, bool full_only, int mode, unsigned lds_pad, hipStream_t s);
+hipError_t launch_alnf(const SimParams& p, const FastBuffers& fb, const SimBuffers& o, uint32_t n_jobs, bool full_only, int mode, hipStream_t s);
 hipError_t launch_perfect_lengths(const BatchView& b, const RefView& r, const SimParams& p, const SimBuffers& o, hipStream_t s);
 hipError_t launch_perfect(const BatchView& b, const RefView& r, const SimParams& p, const SimBuffers& o, const uint64_t* rec_off, uint8_t* records,
                           uint32_t max_raw, int n_cus, hipStream_t s);

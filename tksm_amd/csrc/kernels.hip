@@ -957,8 +957,8 @@ DEV int cdf_pick(const uint32_t* cdf32, uint32_t pself, uint32_t ptot, int na, u
 DEV void go_slow(const FastBuffers& FB, uint64_t r, int lane, int cause) {
     if (lane == 0) {
         FB.state[r].slow = 1;
-        atomicAdd(&FB.counters[4 + cause], 1u);            // diagnostics: 0/3 alignment left the band, 1/2 window shift > 15
-        const uint32_t idx = atomicAdd(&FB.counters[2], 1u);
+        atomicAdd(&FB.counters[CNT_EXIT + cause], 1u);            // diagnostics (ExitCause)
+        const uint32_t idx = atomicAdd(&FB.counters[CNT_SLOW], 1u);
         FB.slow_list[idx] = (uint32_t)r;
     }
 }
@@ -1116,7 +1116,7 @@ __global__ __launch_bounds__(256, 7) void k_init(BatchView B, RefView R, ErrMode
         S.st_draws = 0; S.st_aligns = 0; S.job = 0; S.raw_len = raw_len; S.res_mt = 0; S.res_cols = 0; S.res_fail = 0; S.pad3 = 0;
         FB.state[r] = S;
         O.status[r] |= status;
-        if (slow) { const uint32_t idx = atomicAdd(&FB.counters[2], 1u); FB.slow_list[idx] = (uint32_t)r; }
+        if (slow) { const uint32_t idx = atomicAdd(&FB.counters[CNT_SLOW], 1u); FB.slow_list[idx] = (uint32_t)r; }
         else if (FB.early_hist) atomicAdd(&FB.early_hist[(blockIdx.x & 63u) * 256u + early_bin(L, target)], 1u);    // (64 copies: a batch's reads fall into a dozen bins)
     }
 }
@@ -1293,8 +1293,8 @@ __global__ __launch_bounds__(64) void k_loop(ErrModelView EM, SimParams P, FastB
         if (S.res_fail) {
             // the alignment left the band representation: the read takes the byte-exact wave-wide kernel
             sp->slow = 1;
-            atomicAdd(&FB.counters[4], 1u);
-            FB.slow_list[atomicAdd(&FB.counters[2], 1u)] = r;
+            atomicAdd(&FB.counters[CNT_EXIT + EXIT_BAND_LOOP], 1u);
+            FB.slow_list[atomicAdd(&FB.counters[CNT_SLOW], 1u)] = r;
             act = false;
         } else {
             const double ident = cols ? (double)mt / (double)cols : 0.0;
@@ -1548,7 +1548,7 @@ __global__ __launch_bounds__(64) void k_loop(ErrModelView EM, SimParams P, FastB
         sp->stage = st == NEED_ALN ? 0 : 3;
         if (st == DONE) {
             atomicAdd(&FB.defer_cnt[rc * 32u], 1u);
-            FB.defer_list[atomicAdd(&FB.counters[1], 1u)] = make_uint2(r, rc);
+            FB.defer_list[atomicAdd(&FB.counters[CNT_DEFERRED], 1u)] = make_uint2(r, rc);
         }
     }
 }
@@ -1617,7 +1617,7 @@ __global__ __launch_bounds__(64) void k_loopw(ErrModelView EM, SimParams P, Fast
 #endif
     const bool early_mode = TAIL && from_jobs == 3;           // the predicted stragglers, from their list (side stream, from round 0 on)
     if (early_mode) {
-        if (widx >= FB.counters[27]) return;
+        if (widx >= FB.counters[CNT_EARLY]) return;
         const uint2 e = FB.early_list[widx];
         r = e.x; rc = e.y;
     } else if (!from_jobs) { r = order[begin + widx]; rc = (begin + widx) / FB.rs; }
@@ -1635,8 +1635,8 @@ __global__ __launch_bounds__(64) void k_loopw(ErrModelView EM, SimParams P, Fast
     // an early read never has a job, and its kernel runs beside the rounds (which read the slow list's counter): what it hands to the
     // exact kernel goes on a list of its own, merged after the side kernel has ended
     auto to_exact_kernel = [&]() {
-        if (!early_mode) { go_slow(FB, r, lane, 0); return; }
-        if (lane == 0) { sp->slow = 1; FB.early_slow[atomicAdd(&FB.counters[26], 1u)] = r; }
+        if (!early_mode) { go_slow(FB, r, lane, EXIT_BAND_LOOP); return; }
+        if (lane == 0) { sp->slow = 1; FB.early_slow[atomicAdd(&FB.counters[CNT_EARLY_SLOW], 1u)] = r; }
     };
     const int k = EM.k;
     const int L = S.raw_len + 2 * k;
@@ -1673,8 +1673,8 @@ __global__ __launch_bounds__(64) void k_loopw(ErrModelView EM, SimParams P, Fast
             // the alignment left the band representation: the read takes the byte-exact wave-wide kernel
             if (lane == 0) {
                 sp->slow = 1;
-                atomicAdd(&FB.counters[4], 1u);
-                FB.slow_list[atomicAdd(&FB.counters[2], 1u)] = r;
+                atomicAdd(&FB.counters[CNT_EXIT + EXIT_BAND_LOOP], 1u);
+                FB.slow_list[atomicAdd(&FB.counters[CNT_SLOW], 1u)] = r;
             }
             return;
         }
@@ -1854,7 +1854,7 @@ __global__ __launch_bounds__(64) void k_loopw(ErrModelView EM, SimParams P, Fast
         sp->stage = st == NEED_ALN ? 0 : 3;
         if (st == DONE) {
             atomicAdd(&FB.defer_cnt[rc * 32u], 1u);
-            FB.defer_list[atomicAdd(&FB.counters[1], 1u)] = make_uint2(r, rc);
+            FB.defer_list[atomicAdd(&FB.counters[CNT_DEFERRED], 1u)] = make_uint2(r, rc);
         }
     }
 }
@@ -1943,7 +1943,7 @@ __global__ __launch_bounds__(256, 8) void k_err(BatchView B, ErrModelView EM, Qs
     if (want_q) {
         // ---- S5 q-scores from the alignment k_aln left in job_popd (py/tksm_badread.py:607-655)
         const uint32_t mt = S.res_mt, cols = S.res_cols, fail = S.res_fail;
-        if (fail) { go_slow(FB, r, lane, 3); return; }
+        if (fail) { go_slow(FB, r, lane, EXIT_BAND_ERR); return; }
         identity = cols ? (double)mt / (double)cols : 0.0;
         const uint32_t rc1 = pos / FB.rs;
         const uint8_t* gp = FB.prev_popd + FB.geo_prev[rc1].popd_off + (size_t)(S.job - FB.base_prev[rc1]) * FB.geo_prev[rc1].ncap;
@@ -2064,7 +2064,7 @@ __global__ void k_collect_unfinished(FastBuffers FB, uint64_t n_reads) {
     ReadState S = FB.state[r];
     if (S.stage != 2 && !S.slow) {
         FB.state[r].slow = 1;
-        const uint32_t idx = atomicAdd(&FB.counters[2], 1u);
+        const uint32_t idx = atomicAdd(&FB.counters[CNT_SLOW], 1u);
         FB.slow_list[idx] = (uint32_t)r;
     }
 }
@@ -2516,9 +2516,9 @@ DEV void store_result_f(const FastBuffers& FB, uint32_t r, const AlnResF& R) {
 }
 
 // Alignment passes of a round (launch_alnf): pass 1 = every job with 14 stored rows (ROWS 14, LIST false); pass 2 = the jobs whose
-// path left them (counters[10] of them in redo_list) with all 64 rows, lines in the full-width pool: a fixed grid whose waves loop over
+// path left them (counters[CNT_REDO_LIST] of them in redo_list) with all 64 rows, lines in the full-width pool: a fixed grid whose waves loop over
 // the list.  Rounds with few jobs are bound by the latency of one lane's pass: all their jobs go straight to the 64-row version
-// (LIST false; counters[3] allocates pool lines per wave).
+// (LIST false; counters[CNT_FULL_ROWS] allocates pool lines per wave).
 // (register budget: the 14-row pass needs ~131 vector registers -- 3 waves per SIMD; forced into 128 it spills, and a spill inside
 // the pop's divergent region cost correct results once: never again below its natural size)
 constexpr int ALNF_WAVES = 4;
@@ -2552,7 +2552,7 @@ __global__ __launch_bounds__(64, ROWS == 64 ? 3 : ALNF_WAVES) ALNF_VGPR_CAP void
             const unsigned long long wm = __ballot(act);
             const uint32_t na = (uint32_t)__popcll(wm);
             uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&FB.counters[3], na);
+            if (lane == 0) base = atomicAdd(&FB.counters[CNT_FULL_ROWS], na);
             base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
             if (base + na > FB.full_rows) { norow = act; act = false; base = 0; }    // no pool lines left: reported as failures (the wave-wide kernel takes the reads)
             tg = (int)FB.full_tg;
@@ -2574,14 +2574,14 @@ __global__ __launch_bounds__(64, ROWS == 64 ? 3 : ALNF_WAVES) ALNF_VGPR_CAP void
         if (straight_to_list) { R.fail = false; R.needfull = true; R.overflow = false; }
         if (norow) { R.fail = true; R.needfull = false; R.overflow = false; }
         if (act && R.overflow) { job_overflow(FB, O, r); return; }
-        if (ROWS != 64) list_append(FB.redo_list, FB.counters + 10, act && R.needfull, job, lane);
+        if (ROWS != 64) list_append(FB.redo_list, FB.counters + CNT_REDO_LIST, act && R.needfull, job, lane);
         if ((act || norow) && !R.needfull) store_result_f(FB, r, R);
-        if (act && R.fail) { atomicAdd(&FB.counters[12], 1u); atomicOr(&FB.counters[13], R.why & 255u); FB.counters[14] = R.why; FB.counters[15] = (uint32_t)J.n | ((uint32_t)R.m << 16);
-              for (int b = 0; b < 8; b++) if ((R.why >> b) & 1u) atomicAdd(&FB.counters[16 + b], 1u); if (MODE) atomicAdd(&FB.counters[24], 1u); if (LIST) atomicAdd(&FB.counters[25], 1u); }
+        if (act && R.fail) { atomicAdd(&FB.counters[CNT_FAIL], 1u); atomicOr(&FB.counters[CNT_FAIL_OR], R.why & 255u); FB.counters[CNT_FAIL_LAST] = R.why; FB.counters[CNT_FAIL_NM] = (uint32_t)J.n | ((uint32_t)R.m << 16);
+              for (int b = 0; b < 8; b++) if ((R.why >> b) & 1u) atomicAdd(&FB.counters[CNT_FAIL_REASON + b], 1u); if (MODE) atomicAdd(&FB.counters[CNT_FAIL_QJOB], 1u); if (LIST) atomicAdd(&FB.counters[CNT_FAIL_LIST], 1u); }
     } else {
         static_assert(!LIST || ROWS == 64, "the list holds the jobs of the full-width pass");
-        const uint32_t n_list = FB.counters[10];
-        if (lane == 0 && blockIdx.x == 0 && n_list) { atomicAdd(&FB.counters[8], n_list); atomicAdd(&FB.counters[9], (n_list + 63u) / 64u); }   // diagnostics
+        const uint32_t n_list = FB.counters[CNT_REDO_LIST];
+        if (lane == 0 && blockIdx.x == 0 && n_list) { atomicAdd(&FB.counters[CNT_REDO_JOBS], n_list); atomicAdd(&FB.counters[CNT_REDO_WAVES], (n_list + 63u) / 64u); }   // diagnostics
         const uint32_t* list = FB.redo_list;
         const int tg = (int)FB.full_tg;
         uint4* trl = reinterpret_cast<uint4*>(FB.trace_full) + ((size_t)blockIdx.x * tg * 64 + (uint32_t)lane) * 4;
@@ -2597,8 +2597,8 @@ __global__ __launch_bounds__(64, ROWS == 64 ? 3 : ALNF_WAVES) ALNF_VGPR_CAP void
             const AlnResF R = aln_fused<MODE, ROWS>(J, trl, tg, (int)FB.full_cl, 256u, mcap);
             if (act && R.overflow) job_overflow(FB, O, r);
             else if (act) store_result_f(FB, r, R);
-            if (act && R.fail) { atomicAdd(&FB.counters[12], 1u); atomicOr(&FB.counters[13], R.why & 255u); FB.counters[14] = R.why; FB.counters[15] = (uint32_t)J.n | ((uint32_t)R.m << 16);
-              for (int b = 0; b < 8; b++) if ((R.why >> b) & 1u) atomicAdd(&FB.counters[16 + b], 1u); if (MODE) atomicAdd(&FB.counters[24], 1u); if (LIST) atomicAdd(&FB.counters[25], 1u); }
+            if (act && R.fail) { atomicAdd(&FB.counters[CNT_FAIL], 1u); atomicOr(&FB.counters[CNT_FAIL_OR], R.why & 255u); FB.counters[CNT_FAIL_LAST] = R.why; FB.counters[CNT_FAIL_NM] = (uint32_t)J.n | ((uint32_t)R.m << 16);
+              for (int b = 0; b < 8; b++) if ((R.why >> b) & 1u) atomicAdd(&FB.counters[CNT_FAIL_REASON + b], 1u); if (MODE) atomicAdd(&FB.counters[CNT_FAIL_QJOB], 1u); if (LIST) atomicAdd(&FB.counters[CNT_FAIL_LIST], 1u); }
         }
     }
 }
@@ -3109,13 +3109,13 @@ __global__ void k_mark_early(FastBuffers FB, const uint32_t* __restrict__ order,
     if (sp->stage != 0 || sp->slow) return;
     if (early_bin(sp->raw_len + 2 * k, sp->target) < min_bin) return;
     sp->early = 1;
-    FB.early_list[atomicAdd(&FB.counters[27], 1u)] = make_uint2(r, (uint32_t)(pos / FB.rs));
+    FB.early_list[atomicAdd(&FB.counters[CNT_EARLY], 1u)] = make_uint2(r, (uint32_t)(pos / FB.rs));
 }
 __global__ void k_merge_early_slow(FastBuffers FB) {
-    const uint32_t n = FB.counters[26];
-    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) FB.slow_list[FB.counters[2] + i] = FB.early_slow[i];
+    const uint32_t n = FB.counters[CNT_EARLY_SLOW];
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) FB.slow_list[FB.counters[CNT_SLOW] + i] = FB.early_slow[i];
     __syncthreads();
-    if (threadIdx.x == 0) { FB.counters[2] += n; FB.counters[4] += n; FB.counters[26] = 0u; }
+    if (threadIdx.x == 0) { FB.counters[CNT_SLOW] += n; FB.counters[CNT_EXIT + EXIT_BAND_LOOP] += n; FB.counters[CNT_EARLY_SLOW] = 0u; }
 }
 hipError_t launch_mark_early(const FastBuffers& fb, const uint32_t* order, uint64_t n_reads, int k, uint32_t min_bin, hipStream_t s) {
     hipLaunchKernelGGL(k_mark_early, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, s, fb, order, n_reads, k, min_bin);
@@ -3146,7 +3146,7 @@ hipError_t launch_qjobs(const FastBuffers& fb, int k, uint32_t count, hipStream_
 __global__ void k_round_reset(uint32_t* __restrict__ job_cnt, uint32_t n_words, uint32_t* __restrict__ counters) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_words) job_cnt[i] = 0u;
-    if (i == 0) { counters[3] = 0u; counters[10] = 0u; }
+    if (i == 0) { counters[CNT_FULL_ROWS] = 0u; counters[CNT_REDO_LIST] = 0u; }
 }
 hipError_t launch_round_reset(const FastBuffers& fb, hipStream_t s) {
     const uint32_t n_words = fb.n_ranges * 32u;
@@ -3158,7 +3158,7 @@ hipError_t launch_collect_unfinished(const FastBuffers& fb, uint64_t n_reads, hi
     hipLaunchKernelGGL(k_collect_unfinished, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, s, fb, n_reads);
     return hipGetLastError();
 }
-hipError_t launch_alnf(const SimParams& p, const FastBuffers& fb, const SimBuffers& o, uint32_t n_jobs, bool full_only, int mode, unsigned lds_pad, hipStream_t s) {
+hipError_t launch_alnf(const SimParams& p, const FastBuffers& fb, const SimBuffers& o, uint32_t n_jobs, bool full_only, int mode, hipStream_t s) {
     if (!n_jobs) return hipSuccess;
     const uint32_t waves = (n_jobs + 63) / 64;
     if (full_only) {
@@ -3168,10 +3168,10 @@ hipError_t launch_alnf(const SimParams& p, const FastBuffers& fb, const SimBuffe
     }
     const uint32_t g2 = std::max<uint32_t>(1u, std::min<uint32_t>((waves + 7) / 8, std::max<uint32_t>(1u, fb.full_rows / 64)));
     if (mode) {
-        hipLaunchKernelGGL((k_alnf<1, 14, false>), dim3(waves), dim3(64), lds_pad, s, p, fb, o, n_jobs);
+        hipLaunchKernelGGL((k_alnf<1, 14, false>), dim3(waves), dim3(64), 0, s, p, fb, o, n_jobs);
         hipLaunchKernelGGL((k_alnf<1, 64, true>), dim3(g2), dim3(64), 0, s, p, fb, o, n_jobs);
     } else {
-        hipLaunchKernelGGL((k_alnf<0, 14, false>), dim3(waves), dim3(64), lds_pad, s, p, fb, o, n_jobs);
+        hipLaunchKernelGGL((k_alnf<0, 14, false>), dim3(waves), dim3(64), 0, s, p, fb, o, n_jobs);
         hipLaunchKernelGGL((k_alnf<0, 64, true>), dim3(g2), dim3(64), 0, s, p, fb, o, n_jobs);
     }
     return hipGetLastError();

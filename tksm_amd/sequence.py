@@ -426,6 +426,7 @@ class Sequencer:
         """counts of the last Badread run (tksmseq_run_diagnostics): rounds, reads that took the exact kernel, redo share, fall-backs"""
         out = (C.c_uint32 * 16)()
         self._chk(self._lib.tksmseq_run_diagnostics(self._ctx, out))
+        # the positions are those of enum RunDiag (csrc/ctx.h), which run.cpp fills by name
         keys = ("rounds", "exact_kernel_reads", "predicted_stragglers", "jobs_14_row_rounds", "jobs_redone_full_width", "fallbacks",
                 "fallback_reasons", "fallbacks_qscore_jobs", "fallbacks_list_pass", "jobs_all_rounds", "band_exits")
         return {k: int(out[i]) for i, k in enumerate(keys)}
