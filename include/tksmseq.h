@@ -503,6 +503,52 @@ typedef struct {
 } tksmseq_wgs_progress;
 int tksmseq_wgs(tksmseq_ctx* ctx, const tksmseq_wgs_params* params, tksmseq_batch** out, tksmseq_wgs_progress* progress);
 
+/* ---- model-truncation: the KDE truncation model built on the device ---------------------------------------------------------------------
+ * Replaces py/truncate_kde.py (behind src/model_truncation.cpp), which needs scikit-learn: the 2-D model that tksmseq_truncate's KDE mode
+ * and `tksm truncate --kde-model` read.
+ *
+ * tksmseq_kde_grid replaces KernelDensity(bandwidth).fit(xy).score_samples + exp (ComputeKDELikelihoods, :245-287; also the grid of
+ * KDE_noise_generator.from_data, py/tksm_badread.py:888-901): out[i * gy + j] = 1 / (n 2 pi h^2) sum over the samples of
+ * exp(-((x - px[i])^2 + (y - py[j])^2) / 2 h^2), the EXACT Gaussian density in the linear domain (scikit-learn's tree is approximate in
+ * the tails: DESIGN.md section 7).  xy[n][2], px[gx], py[gy] and out are host arrays; the axis points are arbitrary doubles.  The sum is
+ * one fp64 matrix product over chunks of samples whose partial grids are added in chunk order: the same input gives the same bytes on
+ * every run.  TKSMSEQ_EINVAL: bandwidth <= 0 or non-finite, n = 0, an empty axis, a coordinate that is not finite (or above 1e150);
+ * TKSMSEQ_ELIMIT: gx or gy above 4096, n >= 2^31.
+ *
+ * tksmseq_kde_cv_bandwidth replaces CV_KDE_bandwidth (:223-242), made reproducible: for repeat r = 0, 1, 2, cv_samples indices are drawn
+ * WITH replacement as umul64hi(x << 32 | y, n), (x, y) the first words of Philox(seed, draw t, stream 48, r); the draw is cut into three
+ * contiguous folds (KFold(3): the first cv_samples % 3 one longer); for each bandwidth of 50, 150, ..., 950 the score is the mean over
+ * the folds of the sum over a fold's points of the exact log density of the other two folds; the repeat's bandwidth is the first maximum,
+ * *bandwidth the median of the three.  scores (may be NULL): [3][10] mean scores.  TKSMSEQ_EINVAL: n = 0, cv_samples < 3, a coordinate
+ * that is not finite; TKSMSEQ_ELIMIT: n >= 2^31, cv_samples above 2^24.
+ *
+ * tksmseq_model_truncation is main() of the script (:323-352): reads the primary alignments (lines with tp:A:P) of a PAF -- default: pairs
+ * (truncation length = tstart + tlen - tend, tlen); model_lengths: (tlen, tend - tstart) -- and the end ratios, searches the bandwidth if
+ * params->bandwidth <= 0, evaluates the grid at the cell centres (idx[k] + idx[k + 1]) // 2 of idx = arange(grid_start, grid_end + 1,
+ * grid_step), and writes printModelJson's file (:298-320): KDE_mtx (data = P.T flattened, labels idx[1:] twice) and the 100-bin end_mtx
+ * (np.histogram over np.arange(0, 1.01, 0.01); end_ratio != -1 replaces every ratio first).  The file is written under a temporary name
+ * and renamed: a failure leaves nothing behind.  TKSMSEQ_EINVAL: fewer than two grid indices, an end ratio outside [0, 1] that is not
+ * -1, a malformed PAF line, no primary alignment; TKSMSEQ_EIO: the PAF cannot be read or the output not written; TKSMSEQ_ELIMIT: more
+ * than 4096 cells per axis. */
+typedef struct tksmseq_kde_model_params {
+    uint64_t seed;                   /* -s/--seed: the bandwidth search's draws */
+    uint64_t cv_samples;             /* --cv-samples (100000) */
+    double bandwidth;                /* -b/--bandwidth (100); <= 0: cross-validated search */
+    int64_t grid_start, grid_end, grid_step;   /* --grid-start (0), --grid-end (10000), --grid-step (100) */
+    int32_t model_lengths;           /* --model-lengths */
+    int32_t reserved;
+    double end_ratio;                /* --end-ratio (-1: from the PAF) */
+} tksmseq_kde_model_params;
+int tksmseq_kde_grid(tksmseq_ctx* ctx, const double* xy, uint64_t n, const double* px, uint32_t gx, const double* py, uint32_t gy,
+                     double bandwidth, double* out);
+int tksmseq_kde_cv_bandwidth(tksmseq_ctx* ctx, const double* xy, uint64_t n, uint64_t seed, uint64_t cv_samples, double* bandwidth,
+                             double* scores /* [3][10] or NULL */);
+int tksmseq_model_truncation(tksmseq_ctx* ctx, const tksmseq_kde_model_params* params, const char* paf_path, const char* out_path);
+/* `tksm model-truncation` (src/model_truncation.cpp, py/truncate_kde.py:36-112): -i, -o, -b, --grid-start, --grid-end, --grid-step,
+ * --model-lengths, --end-ratio, -t (accepted, ignored), --list; here also -s, --cv-samples, --devices (the first entry is used), --verbosity,
+ * --log-file.  Exit codes as argparse: 2 for a missing -i / -o or an unknown option, 1 for everything that fails later. */
+int tksmseq_model_truncation_main(int argc, char** argv);
+
 /* The batch as MDF text, the way molecule_descriptor::operator<< writes it (src/interval.h:898-905): "+id<TAB>depth<TAB>comment",
  * then "chr<TAB>start<TAB>end<TAB>strand<TAB>pos<base>,..." per segment; depth 1 per molecule; comments re-serialised key-sorted
  * like dump_comment (:880-890).  *text is malloc'ed: release with tksmseq_text_free. */

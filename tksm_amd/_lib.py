@@ -107,6 +107,15 @@ class NoiseParams(C.Structure):              # tksmseq_noise_params
 NOISE_NORMAL, NOISE_LOGNORMAL = 0, 1
 NOISE_DISTS = {"normal": NOISE_NORMAL, "lognormal": NOISE_LOGNORMAL}
 
+class KdeModelParams(C.Structure):           # tksmseq_kde_model_params
+    _fields_ = [("seed", C.c_uint64), ("cv_samples", C.c_uint64), ("bandwidth", C.c_double), ("grid_start", C.c_int64),
+                ("grid_end", C.c_int64), ("grid_step", C.c_int64), ("model_lengths", C.c_int32), ("reserved", C.c_int32),
+                ("end_ratio", C.c_double)]
+
+
+KDE_CHUNK = 4096                             # samples per partial grid of tksmseq_kde_grid (kde_kernels.h; doubled for large inputs)
+KDE_BANDWIDTHS = tuple(range(50, 1000, 100))
+
 SYMBOLS = [
     "tksmseq_create", "tksmseq_destroy", "tksmseq_last_error", "tksmseq_version", "tksmseq_set_stream",
     "tksmseq_synchronize", "tksmseq_reference_add_fasta", "tksmseq_reference_add_contig",
@@ -125,6 +134,7 @@ SYMBOLS = [
     "tksmseq_gzip_copy_device", "tksmseq_gzip_eof",
     "tksmseq_reference_declare_contig", "tksmseq_wgs", "tksmseq_random_wgs_main",
     "tksmseq_append_noise", "tksmseq_tail_noise_main",
+    "tksmseq_kde_grid", "tksmseq_kde_cv_bandwidth", "tksmseq_model_truncation", "tksmseq_model_truncation_main",
 ]
 
 _lib = None
@@ -206,6 +216,10 @@ def load():
         "tksmseq_random_wgs_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
         "tksmseq_append_noise": (C.c_int, [vp, vp, P(NoiseParams), P(vp)]),
         "tksmseq_tail_noise_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
+        "tksmseq_kde_grid": (C.c_int, [vp, vp, u64, vp, C.c_uint32, vp, C.c_uint32, C.c_double, vp]),
+        "tksmseq_kde_cv_bandwidth": (C.c_int, [vp, vp, u64, u64, u64, P(C.c_double), vp]),
+        "tksmseq_model_truncation": (C.c_int, [vp, P(KdeModelParams), C.c_char_p, C.c_char_p]),
+        "tksmseq_model_truncation_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

@@ -13,6 +13,7 @@
 //   StrandMan_module        src/strand_man.cpp:20-124 -p/--flip-probability (outside [0, 1]: logged, not refused)
 //   RWGS_module             src/random_wgs.cpp:24-229 -r/--reference, --frag-len-dist "NAME A [B]", -o, --base-count | --depth
 //   AppendNoise_module      src/append_noise.cpp:131-229 --length-dist NAME,MU,SIGMA, --alphabet, --palindromic, --error-rate
+//   model-truncation        py/truncate_kde.py:36-112, :323-352 (behind src/model_truncation.cpp) PAF in, KDE model JSON out: no MDF, one context
 //   utility flags           src/module.h:75-104      -s/--seed (default 42), --verbosity, --log-file, -h
 // All stream: `truncate` and the four segment edits read the input in batches of whole molecules (--batch-bytes), `pcr` amplifies its templates in slices
 // of about --slice-molecules output molecules (tksmseq_pcr_params::template_begin / _end); the pieces go round the entries of
@@ -38,6 +39,7 @@
 
 #include "../../include/tksmseq.h"
 #include "host.h"
+#include "kde_host.h"
 #include "module_log.h"
 #include "sequencer_module.h"
 
@@ -674,4 +676,68 @@ extern "C" int tksmseq_random_wgs_main(int argc, char** argv) {
     return run_pieces(c, log, "random-wgs", prepare, next_piece, work, true, [&] {
         return ", " + std::to_string(st.bases) + " bases from " + std::to_string(st.next_candidate) + " candidates";
     });
+}
+
+// `tksm model-truncation`: the reference runs py/truncate_kde.py (argparse: a missing -i / -o and an unknown option exit with 2; --list
+// prints the option names and exits before anything is required).  One context on the first entry of --devices.
+extern "C" int tksmseq_model_truncation_main(int argc, char** argv) {
+    Common c;
+    tksmseq_kde_model_params p{};
+    p.bandwidth = 100.0; p.grid_start = 0; p.grid_end = 10000; p.grid_step = 100; p.end_ratio = -1.0; p.cv_samples = 100000;
+    bool list = false;
+    auto integer = [](const char* v, long long& out) { char* e = nullptr; out = strtoll(v, &e, 10); return e != v && !*e; };
+    auto real = [](const char* v, double& out) { char* e = nullptr; out = strtod(v, &e); return e != v && !*e; };
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            // (the common flags know --batch-bytes and --slice-molecules, which this module does not have)
+            if (o == "--batch-bytes" || o == "--slice-molecules") return NO_SUCH;
+            if (o == "--list") { list = true; return TOOK_FLAG; }
+            if (o == "--model-lengths") { p.model_lengths = 1; return TOOK_FLAG; }
+            long long iv = 0;
+            if ((o == "-b" || o == "--bandwidth") && v) { if (!real(v, p.bandwidth)) return MALFORMED; }
+            else if (o == "--end-ratio" && v) { if (!real(v, p.end_ratio)) return MALFORMED; }
+            else if (o == "--grid-start" && v) { if (!integer(v, iv)) return MALFORMED; p.grid_start = iv; }
+            else if (o == "--grid-end" && v) { if (!integer(v, iv)) return MALFORMED; p.grid_end = iv; }
+            else if (o == "--grid-step" && v) { if (!integer(v, iv)) return MALFORMED; p.grid_step = iv; }
+            else if (o == "--cv-samples" && v) { if (!integer(v, iv) || iv < 3) return MALFORMED; p.cv_samples = (uint64_t)iv; }
+            else if ((o == "-t" || o == "--threads") && v) { if (!integer(v, iv)) return MALFORMED; }      // accepted, ignored: the device does the work
+            else return NOT_MINE;
+            return TOOK_VALUE;
+        })) return 2;
+    if (list) { printf("help\ninput\noutput\nbandwidth\ngrid_start\ngrid_end\ngrid_step\nthreads\nmodel_lengths\nlist\nend_ratio\nseed\ncv_samples\ndevices\nverbosity\nlog_file\n"); return 0; }
+    if (c.help) { printf("KDE computation module of truncation of transcriptomic long-reads using their cDNA mapping.\n"
+                         "usage: model-truncation -i INPUT.paf -o OUTPUT.json [-b BANDWIDTH] [--grid-start 0] [--grid-end 10000] [--grid-step 100] [--model-lengths]\n"
+                         "                        [--end-ratio R] [-t THREADS] [--list] [-s SEED] [--cv-samples 100000] [--devices D] [--verbosity L] [--log-file F]\n"
+                         "BANDWIDTH <= 0: chosen by 3-fold cross-validation over 50, 150, ..., 950 on --cv-samples draws (seeded by -s)\n"); return 0; }
+    if (c.input.empty() || c.output.empty()) {
+        fprintf(stderr, "model-truncation: error: the following arguments are required: %s%s%s\n", c.input.empty() ? "-i/--input" : "",
+                c.input.empty() && c.output.empty() ? ", " : "", c.output.empty() ? "-o/--output" : "");
+        return 2;
+    }
+    if (p.end_ratio != -1.0 && !(p.end_ratio >= 0.0 && p.end_ratio <= 1.0)) { fprintf(stderr, "Error: --end-ratio must be -1 or between 0 and 1\n"); return 1; }
+    Logger log;
+    if (!open_log(c, "model-truncation", log)) return 1;
+    p.seed = (uint64_t)c.seed;
+    log.log(Logger::INFO, "Reading %s", c.input.c_str());
+    log.log(Logger::INFO, p.model_lengths ? "Modelling read lengths" : "Modelling truncation lengths");
+    tksmseq_ctx* ctx = nullptr;
+    if (tksmseq_create(c.devices[0], &ctx)) { fprintf(stderr, "Error: %s\n", tksmseq_last_error(nullptr)); return 1; }
+    const auto t0 = std::chrono::steady_clock::now();
+    tkh::KdeBuildInfo info;
+    const int rc = tkh::kde_build_model(ctx, &p, c.input.c_str(), c.output.c_str(), &info);
+    if (rc) fprintf(stderr, "Error: %s\n", tksmseq_last_error(ctx));
+    else {
+        if (info.searched) {
+            log.log(Logger::INFO, "Non-positive bandwidth selected: recomputed by 3-fold cross-validation on %llu draws (seed %lld)", (unsigned long long)p.cv_samples, c.seed);
+            for (int r = 0; r < 3; r++) {
+                int arg = 0;
+                for (int k = 1; k < 10; k++) if (info.scores[10 * r + k] > info.scores[10 * r + arg]) arg = k;
+                log.log(Logger::DEBUG, "repeat %d: bandwidth %d (mean score %.17g)", r, 50 + 100 * arg, info.scores[10 * r + arg]);
+            }
+        }
+        log.log(Logger::INFO, "bandwidth: %.17g", info.bandwidth);
+        log.log(Logger::INFO, "model-truncation: %llu primary alignments, %llu end ratios, model written to %s in %.2f s", (unsigned long long)info.n_pairs,
+                (unsigned long long)info.n_ratios, c.output.c_str(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    }
+    tksmseq_destroy(ctx);
+    return rc ? 1 : 0;
 }

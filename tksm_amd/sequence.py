@@ -347,6 +347,32 @@ class Sequencer:
         self._chk(self._lib.tksmseq_append_noise(self._ctx, batch._h, C.byref(p), C.byref(h)))
         return Batch(self, h)
 
+    # ---- model-truncation: the KDE truncation model built on the device
+    def kde_grid(self, xy, px, py, bandwidth):
+        """KernelDensity(bandwidth).fit(xy).score_samples on the grid px x py, exp'ed (py/truncate_kde.py:245-287), as the EXACT density
+        (tksmseq_kde_grid): float64[len(px)][len(py)], P[i][j] for the point (px[i], py[j])."""
+        xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        px = np.ascontiguousarray(px, np.float64).ravel(); py = np.ascontiguousarray(py, np.float64).ravel()
+        out = np.empty((len(px), len(py)), np.float64)
+        self._chk(self._lib.tksmseq_kde_grid(self._ctx, xy.ctypes.data, len(xy), px.ctypes.data, len(px), py.ctypes.data, len(py), float(bandwidth),
+                                             out.ctypes.data))
+        return out
+
+    def kde_cv_bandwidth(self, xy, seed=42, cv_samples=100000):
+        """CV_KDE_bandwidth (py/truncate_kde.py:223-242) with seeded draws (tksmseq_kde_cv_bandwidth): (bandwidth, mean scores float64[3][10]
+        for the bandwidths L.KDE_BANDWIDTHS)."""
+        xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        bw, scores = C.c_double(), np.empty((3, 10), np.float64)
+        self._chk(self._lib.tksmseq_kde_cv_bandwidth(self._ctx, xy.ctypes.data, len(xy), int(seed), int(cv_samples), C.byref(bw), scores.ctypes.data))
+        return bw.value, scores
+
+    def model_truncation(self, paf, out, bandwidth=100.0, grid_start=0, grid_end=10000, grid_step=100, model_lengths=False, end_ratio=-1.0, seed=42,
+                         cv_samples=100000):
+        """main() of py/truncate_kde.py (:323-352): the PAF's primary alignments -> the JSON model `tksm truncate --kde-model` reads."""
+        p = L.KdeModelParams(int(seed), int(cv_samples), float(bandwidth), int(grid_start), int(grid_end), int(grid_step), 1 if model_lengths else 0, 0,
+                             float(end_ratio))
+        self._chk(self._lib.tksmseq_model_truncation(self._ctx, C.byref(p), str(paf).encode(), str(out).encode()))
+
     # ---- random-wgs: whole-genome fragments made on the device
     def wgs(self, dist, a, b=0, base_count=None, depth=None, seed=42, first_candidate=0, n_candidates=1 << 20, state=None):
         """The loop of RWGS_module::run (src/random_wgs.cpp:181-207) for candidates [first_candidate, first_candidate + n_candidates)
@@ -460,3 +486,31 @@ def sequence_main(argv):
     lib = L.load()
     arr = (C.c_char_p * len(argv))(*[a.encode() for a in argv])
     return lib.tksmseq_sequence_main(len(argv), arr)
+
+
+def build_tail_model(mapped, unmapped, lx, ly, begin, trans, bandwidth, path, device=0):
+    """KDE_noise_generator.from_data + .save (py/tksm_badread.py:888-901, :933-939): the tail-noise model of `tksm sequence --badread-tail-model`
+    from (mapped, unmapped) length pairs -- grid[a][b] = density(mapped = lx[a], unmapped = ly[b]) from Sequencer.kde_grid, ratio = share of
+    reads with unmapped > 0, bases AGTC, begin / trans the base chain's start weights and 4 x 4 transition weights -- written to `path` as the
+    JSON tksmseq_load_tail_model reads.  The reference indexes the grid's rows by ly when it samples, so its layout holds together only for
+    axes of equal length: anything else is refused here."""
+    import json
+    mapped = np.asarray(mapped, np.float64).ravel(); unmapped = np.asarray(unmapped, np.float64).ravel()
+    lx = np.asarray(lx, np.float64).ravel(); ly = np.asarray(ly, np.float64).ravel()
+    trans = np.asarray(trans, np.float64); begin = np.asarray(begin, np.float64).ravel()
+    if len(mapped) != len(unmapped) or len(mapped) == 0:
+        raise ValueError("tail model: mapped and unmapped must be non-empty and of one length")
+    if len(lx) != len(ly):
+        raise ValueError("tail model: lx and ly must have the same length (the reference's sampler reads grid rows by ly)")
+    if trans.shape != (4, 4) or begin.shape != (4,):
+        raise ValueError("tail model: begin must hold 4 weights, trans 4 x 4")
+    s = Sequencer(device)
+    try:
+        grid = s.kde_grid(np.stack([mapped, unmapped], axis=1), lx, ly, bandwidth)
+    finally:
+        s.close()
+    dc = {"lx": lx.tolist(), "ly": ly.tolist(), "grid": grid.tolist(), "bases": list("AGTC"), "ratio": float(np.sum(unmapped > 0) / len(unmapped)),
+          "trans": trans.tolist(), "begin": begin.tolist()}
+    with open(path, "w") as f:
+        json.dump(dc, f)
+    return dc
