@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -125,10 +126,16 @@ inline size_t last_molecule_boundary(const char* buf, size_t have, size_t floor)
 struct ChunkReader {
     FILE* in = nullptr; uint64_t bytes = 64ull << 20; std::vector<char> buf; size_t have = 0; bool eof = false;
     size_t floor = 0;                                        // buf[0, floor) holds no boundary: a molecule larger than `bytes` is scanned once, not once per refill
+    std::function<size_t(char*, size_t)> read;               // up to n bytes into dst, 0 at the end of the input; unset: fread on `in`
+    size_t fill(char* dst, size_t n) {                       // n bytes unless the input ends
+        size_t got = 0;
+        for (size_t r; got < n && (r = read ? read(dst + got, n - got) : fread(dst + got, 1, n - got, in)) > 0;) got += r;
+        return got;
+    }
     bool next(std::vector<char>& out) {
         while (!eof || have) {
             buf.resize(have + bytes);
-            const size_t got = eof ? 0 : fread(buf.data() + have, 1, bytes, in);
+            const size_t got = eof ? 0 : fill(buf.data() + have, bytes);
             if (got < bytes) eof = true;
             have += got;
             size_t cut = have;
