@@ -503,6 +503,69 @@ typedef struct {
 } tksmseq_wgs_progress;
 int tksmseq_wgs(tksmseq_ctx* ctx, const tksmseq_wgs_params* params, tksmseq_batch** out, tksmseq_wgs_progress* progress);
 
+/* ---- transcribe: GTF + abundance tables to molecules, expanded on the device -------------------------------------------------------------
+ * Replaces Splicer_module::run (src/transcribe.cpp:119-198) without its fusion submodule (src/fusion.cpp: not built).  The entry module of
+ * every transcriptome route: a row "transcript_id tpm cell-barcode" of an abundance table becomes `depth` copies of its transcript's exons
+ * with the comment "CB=<barcode>;tid=<id>;".
+ *
+ * tksmseq_transcripts_add_gtf replaces read_gtf_transcripts_deep + the gtf line constructor + the merge of :134-137 (src/gtf.h:274-304,
+ * src/interval.h:252-275): the transcripts of one more GTF go into the context's table; an id the table already has keeps what it has.
+ * skip_non_coding is what the reference passes --default-depth as (:136): non-zero drops every line whose gene_biotype is not
+ * protein_coding.  The reference's quirks are kept and listed in csrc/tsb_host.h; where it is undefined this is an error: TKSMSEQ_EINVAL
+ * for a line with fewer than 9 fields, a coordinate that is no number in [1, 2^31 - 1], an exon before any transcript (the message names
+ * file and line), TKSMSEQ_EIO for a file that cannot be read (the reference reads nothing, silently).  A failed call leaves the table as
+ * it was.  Clones made afterwards share the table; plans keep the table they were made with. */
+typedef struct tksmseq_tsb_plan tksmseq_tsb_plan;
+int tksmseq_transcripts_add_gtf(tksmseq_ctx* ctx, const char* path, int skip_non_coding);
+int tksmseq_transcripts_info(const tksmseq_ctx* ctx, uint64_t* n_transcripts, uint64_t* n_exons);
+int tksmseq_transcripts_clear(tksmseq_ctx* ctx);
+/* tksmseq_transcribe_plan_create replaces the abundance reader and the count loop (:149-158, :168-190) for ONE abundance table, read from
+ * abundance_path, or (path NULL) from text[0, len).  Rows are read as operator>> reads them, the first line is skipped, only the row's id is
+ * cut at its first '.' unless use_whole_id (format_annot_id, src/util.h:203-210).  For data row i, in IEEE double and in this order:
+ * c = ((weight x tpm_i) x molecule_count) / sum_tpm, sum_tpm the left-to-right sum over all rows; carry = c - int(c); if a uniform of
+ * Philox(seed, first_row_index + i, stream 56) is below carry, c += 1; depth = int(c); int() clamps in double first and takes NaN to 0.
+ * A row is emitted when its id is in the transcript table and depth >= 1 (the reference also writes negative depths); the molecule id is
+ * prefix + the row's rank among the emitted rows of this table (:168, :195: the index restarts with every table).  weight: the caller's
+ * share of this table (process_file_weights, :65-77: one weight w is w / n_files for every table, several are normalised to sum 1);
+ * first_row_index: the data rows of the tables before this one.  The counts and their prefix sums are computed on the device and stay
+ * there.  TKSMSEQ_ESTATE: no GTF added; TKSMSEQ_EIO: "Could not open abundance file X!" (:146); TKSMSEQ_ELIMIT: a table of 4 GB or 2^32 - 2 rows. */
+typedef struct {
+    uint64_t seed;
+    int64_t molecule_count;          /* --molecule-count */
+    double weight;
+    uint64_t first_row_index;
+    int32_t use_whole_id;            /* --use-whole-id */
+    int32_t reserved;
+    const char* prefix;              /* --molecule-prefix (NULL: "M") */
+} tksmseq_tsb_params;
+int tksmseq_transcribe_plan_create(tksmseq_ctx* ctx, const char* abundance_path, const char* text, uint64_t len, const tksmseq_tsb_params* params,
+                                   tksmseq_tsb_plan** out);
+/* the same plan for another context that holds the same transcript table (a clone): the parsed rows are shared, the counts computed again */
+int tksmseq_transcribe_plan_clone(tksmseq_ctx* ctx, const tksmseq_tsb_plan* src, tksmseq_tsb_plan** out);
+/* rows: data rows; records: emitted rows; molecules: the sum of their depths; missing: rows whose id the table lacks, whose ids
+ * tksmseq_transcribe_plan_missing gives in row order (not NUL-terminated: *len bytes) for "Isoform {} is not found in the input GTFs!" (:177) */
+int tksmseq_transcribe_plan_info(const tksmseq_tsb_plan* plan, uint64_t* rows, uint64_t* records, uint64_t* molecules, uint64_t* missing);
+int tksmseq_transcribe_plan_missing(const tksmseq_tsb_plan* plan, uint64_t i, const char** id, uint64_t* len);
+void tksmseq_transcribe_plan_free(tksmseq_tsb_plan* plan);
+/* tksmseq_transcribe replaces the molecule of :180, :192-196 read back with unroll (src/mdf.h:97-105): molecules [first_molecule,
+ * first_molecule + n_molecules) of the plan's records unrolled (clipped to the end: a slice past it is an empty batch) as an ordinary batch
+ * on ctx, the context the plan was made for.  Copies of a record with depth > 1 print as id_0, id_1, ... and sequence as molecule_id=id,
+ * like the copies of a parsed depth > 1 molecule.  A contig the context's reference knows is that contig, any other name a literal, as the
+ * MDF parser has it.  flags: TKSMSEQ_MOL_NO_COMMENTS or 0.  Results depend on (seed, row index) and prefix sums only, never on the slicing
+ * or the device.  TKSMSEQ_ELIMIT: more than 2^28 molecules per call (checked first), a batch beyond the table limits of a batch;
+ * TKSMSEQ_ESTATE: a plan of another context, a transcript table that has changed. */
+int tksmseq_transcribe(tksmseq_ctx* ctx, const tksmseq_tsb_plan* plan, uint64_t first_molecule, uint64_t n_molecules, int32_t flags, tksmseq_batch** out);
+/* Device time by HIP events (0 unless tksmseq_set_timing is on) of the context's last plan -- count, size and the four scans -- and of its
+ * last tksmseq_transcribe -- the write kernel alone, without the batch finalisation every device-made batch goes through. */
+int tksmseq_transcribe_device_ms(const tksmseq_ctx* ctx, float* plan_ms, float* write_ms);
+/* outfile << molecule (:196; operator<< and dump_comment, src/interval.h:881-905) for records [first_record, first_record + n_records):
+ * "+id<TAB>depth<TAB>CB=..;tid=..;" and one line per exon -- the reference's own compact output.  Release with tksmseq_text_free. */
+int tksmseq_transcribe_text(const tksmseq_tsb_plan* plan, uint64_t first_record, uint64_t n_records, char** text, uint64_t* len);
+/* `tksm transcribe` (Splicer_module src/transcribe.cpp:19-218): -g/--gtf, -a/--abundance (repeatable, comma-separated), --use-whole-id,
+ * --molecule-count, -o/--output, --non-coding (no effect, :124), --default-depth (see above), --molecule-prefix, -w/--weights, -s/--seed,
+ * --verbosity, --log-file; here also --devices (the first entry is used) and --batch-molecules.  The --fusion-* options are not taken. */
+int tksmseq_transcribe_main(int argc, char** argv);
+
 /* ---- model-truncation: the KDE truncation model built on the device ---------------------------------------------------------------------
  * Replaces py/truncate_kde.py (behind src/model_truncation.cpp), which needs scikit-learn: the 2-D model that tksmseq_truncate's KDE mode
  * and `tksm truncate --kde-model` read.

@@ -107,6 +107,11 @@ class NoiseParams(C.Structure):              # tksmseq_noise_params
 NOISE_NORMAL, NOISE_LOGNORMAL = 0, 1
 NOISE_DISTS = {"normal": NOISE_NORMAL, "lognormal": NOISE_LOGNORMAL}
 
+class TsbParams(C.Structure):                # tksmseq_tsb_params
+    _fields_ = [("seed", C.c_uint64), ("molecule_count", C.c_int64), ("weight", C.c_double), ("first_row_index", C.c_uint64),
+                ("use_whole_id", C.c_int32), ("reserved", C.c_int32), ("prefix", C.c_char_p)]
+
+
 class KdeModelParams(C.Structure):           # tksmseq_kde_model_params
     _fields_ = [("seed", C.c_uint64), ("cv_samples", C.c_uint64), ("bandwidth", C.c_double), ("grid_start", C.c_int64),
                 ("grid_end", C.c_int64), ("grid_step", C.c_int64), ("model_lengths", C.c_int32), ("reserved", C.c_int32),
@@ -135,6 +140,9 @@ SYMBOLS = [
     "tksmseq_reference_declare_contig", "tksmseq_wgs", "tksmseq_random_wgs_main",
     "tksmseq_append_noise", "tksmseq_tail_noise_main",
     "tksmseq_kde_grid", "tksmseq_kde_cv_bandwidth", "tksmseq_model_truncation", "tksmseq_model_truncation_main",
+    "tksmseq_transcripts_add_gtf", "tksmseq_transcripts_info", "tksmseq_transcripts_clear", "tksmseq_transcribe_plan_create",
+    "tksmseq_transcribe_plan_clone", "tksmseq_transcribe_plan_info", "tksmseq_transcribe_plan_missing", "tksmseq_transcribe_plan_free",
+    "tksmseq_transcribe", "tksmseq_transcribe_text", "tksmseq_transcribe_main", "tksmseq_transcribe_device_ms",
 ]
 
 _lib = None
@@ -220,6 +228,18 @@ def load():
         "tksmseq_kde_cv_bandwidth": (C.c_int, [vp, vp, u64, u64, u64, P(C.c_double), vp]),
         "tksmseq_model_truncation": (C.c_int, [vp, P(KdeModelParams), C.c_char_p, C.c_char_p]),
         "tksmseq_model_truncation_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
+        "tksmseq_transcripts_add_gtf": (C.c_int, [vp, C.c_char_p, C.c_int]),
+        "tksmseq_transcripts_info": (C.c_int, [vp, P(u64), P(u64)]),
+        "tksmseq_transcripts_clear": (C.c_int, [vp]),
+        "tksmseq_transcribe_plan_create": (C.c_int, [vp, C.c_char_p, C.c_char_p, u64, P(TsbParams), P(vp)]),
+        "tksmseq_transcribe_plan_clone": (C.c_int, [vp, vp, P(vp)]),
+        "tksmseq_transcribe_plan_info": (C.c_int, [vp, P(u64), P(u64), P(u64), P(u64)]),
+        "tksmseq_transcribe_plan_missing": (C.c_int, [vp, u64, P(vp), P(u64)]),
+        "tksmseq_transcribe_plan_free": (None, [vp]),
+        "tksmseq_transcribe": (C.c_int, [vp, vp, u64, u64, i32, P(vp)]),
+        "tksmseq_transcribe_text": (C.c_int, [vp, u64, u64, P(vp), P(u64)]),
+        "tksmseq_transcribe_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
+        "tksmseq_transcribe_device_ms": (C.c_int, [vp, P(C.c_float), P(C.c_float)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

@@ -69,6 +69,7 @@ int tksmseq_clone(const tksmseq_ctx* src, tksmseq_ctx** out) {
     c->contig_names = src->contig_names; c->contig_index = src->contig_index; c->contigs = src->contigs;
     c->total_alloc = src->total_alloc; c->total_bases = src->total_bases; c->pool_blocks = src->pool_blocks;
     c->contig_declared = src->contig_declared; c->n_declared = src->n_declared;
+    c->tsb = src->tsb;                                       // (the transcript table of transcribe: immutable, shared)
     c->d_packed.borrow(src->d_packed); c->d_blocktab.borrow(src->d_blocktab); c->d_pool.borrow(src->d_pool); c->d_contigs.borrow(src->d_contigs);
     c->em = src->em; c->qm = src->qm; c->idm = src->idm; c->em_uniform = src->em_uniform; c->em_alt0 = src->em_alt0;
     c->d_pself.borrow(src->d_pself); c->d_pseg.borrow(src->d_pseg); c->d_pt0.borrow(src->d_pt0); c->d_cdf32.borrow(src->d_cdf32); c->d_cdf.borrow(src->d_cdf); c->d_alts.borrow(src->d_alts); c->d_altenc.borrow(src->d_altenc);

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -15,6 +16,7 @@
 #include "../../include/tksmseq.h"
 #include "host.h"
 #include "kernels.h"
+#include "tsb_host.h"
 
 using namespace tkh;
 
@@ -241,6 +243,14 @@ struct tksmseq_ctx : ContigLookup {
     uint64_t ref_version = 0, wgs_version = ~0ull;
     DevBuf d_wgs_sofar, d_wgs_nameoff, d_wgs_namelen, d_wgs_names;
     DevBuf d_packed, d_blocktab, d_pool, d_contigs, d_stage;
+    // transcribe: the transcript table (host; shared with clones and plans, replaced -- never changed -- by tksmseq_transcripts_add_gtf) and
+    // its device form: exon tuples in the interval layout of a batch, contigs resolved against THIS context's reference (a name it does not
+    // know is a literal of every output batch), rebuilt when the table or the reference has changed
+    std::shared_ptr<const tsb::Transcripts> tsb;
+    uint64_t tsb_dev_serial = 0, tsb_ref_version = ~0ull;      // (serial 0: no device form yet)
+    DevBuf d_tsb_first, d_tsb_exons, d_tsb_lits, d_tsb_litpool;
+    uint64_t tsb_n_lits = 0, tsb_lit_bytes = 0;
+    float tsb_plan_ms = 0.f, tsb_write_ms = 0.f;          // device time of the last plan / tksmseq_transcribe by HIP events (tksmseq_set_timing)
 
     // models
     ErrorModelHost em; QScoreModelHost qm; IdentityHost idm;

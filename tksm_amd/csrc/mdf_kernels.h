@@ -114,6 +114,29 @@ hipError_t launch_wgs_cut(uint64_t n, const uint4* plan, const uint64_t* rank, c
 hipError_t launch_wgs_write(uint64_t n, const uint4* plan, const uint64_t* rank, const uint64_t* idlen, const uint64_t* id_off, const uint32_t* name_off,
                             const uint32_t* name_len, const uint8_t* names, uint64_t mols_before, const MolOut& o, hipStream_t s);
 
+// transcribe (src/transcribe.cpp:170-197): an abundance row becomes `depth` copies of its transcript; see mdf_kernels.hip
+struct TsbCount {
+    uint64_t seed, first_row;             // row r draws from Philox(seed, first_row + r, ST_TSB, 0)
+    double weight, molecule_count, sum_tpm;   // c = ((weight x tpm) x molecule_count) / sum_tpm
+};
+// depth[r]: molecules of row r (0: transcript not found, or a count below 1); flag[r]: 1 when depth[r] >= 1.  tx[r]: transcript, ~0: none
+hipError_t launch_tsb_count(uint64_t n_rows, const TsbCount& p, const uint32_t* tx, const double* tpm, uint64_t* depth, uint64_t* flag, hipStream_t s);
+// rank: exclusive scan of flag ([n_rows + 1]); n_ivl[r] = depth x exons of the transcript, id_bytes[r] = depth x (prefix_len + digits of rank)
+hipError_t launch_tsb_size(uint64_t n_rows, const uint32_t* tx, const uint32_t* exon_first, const uint64_t* depth, const uint64_t* rank, uint32_t prefix_len,
+                           uint64_t* n_ivl, uint64_t* id_bytes, hipStream_t s);
+struct TsbPlanView {                      // the plan's device arrays: per row, and their exclusive scans ([n_rows + 1])
+    uint64_t n_rows;
+    const uint32_t* tx;
+    const uint64_t *mol_first, *rank, *ivl_first, *id_first;
+    const uint32_t* exon_first;           // [n_transcripts + 1]
+    const uint4* exons;                   // {contig (bit 31: literal), start, end, minus << 31}: an interval of the batch layout
+    const uint8_t* prefix; uint32_t prefix_len;
+};
+// molecules [first_mol, first_mol + n_mol) of the unrolled range; their intervals are [ivl_base, ivl_base + n_ivl) and their id bytes start
+// at id_base of the whole run's.  dup: [n_mol] bit 31 for a copy of a row with depth > 1, low bits the copy's index
+hipError_t launch_tsb_write(const TsbPlanView& v, uint64_t first_mol, uint64_t n_mol, uint64_t ivl_base, uint64_t n_ivl, uint64_t id_base, const MolOut& o,
+                            uint32_t* dup, hipStream_t s);
+
 // tail-noise (src/append_noise.cpp:83-128, NoiseAdder::operator()): a noise length L per molecule from normal / lognormal(mu, sigma);
 // random mode appends a literal of L letters of the alphabet, palindromic mode appends the molecule's last segments again, strands
 // toggled, the last copy cut so that the hairpin has min(L, molecule size) bases, then a Bernoulli(error_rate) substitution per hairpin

@@ -13,6 +13,7 @@
 //   flip_molecule                src/interval.h:908-920   reverse the segment order, toggle every strand
 //   RWGS_module::run             src/random_wgs.cpp:181-207 whole-genome fragments: position, length and strand draws, no input
 //   NoiseAdder::operator()       src/append_noise.cpp:83-128 tail noise: a random literal, or the last segments again as a hairpin
+//   Splicer_module::run          src/transcribe.cpp:170-197 an abundance row becomes `depth` copies of its transcript's exons, no input batch
 // Integer / byte work, one LANE per molecule (tail-noise alone spreads its per-base work: one wave per molecule, or a flat grid): the tables of a molecule are a few dozen bytes, the work per molecule is a short
 // serial walk (tree of copies; list of segments).  The reference draws from a sequential Mersenne Twister; here every
 // decision has its own Philox counter (template molecule, path of copy cycles, purpose), so the result does not depend on
@@ -26,7 +27,7 @@ namespace tk {
 struct Ph4m { uint32_t x, y, z, w; };
 enum { ST_PCR_PICK = 16, ST_PCR_EMIT = 17, ST_PCR_CHILD = 18, ST_PCR_MUT = 19, ST_TRC_LEN = 24, ST_TRC_SIDE = 25,
        ST_PLA_LEN = 26, ST_TAG5 = 27, ST_TAG3 = 28, ST_FLIP = 29, ST_WGS_POS = 32, ST_WGS_LEN = 33, ST_WGS_STRAND = 34,
-       ST_NOISE_LEN = 40, ST_NOISE_SEQ = 41, ST_NOISE_ERR = 42 };
+       ST_NOISE_LEN = 40, ST_NOISE_SEQ = 41, ST_NOISE_ERR = 42, ST_TSB = 56 };
 
 DEV Ph4m philox_raw(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
@@ -856,6 +857,83 @@ __global__ void __launch_bounds__(256) k_pal_write(MolView M, NoiseParams P, uin
 }
 
 // ------------------------------------------------------------------------------------------------
+// transcribe (src/transcribe.cpp:170-197): molecules made here from the transcript table of the context and the rows of an abundance
+// table.  k_tsb_count, one lane per ROW: count = ((W x tpm) x molecule_count) / sum_tpm in double, in this order (:181; sum_tpm is the
+// host's left-to-right sum, :170); carry = count - int(count); one uniform of Philox(seed, row index, ST_TSB, 0) below the carry adds 1
+// (:182-186); depth = int(count), with the clamp-in-double and NaN -> 0 rule of wgs_to_int for both conversions.  A row is emitted when its
+// transcript was found and depth >= 1.  launch_scan ranks the emitted rows (the molecule index of :195 is the rank), k_tsb_size then
+// knows every row's id length, and three more scans give each row's first molecule, first interval and first id byte.
+// k_tsb_write fills the tables of any slice of the unrolled molecule range.  A row owns between one and 10^6 molecules and a transcript one
+// to several hundred exons, so neither a lane nor a wave per row (or per molecule) has even work: one would serialise a million copies
+// behind one lane, the other idle 63 lanes on a single-exon transcript.  The grid is FLAT over the OUTPUT instead (the k_noise_fill
+// argument): lane t writes molecule t of the slice -- its reads entry, id and dup word -- and interval t of the slice, each owner found by
+// a binary search in the scans (~22 probes for 4 M rows; the upper levels of the search are the same lines for every lane and stay in L2,
+// the last ones are shared by neighbouring lanes).  The stores are what matters: lane t stores the 16 bytes of interval t, so a wave
+// writes 1 KB in one piece whatever the exon counts are, and the exon tuples it copies come from a table that is small next to the
+// output (8 exons per transcript on average: read once from HBM, then from L2).  Nothing is staged in LDS: no element is used by a
+// second lane.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_tsb_count(uint64_t n, TsbCount P, const uint32_t* __restrict__ tx, const double* __restrict__ tpm,
+                                                   uint64_t* __restrict__ depth, uint64_t* __restrict__ flag) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    double c = ((P.weight * tpm[r]) * P.molecule_count) / P.sum_tpm;
+    const double carry = c - (double)wgs_to_int(c);
+    const Ph4m w = philox_mol(P.seed, P.first_row + r, ST_TSB, 0);
+    if (u53(w.x, w.y) < carry) c += 1.0;
+    const int d = wgs_to_int(c);
+    const bool emit = tx[r] != 0xffffffffu && d >= 1;
+    depth[r] = emit ? (uint64_t)d : 0ull;
+    flag[r] = emit ? 1ull : 0ull;
+}
+
+__global__ void __launch_bounds__(256) k_tsb_size(uint64_t n, const uint32_t* __restrict__ tx, const uint32_t* __restrict__ exon_first,
+                                                  const uint64_t* __restrict__ depth, const uint64_t* __restrict__ rank, uint32_t prefix_len,
+                                                  uint64_t* __restrict__ n_ivl, uint64_t* __restrict__ id_bytes) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const uint64_t d = depth[r];
+    const uint32_t t = tx[r];
+    n_ivl[r] = d ? d * (uint64_t)(exon_first[t + 1] - exon_first[t]) : 0ull;
+    id_bytes[r] = d ? d * (uint64_t)(prefix_len + (uint32_t)ndig64(rank[r])) : 0ull;
+}
+
+// the owner of element v: the last r in [0, n) with first[r] <= v (first[0] = 0; rows without elements share their successor's start and
+// are never the last)
+DEV uint64_t tsb_owner(const uint64_t* __restrict__ first, uint64_t n, uint64_t v) {
+    uint64_t lo = 0, hi = n;
+    while (lo + 1 < hi) { const uint64_t mid = (lo + hi) >> 1; if (first[mid] <= v) lo = mid; else hi = mid; }
+    return lo;
+}
+
+__global__ void __launch_bounds__(256) k_tsb_write(TsbPlanView V, uint64_t first_mol, uint64_t n_mol, uint64_t ivl_base, uint64_t n_ivl, uint64_t id_base,
+                                                   MolOut O, uint32_t* __restrict__ dup) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n_mol) {
+        const uint64_t m = first_mol + t;
+        const uint64_t r = tsb_owner(V.mol_first, V.n_rows, m);
+        const uint64_t copy = m - V.mol_first[r], depth = V.mol_first[r + 1] - V.mol_first[r];
+        const uint32_t tr = V.tx[r], ec = V.exon_first[tr + 1] - V.exon_first[tr];
+        O.reads[2 * t] = (uint32_t)(V.ivl_first[r] + copy * ec - ivl_base); O.reads[2 * t + 1] = ec;
+        const uint64_t index = V.rank[r];
+        const uint32_t idl = V.prefix_len + (uint32_t)ndig64(index);
+        const uint64_t at = V.id_first[r] + copy * idl - id_base;
+        uint8_t* d = O.idpool + at;
+        for (uint32_t q = 0; q < V.prefix_len; q++) d[q] = V.prefix[q];
+        put_dec64(d + V.prefix_len, index);
+        O.ids[2 * t] = (uint32_t)at; O.ids[2 * t + 1] = idl;
+        dup[t] = depth > 1ull ? (0x80000000u | (uint32_t)copy) : 0u;
+    }
+    if (t < n_ivl) {
+        const uint64_t g = ivl_base + t;
+        const uint64_t r = tsb_owner(V.ivl_first, V.n_rows, g);
+        const uint32_t tr = V.tx[r], e0 = V.exon_first[tr], ec = V.exon_first[tr + 1] - e0;
+        const uint64_t within = g - V.ivl_first[r];
+        reinterpret_cast<uint4*>(O.intervals)[t] = V.exons[e0 + (uint32_t)(within % ec)];      // (mod_begin 0: no substitutions)
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
 static inline unsigned nblk(uint64_t n) { return (unsigned)((n + 127) / 128); }
@@ -934,6 +1012,25 @@ hipError_t launch_wgs_write(uint64_t n, const uint4* plan, const uint64_t* rank,
                             const uint32_t* name_len, const uint8_t* names, uint64_t mols_before, const MolOut& o, hipStream_t s) {
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(k_wgs_write, dim3(nblk(n)), dim3(128), 0, s, n, plan, rank, idlen, id_off, name_off, name_len, names, mols_before, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_tsb_count(uint64_t n_rows, const TsbCount& p, const uint32_t* tx, const double* tpm, uint64_t* depth, uint64_t* flag, hipStream_t s) {
+    if (!n_rows) return hipSuccess;
+    hipLaunchKernelGGL(k_tsb_count, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s, n_rows, p, tx, tpm, depth, flag);
+    return hipGetLastError();
+}
+hipError_t launch_tsb_size(uint64_t n_rows, const uint32_t* tx, const uint32_t* exon_first, const uint64_t* depth, const uint64_t* rank, uint32_t prefix_len,
+                           uint64_t* n_ivl, uint64_t* id_bytes, hipStream_t s) {
+    if (!n_rows) return hipSuccess;
+    hipLaunchKernelGGL(k_tsb_size, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s, n_rows, tx, exon_first, depth, rank, prefix_len, n_ivl, id_bytes);
+    return hipGetLastError();
+}
+hipError_t launch_tsb_write(const TsbPlanView& v, uint64_t first_mol, uint64_t n_mol, uint64_t ivl_base, uint64_t n_ivl, uint64_t id_base, const MolOut& o,
+                            uint32_t* dup, hipStream_t s) {
+    const uint64_t n = n_mol > n_ivl ? n_mol : n_ivl;
+    if (!n || !v.n_rows) return hipSuccess;
+    hipLaunchKernelGGL(k_tsb_write, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, first_mol, n_mol, ivl_base, n_ivl, id_base, o, dup);
     return hipGetLastError();
 }
 

@@ -13,6 +13,7 @@
 //   StrandMan_module        src/strand_man.cpp:20-124 -p/--flip-probability (outside [0, 1]: logged, not refused)
 //   RWGS_module             src/random_wgs.cpp:24-229 -r/--reference, --frag-len-dist "NAME A [B]", -o, --base-count | --depth
 //   AppendNoise_module      src/append_noise.cpp:131-229 --length-dist NAME,MU,SIGMA, --alphabet, --palindromic, --error-rate
+//   Splicer_module          src/transcribe.cpp:19-218 -g/--gtf, -a/--abundance, --molecule-count, -w/--weights, ... (no fusion submodule): GTF + TSV in, MDF out
 //   model-truncation        py/truncate_kde.py:36-112, :323-352 (behind src/model_truncation.cpp) PAF in, KDE model JSON out: no MDF, one context
 //   utility flags           src/module.h:75-104      -s/--seed (default 42), --verbosity, --log-file, -h
 // All stream: `truncate` and the four segment edits read the input in batches of whole molecules (--batch-bytes), `pcr` amplifies its templates in slices
@@ -676,6 +677,114 @@ extern "C" int tksmseq_random_wgs_main(int argc, char** argv) {
     return run_pieces(c, log, "random-wgs", prepare, next_piece, work, true, [&] {
         return ", " + std::to_string(st.bases) + " bases from " + std::to_string(st.next_candidate) + " candidates";
     });
+}
+
+// `tksm transcribe` (Splicer_module, src/transcribe.cpp:19-218) without the fusion submodule: GTFs and abundance tables in, the reference's
+// compact MDF out (one record per emitted row, depth = its count).  One context on the first entry of --devices: the counts are made on the
+// device (tksmseq_transcribe_plan_create), the text from them on the host (tksmseq_transcribe_text), --batch-molecules records at a time.
+static void split_commas(const char* v, std::vector<std::string>& out) {      // cxxopts' vector<string>: every occurrence, split at ','
+    const char* q = v;
+    for (;;) {
+        const char* e = strchr(q, ',');
+        out.emplace_back(q, e ? (size_t)(e - q) : strlen(q));
+        if (!e) return;
+        q = e + 1;
+    }
+}
+
+extern "C" int tksmseq_transcribe_main(int argc, char** argv) {
+    Common c;
+    std::vector<std::string> gtfs, abundances;
+    std::vector<double> weights;
+    bool have_count = false;
+    long long molecule_count = 0, default_depth = 0;
+    int32_t use_whole_id = 0, non_coding = 0;
+    std::string prefix = "M";
+    uint64_t batch_molecules = 1 << 20;
+    auto integer = [](const char* v, long long& out) { char* e = nullptr; out = strtoll(v, &e, 10); return e != v && !*e; };
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            // (the common flags know -i, --batch-bytes and --slice-molecules, which this module does not have)
+            if (o == "-i" || o == "--input" || o == "--batch-bytes" || o == "--slice-molecules") return NO_SUCH;
+            if (o == "--use-whole-id") return bool_flag(v, use_whole_id);
+            if (o == "--non-coding") return bool_flag(v, non_coding);
+            if ((o == "-g" || o == "--gtf") && v) split_commas(v, gtfs);
+            else if ((o == "-a" || o == "--abundance") && v) split_commas(v, abundances);
+            else if (o == "--molecule-count" && v) { if (!integer(v, molecule_count) || molecule_count < -2147483648ll || molecule_count > 2147483647ll) return MALFORMED; have_count = true; }
+            else if (o == "--default-depth" && v) { if (!integer(v, default_depth)) return MALFORMED; }
+            else if (o == "--molecule-prefix" && v) prefix = v;
+            else if ((o == "-w" || o == "--weights") && v) { std::vector<double> w; if (!parse_doubles(v, w)) return MALFORMED; weights.insert(weights.end(), w.begin(), w.end()); }
+            else if (o == "--batch-molecules" && v) { batch_molecules = strtoull(v, nullptr, 10); if (batch_molecules < 1 || batch_molecules > (1ull << 28)) return MALFORMED; }
+            else return NOT_MINE;
+            return TOOK_VALUE;
+        })) return 1;
+    static const char* help =
+        "RNA Splicing module\nusage: transcribe -g GTF[,GTF...] -a ABUNDANCE[,ABUNDANCE...] --molecule-count N -o OUTPUT [--use-whole-id] [--non-coding]\n"
+        "                  [--default-depth D] [--molecule-prefix M] [-w W[,W...]] [-s SEED] [--devices D] [--batch-molecules M] [--verbosity L] [--log-file F]\n"
+        "ABUNDANCE: a header line, then rows `transcript_id tpm cell-barcode`; -w: one weight, or one per abundance table\n"
+        "--default-depth D: a non-zero D keeps only the lines whose gene_biotype is protein_coding; --non-coding has no effect (both as the reference)\n"
+        "The gene-fusion options of the reference (--fusion-gtf, --fusion-file, --fusion-output, --fusion-count, --disable-deletions,\n"
+        "--translocation-ratio, --expression-fallback) are not built: they are refused like any unknown option\n";
+    if (c.help) { printf("%s", help); return 0; }
+    // validate_arguments (src/transcribe.cpp:90-108)
+    int missing = 0;
+    if (gtfs.empty()) { fprintf(stderr, "Missing mandatory parameter gtf\n"); missing++; }
+    if (abundances.empty()) { fprintf(stderr, "Missing mandatory parameter abundance\n"); missing++; }
+    if (c.output.empty()) { fprintf(stderr, "Missing mandatory parameter output\n"); missing++; }
+    if (!have_count) { fprintf(stderr, "Missing mandatory parameter molecule-count\n"); missing++; }
+    if (missing) { printf("%s\n", help); return 1; }
+    // process_file_weights (:65-77): one weight for all tables, or one each
+    if (weights.empty()) weights.push_back(1.0);
+    if (weights.size() != 1 && weights.size() != abundances.size()) {
+        fprintf(stderr, "Error: -w/--weights takes one weight, or one per abundance file (%zu weights for %zu files)\n", weights.size(), abundances.size());
+        return 1;
+    }
+    std::vector<double> file_w(abundances.size());
+    if (weights.size() == 1) for (auto& w : file_w) w = weights[0] / (double)abundances.size();
+    else { double sum = 0.0; for (double w : weights) sum += w; for (size_t i = 0; i < file_w.size(); i++) file_w[i] = weights[i] / sum; }
+    Logger log;
+    if (!open_log(c, "transcribe", log)) return 1;
+    for (auto& g : gtfs) { FILE* f = fopen(g.c_str(), "rb"); if (!f) { fprintf(stderr, "Could not open GTF file %s!\n", g.c_str()); return 1; } fclose(f); }
+    for (auto& a : abundances) { FILE* f = fopen(a.c_str(), "rb"); if (!f) { fprintf(stderr, "Could not open abundance file %s!\n", a.c_str()); return 1; } fclose(f); }
+    tksmseq_ctx* ctx = nullptr;
+    if (tksmseq_create(c.devices[0], &ctx)) { fprintf(stderr, "Error: %s\n", tksmseq_last_error(nullptr)); return 1; }
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = 0;
+    FILE* out = nullptr;
+    uint64_t n_records = 0, n_molecules = 0, first_row = 0;
+    for (auto& g : gtfs) {
+        log.log(Logger::INFO, "Reading GTF file %s", g.c_str());
+        if (tksmseq_transcripts_add_gtf(ctx, g.c_str(), default_depth != 0)) { fprintf(stderr, "Error: %s\n", tksmseq_last_error(ctx)); rc = 1; break; }
+    }
+    if (!rc && !(out = fopen(c.output.c_str(), "wb"))) { fprintf(stderr, "Error: cannot write %s\n", c.output.c_str()); rc = 1; }
+    for (size_t k = 0; k < abundances.size() && !rc; k++) {
+        log.log(Logger::INFO, "Reading abundance file %s and printing simulated molecules to %s!", abundances[k].c_str(), c.output.c_str());
+        tksmseq_tsb_params p{};
+        p.seed = (uint64_t)c.seed; p.molecule_count = molecule_count; p.weight = file_w[k]; p.first_row_index = first_row; p.use_whole_id = use_whole_id;
+        p.prefix = prefix.c_str();
+        tksmseq_tsb_plan* plan = nullptr;
+        if (tksmseq_transcribe_plan_create(ctx, abundances[k].c_str(), nullptr, 0, &p, &plan)) { fprintf(stderr, "%s\n", tksmseq_last_error(ctx)); rc = 1; break; }
+        uint64_t rows = 0, records = 0, molecules = 0, n_missing = 0;
+        tksmseq_transcribe_plan_info(plan, &rows, &records, &molecules, &n_missing);
+        for (uint64_t i = 0; i < n_missing; i++) {
+            const char* id = nullptr; uint64_t len = 0;
+            tksmseq_transcribe_plan_missing(plan, i, &id, &len);
+            log.log(Logger::WARN, "Isoform %.*s is not found in the input GTFs!", (int)len, id);
+        }
+        for (uint64_t r = 0; r < records && !rc; r += batch_molecules) {
+            char* text = nullptr; uint64_t len = 0;
+            if (tksmseq_transcribe_text(plan, r, batch_molecules, &text, &len)) { fprintf(stderr, "Error: out of memory\n"); rc = 1; }
+            else if (len && fwrite(text, 1, len, out) != len) { fprintf(stderr, "Error: cannot write %s\n", c.output.c_str()); rc = 1; }
+            tksmseq_text_free(text);
+        }
+        tksmseq_transcribe_plan_free(plan);
+        first_row += rows; n_records += records; n_molecules += molecules;
+    }
+    if (out && fclose(out) != 0 && !rc) { fprintf(stderr, "Error: cannot write %s\n", c.output.c_str()); rc = 1; }
+    tksmseq_destroy(ctx);
+    if (!rc)
+        log.log(Logger::INFO, "transcribe: %llu records (%llu molecules) written in %.2f s", (unsigned long long)n_records, (unsigned long long)n_molecules,
+                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return rc;
 }
 
 // `tksm model-truncation`: the reference runs py/truncate_kde.py (argparse: a missing -i / -o and an unknown option exit with 2; --list

@@ -4,9 +4,11 @@
 //   tksmseq_polya / _tag / _scb / _flip   src/polyA.cpp:133-148, src/tag.cpp:70-113, src/scb.cpp:57-80, src/interval.h:908-920
 //   tksmseq_wgs            src/random_wgs.cpp:181-207 (no input: the molecules are made on the device)
 //   tksmseq_append_noise   src/append_noise.cpp:83-128 (tail-noise: a random literal or a hairpin behind every molecule)
+//   tksmseq_transcribe     src/transcribe.cpp:170-197 (no input batch: abundance rows x the context's transcript table)
 //   tksmseq_batch_to_mdf_text   molecule_descriptor::operator<<, src/interval.h:898-905 (+ dump_comment :880-890)
 // The molecule tables stay on the device from one transform to the next and into tksmseq_run; only sizes, per-read lengths
 // (which the host needs to size and order a Seq batch) and, for the text writer, the tables themselves come back.
+#include <atomic>
 #include <charconv>
 #include <cmath>
 #include <cstring>
@@ -862,6 +864,280 @@ int tksmseq_wgs(tksmseq_ctx* ctx, const tksmseq_wgs_params* p, tksmseq_batch** o
         progress->molecules = p->molecules_before + n_mol; progress->bases = p->bases_before + n_bases;
         progress->reached = reached ? 1 : 0;
     }
+    return TKSMSEQ_OK;
+}
+
+// ---- transcribe ------------------------------------------------------------------------------------------------------------------
+// One abundance table joined with the context's transcript table: the rows on the host (shared by the plans cloned from one another),
+// per-row counts and their scans on the device of the plan's context.
+struct TsbShared {
+    std::shared_ptr<const tsb::Transcripts> tx;
+    tsb::Abundance ab;
+    std::string prefix;
+    uint64_t seed = 0, first_row = 0;
+    double weight = 1.0, molecule_count = 0.0;
+    // host copies of the device scans ([rows + 1]) and the emitted rows in order (a row's position here is its molecule index)
+    std::vector<uint64_t> mol_first, ivl_first, id_first;
+    std::vector<uint32_t> emitted;
+};
+struct tksmseq_tsb_plan {
+    tksmseq_ctx* ctx = nullptr;
+    std::shared_ptr<TsbShared> sh;
+    DevBuf d_tx, d_rank, d_mol_first, d_ivl_first, d_id_first, d_prefix;
+};
+
+// the transcript table as k_tsb_write reads it, with contigs resolved against this context's reference
+static int tsb_table(tksmseq_ctx* ctx) {
+    if (!ctx->tsb) { ctx->err = "transcribe: no GTF has been added (tksmseq_transcripts_add_gtf)"; return TKSMSEQ_ESTATE; }
+    const tsb::Transcripts& T = *ctx->tsb;
+    if (ctx->tsb_dev_serial == T.serial && ctx->tsb_ref_version == ctx->ref_version) return TKSMSEQ_OK;
+    std::vector<uint32_t> contig(T.contig_names.size());
+    std::vector<uint64_t> lits;
+    std::string pool;
+    for (size_t i = 0; i < contig.size(); i++) {
+        const int ci = ctx->find(T.contig_names[i]);
+        if (ci >= 0) { contig[i] = (uint32_t)ci; continue; }
+        contig[i] = 0x80000000u | (uint32_t)(lits.size() / 2);          // a literal: what the MDF parser makes of an unknown name
+        lits.push_back(pool.size()); lits.push_back(T.contig_names[i].size());
+        pool += T.contig_names[i];
+    }
+    const uint64_t E = T.n_exons();
+    std::vector<uint32_t> ex(4 * E);
+    for (uint64_t e = 0; e < E; e++) { ex[4 * e] = contig[T.ex_contig[e]]; ex[4 * e + 1] = T.ex_start[e]; ex[4 * e + 2] = T.ex_end[e]; ex[4 * e + 3] = (uint32_t)T.ex_minus[e] << 31; }
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx, hipStreamSynchronize(s));                               // (nothing queued may still read the table that goes)
+    HIPCHK(ctx, ctx->d_tsb_first.ensure(T.exon_first.size() * 4 + 16)); HIPCHK(ctx, ctx->d_tsb_exons.ensure(E * 16 + 16));
+    HIPCHK(ctx, ctx->d_tsb_lits.ensure(lits.size() * 8 + 16)); HIPCHK(ctx, ctx->d_tsb_litpool.ensure(pool.size() + 16));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_tsb_first.p, T.exon_first.data(), T.exon_first.size() * 4, hipMemcpyHostToDevice, s));
+    if (E) HIPCHK(ctx, hipMemcpyAsync(ctx->d_tsb_exons.p, ex.data(), E * 16, hipMemcpyHostToDevice, s));
+    if (!lits.empty()) HIPCHK(ctx, hipMemcpyAsync(ctx->d_tsb_lits.p, lits.data(), lits.size() * 8, hipMemcpyHostToDevice, s));
+    if (!pool.empty()) HIPCHK(ctx, hipMemcpyAsync(ctx->d_tsb_litpool.p, pool.data(), pool.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    ctx->tsb_n_lits = lits.size() / 2; ctx->tsb_lit_bytes = pool.size();
+    ctx->tsb_dev_serial = T.serial; ctx->tsb_ref_version = ctx->ref_version;
+    return TKSMSEQ_OK;
+}
+
+// counts and scans of plan p on its context; fills the shared host copies when they are not there yet
+static int tsb_plan_device(tksmseq_tsb_plan* p) {
+    tksmseq_ctx* ctx = p->ctx;
+    TsbShared& S = *p->sh;
+    const uint64_t R = S.ab.rows();
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = tsb_table(ctx);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    TmpBuf d_tpm(s), d_depth(s), d_flag(s), d_nivl(s), d_idb(s);
+    HIPCHK(ctx, p->d_tx.ensure(R * 4 + 16)); HIPCHK(ctx, p->d_prefix.ensure(S.prefix.size() + 16));
+    for (DevBuf* b : {&p->d_rank, &p->d_mol_first, &p->d_ivl_first, &p->d_id_first}) { HIPCHK(ctx, b->ensure((R + 1) * 8 + 16)); HIPCHK(ctx, hipMemsetAsync(b->p, 0, 8, s)); }
+    if (!S.prefix.empty()) HIPCHK(ctx, hipMemcpyAsync(p->d_prefix.p, S.prefix.data(), S.prefix.size(), hipMemcpyHostToDevice, s));
+    if (R) {
+        HIPCHK(ctx, d_tpm.ensure(R * 8 + 16));
+        for (DevBuf* b : {&d_depth, &d_flag, &d_nivl, &d_idb}) HIPCHK(ctx, b->ensure(R * 8 + 16));
+        HIPCHK(ctx, ctx->w_scan.ensure(tk::scan_temp_bytes(R) + 64));
+        HIPCHK(ctx, hipMemcpyAsync(p->d_tx.p, S.ab.tx.data(), R * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(d_tpm.p, S.ab.tpm.data(), R * 8, hipMemcpyHostToDevice, s));
+        const tk::TsbCount C{S.seed, S.first_row, S.weight, S.molecule_count, S.ab.sum_tpm};
+        if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], s));
+        HIPCHK(ctx, tk::launch_tsb_count(R, C, p->d_tx.as<uint32_t>(), d_tpm.as<double>(), d_depth.as<uint64_t>(), d_flag.as<uint64_t>(), s));
+        HIPCHK(ctx, tk::launch_scan(d_flag.as<uint64_t>(), p->d_rank.as<uint64_t>(), R, ctx->w_scan.p, ctx->w_scan.cap, s));
+        HIPCHK(ctx, tk::launch_tsb_size(R, p->d_tx.as<uint32_t>(), ctx->d_tsb_first.as<uint32_t>(), d_depth.as<uint64_t>(), p->d_rank.as<uint64_t>(), (uint32_t)S.prefix.size(),
+                                        d_nivl.as<uint64_t>(), d_idb.as<uint64_t>(), s));
+        HIPCHK(ctx, tk::launch_scan(d_depth.as<uint64_t>(), p->d_mol_first.as<uint64_t>(), R, ctx->w_scan.p, ctx->w_scan.cap, s));
+        HIPCHK(ctx, tk::launch_scan(d_nivl.as<uint64_t>(), p->d_ivl_first.as<uint64_t>(), R, ctx->w_scan.p, ctx->w_scan.cap, s));
+        HIPCHK(ctx, tk::launch_scan(d_idb.as<uint64_t>(), p->d_id_first.as<uint64_t>(), R, ctx->w_scan.p, ctx->w_scan.cap, s));
+        if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[1], s));
+    }
+    if (S.mol_first.empty()) {
+        S.mol_first.assign(R + 1, 0); S.ivl_first.assign(R + 1, 0); S.id_first.assign(R + 1, 0);
+        HIPCHK(ctx, hipMemcpyAsync(S.mol_first.data(), p->d_mol_first.p, (R + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(S.ivl_first.data(), p->d_ivl_first.p, (R + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(S.id_first.data(), p->d_id_first.p, (R + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        for (uint64_t r = 0; r < R; r++) if (S.mol_first[r + 1] > S.mol_first[r]) S.emitted.push_back((uint32_t)r);
+    } else HIPCHK(ctx, hipStreamSynchronize(s));
+    ctx->tsb_plan_ms = 0.f;
+    if (ctx->timing && R) HIPCHK(ctx, hipEventElapsedTime(&ctx->tsb_plan_ms, ctx->ev[0], ctx->ev[1]));
+    return TKSMSEQ_OK;
+}
+
+static int ndig_host(uint64_t v) { int d = 1; while (v >= 10) { v /= 10; d++; } return d; }
+
+int tksmseq_transcripts_add_gtf(tksmseq_ctx* ctx, const char* path, int skip_non_coding) {
+    if (!ctx || !path) return TKSMSEQ_EINVAL;
+    static std::atomic<uint64_t> serial{0};
+    auto next = std::make_shared<tsb::Transcripts>(ctx->tsb ? *ctx->tsb : tsb::Transcripts());      // (plans and clones keep the table they have)
+    bool io = false;
+    if (!tsb::read_gtf(path, skip_non_coding != 0, *next, ctx->err, io)) return io ? TKSMSEQ_EIO : TKSMSEQ_EINVAL;
+    next->serial = ++serial;
+    ctx->tsb = std::move(next);
+    return TKSMSEQ_OK;
+}
+int tksmseq_transcripts_info(const tksmseq_ctx* ctx, uint64_t* n_transcripts, uint64_t* n_exons) {
+    if (!ctx) return TKSMSEQ_EINVAL;
+    if (n_transcripts) *n_transcripts = ctx->tsb ? ctx->tsb->n() : 0;
+    if (n_exons) *n_exons = ctx->tsb ? ctx->tsb->n_exons() : 0;
+    return TKSMSEQ_OK;
+}
+int tksmseq_transcripts_clear(tksmseq_ctx* ctx) {
+    if (!ctx) return TKSMSEQ_EINVAL;
+    ctx->tsb.reset(); ctx->tsb_dev_serial = 0;
+    return TKSMSEQ_OK;
+}
+
+int tksmseq_transcribe_plan_create(tksmseq_ctx* ctx, const char* abundance_path, const char* text, uint64_t len, const tksmseq_tsb_params* p, tksmseq_tsb_plan** out) {
+    if (!ctx || !p || !out || (!abundance_path && !text && len)) return TKSMSEQ_EINVAL;
+    *out = nullptr;
+    if (!ctx->tsb) { ctx->err = "transcribe: no GTF has been added (tksmseq_transcripts_add_gtf)"; return TKSMSEQ_ESTATE; }
+    if (!std::isfinite(p->weight)) { ctx->err = "transcribe: the weight of an abundance file must be finite"; return TKSMSEQ_EINVAL; }
+    std::string file;
+    if (abundance_path) {
+        FILE* f = fopen(abundance_path, "rb");
+        if (!f) { ctx->err = std::string("Could not open abundance file ") + abundance_path + "!"; return TKSMSEQ_EIO; }
+        char buf[1 << 16];
+        size_t n;
+        while ((n = fread(buf, 1, sizeof buf, f)) > 0) file.append(buf, n);
+        fclose(f);
+        text = file.data(); len = file.size();
+    }
+    std::unique_ptr<tksmseq_tsb_plan> plan(new tksmseq_tsb_plan());
+    plan->ctx = ctx;
+    plan->sh = std::make_shared<TsbShared>();
+    TsbShared& S = *plan->sh;
+    S.tx = ctx->tsb;
+    if (!tsb::parse_abundance(text, len, p->use_whole_id != 0, *S.tx, S.ab, ctx->err)) return TKSMSEQ_ELIMIT;
+    S.prefix = p->prefix ? p->prefix : "M";
+    if (S.prefix.size() > 4096) { ctx->err = "transcribe: a molecule prefix of more than 4096 bytes"; return TKSMSEQ_ELIMIT; }
+    S.seed = p->seed; S.first_row = p->first_row_index; S.weight = p->weight; S.molecule_count = (double)p->molecule_count;
+    const int rc = tsb_plan_device(plan.get());
+    if (rc) return rc;
+    *out = plan.release();
+    return TKSMSEQ_OK;
+}
+int tksmseq_transcribe_plan_clone(tksmseq_ctx* ctx, const tksmseq_tsb_plan* src, tksmseq_tsb_plan** out) {
+    if (!ctx || !src || !out) return TKSMSEQ_EINVAL;
+    *out = nullptr;
+    if (ctx->tsb != src->sh->tx) { ctx->err = "transcribe: the context does not hold the transcript table the plan was made with"; return TKSMSEQ_ESTATE; }
+    std::unique_ptr<tksmseq_tsb_plan> plan(new tksmseq_tsb_plan());
+    plan->ctx = ctx; plan->sh = src->sh;
+    const int rc = tsb_plan_device(plan.get());
+    if (rc) return rc;
+    *out = plan.release();
+    return TKSMSEQ_OK;
+}
+int tksmseq_transcribe_plan_info(const tksmseq_tsb_plan* plan, uint64_t* rows, uint64_t* records, uint64_t* molecules, uint64_t* missing) {
+    if (!plan) return TKSMSEQ_EINVAL;
+    const TsbShared& S = *plan->sh;
+    if (rows) *rows = S.ab.rows();
+    if (records) *records = S.emitted.size();
+    if (molecules) *molecules = S.mol_first.back();
+    if (missing) *missing = S.ab.missing_off.size();
+    return TKSMSEQ_OK;
+}
+int tksmseq_transcribe_plan_missing(const tksmseq_tsb_plan* plan, uint64_t i, const char** id, uint64_t* len) {
+    if (!plan || !id || !len || i >= plan->sh->ab.missing_off.size()) return TKSMSEQ_EINVAL;
+    const tsb::Abundance& A = plan->sh->ab;
+    *id = A.missing_off[i] == 0xffffffffu ? "BEG" : A.text.data() + A.missing_off[i];
+    *len = A.missing_len[i];
+    return TKSMSEQ_OK;
+}
+void tksmseq_transcribe_plan_free(tksmseq_tsb_plan* plan) {
+    if (!plan) return;
+    if (plan->ctx) { (void)hipSetDevice(plan->ctx->device); (void)hipStreamSynchronize(plan->ctx->stream); }
+    delete plan;
+}
+
+int tksmseq_transcribe(tksmseq_ctx* ctx, const tksmseq_tsb_plan* plan, uint64_t first_molecule, uint64_t n_molecules, int32_t flags, tksmseq_batch** out) {
+    if (!ctx || !plan || !out) return TKSMSEQ_EINVAL;
+    *out = nullptr;
+    if (n_molecules > (1ull << 28)) { ctx->err = "transcribe: more than 2^28 molecules in one call (split the range)"; return TKSMSEQ_ELIMIT; }
+    const TsbShared& S = *plan->sh;
+    if (plan->ctx != ctx) { ctx->err = "transcribe: the plan belongs to another context (tksmseq_transcribe_plan_clone makes one for this context)"; return TKSMSEQ_ESTATE; }
+    if (ctx->tsb != S.tx) { ctx->err = "transcribe: the transcript table has changed since the plan was made"; return TKSMSEQ_ESTATE; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = tsb_table(ctx);                                            // (the reference may have changed: contigs are resolved again)
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const tsb::Transcripts& T = *S.tx;
+    const uint64_t R = S.ab.rows(), total = S.mol_first.back();
+    const uint64_t m0 = std::min(first_molecule, total), n = std::min(n_molecules, total - m0), m1 = m0 + n;
+    auto exons_of = [&](uint64_t r) { const uint32_t t = S.ab.tx[r]; return (uint64_t)(T.exon_first[t + 1] - T.exon_first[t]); };
+    auto owner = [&](uint64_t m) { return (uint64_t)(std::upper_bound(S.mol_first.begin(), S.mol_first.end(), m) - S.mol_first.begin()) - 1; };
+    auto id_len = [&](uint64_t r) { return S.prefix.size() + (uint64_t)ndig_host((uint64_t)(std::lower_bound(S.emitted.begin(), S.emitted.end(), (uint32_t)r) - S.emitted.begin())); };
+    // where molecule m's intervals and id bytes start in the whole run's
+    auto bases = [&](uint64_t m, uint64_t& ivl, uint64_t& idb) {
+        if (m >= total) { ivl = S.ivl_first[R]; idb = S.id_first[R]; return; }
+        const uint64_t r = owner(m), copy = m - S.mol_first[r];
+        ivl = S.ivl_first[r] + copy * exons_of(r); idb = S.id_first[r] + copy * id_len(r);
+    };
+    uint64_t ivl0 = 0, id0 = 0, ivl1 = 0, id1 = 0;
+    if (n) { bases(m0, ivl0, id0); bases(m1, ivl1, id1); }
+    OutBatch b(ctx);
+    b.t_ivl = ivl1 - ivl0; b.t_mod = 0; b.t_id = id1 - id0;
+    if ((rc = b.alloc(n, "transcribe: ", "fewer molecules per call")) || (rc = b.literals(nullptr, ctx->tsb_n_lits, ctx->tsb_lit_bytes))) return rc;
+    if (ctx->tsb_n_lits) HIPCHK(ctx, hipMemcpyAsync(b->literals.p, ctx->d_tsb_lits.p, ctx->tsb_n_lits * 16, hipMemcpyDeviceToDevice, s));
+    if (ctx->tsb_lit_bytes) HIPCHK(ctx, hipMemcpyAsync(b->litpool.p, ctx->d_tsb_litpool.p, ctx->tsb_lit_bytes, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, b->d_dup.ensure(n * 4 + 16));
+    if (n) {
+        const tk::TsbPlanView V{R, plan->d_tx.as<uint32_t>(), plan->d_mol_first.as<uint64_t>(), plan->d_rank.as<uint64_t>(), plan->d_ivl_first.as<uint64_t>(),
+                                plan->d_id_first.as<uint64_t>(), ctx->d_tsb_first.as<uint32_t>(), ctx->d_tsb_exons.as<uint4>(), plan->d_prefix.as<uint8_t>(), (uint32_t)S.prefix.size()};
+        if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], s));
+        HIPCHK(ctx, tk::launch_tsb_write(V, m0, n, ivl0, b.t_ivl, id0, b.tables(), b->d_dup.as<uint32_t>(), s));
+        if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[1], s));
+        b->h_dup.resize(n);
+        HIPCHK(ctx, hipMemcpyAsync(b->h_dup.data(), b->d_dup.p, n * 4, hipMemcpyDeviceToHost, s));
+    }
+    if (!(flags & TKSMSEQ_MOL_NO_COMMENTS) && n) {
+        // the copies of a row share one comment: work per row touched, and one (offset, length) pair per molecule
+        b->h_comments.reserve(2 * n);
+        std::string c;
+        for (uint64_t r = owner(m0), m = m0; m < m1; r++) {
+            const uint64_t end = std::min(S.mol_first[r + 1], m1);
+            if (end <= m) continue;
+            const uint32_t t = S.ab.tx[r];
+            c.clear();
+            tsb::append_comment(c, S.ab.text.data() + S.ab.cb_off[r], S.ab.cb_len[r], T.id_pool.data() + T.id_off[t], T.id_len[t]);
+            if (b->h_comment_pool.size() + c.size() >= 0xffffffffull) { ctx->err = "transcribe: more than 4 GB of header comments in one batch (fewer molecules per call)"; return TKSMSEQ_ELIMIT; }
+            const uint32_t off = (uint32_t)b->h_comment_pool.size(), cl = (uint32_t)c.size();
+            b->h_comment_pool.insert(b->h_comment_pool.end(), c.begin(), c.end());
+            for (; m < end; m++) { b->h_comments.push_back(off); b->h_comments.push_back(cl); }
+        }
+    }
+    if ((rc = b.finish(out))) return rc;
+    ctx->tsb_write_ms = 0.f;
+    if (ctx->timing && n) HIPCHK(ctx, hipEventElapsedTime(&ctx->tsb_write_ms, ctx->ev[0], ctx->ev[1]));
+    return TKSMSEQ_OK;
+}
+
+int tksmseq_transcribe_device_ms(const tksmseq_ctx* ctx, float* plan_ms, float* write_ms) {
+    if (!ctx) return TKSMSEQ_EINVAL;
+    if (plan_ms) *plan_ms = ctx->tsb_plan_ms;
+    if (write_ms) *write_ms = ctx->tsb_write_ms;
+    return TKSMSEQ_OK;
+}
+
+int tksmseq_transcribe_text(const tksmseq_tsb_plan* plan, uint64_t first_record, uint64_t n_records, char** text, uint64_t* len) {
+    if (!plan || !text || !len) return TKSMSEQ_EINVAL;
+    *text = nullptr; *len = 0;
+    const TsbShared& S = *plan->sh;
+    const tsb::Transcripts& T = *S.tx;
+    const uint64_t k0 = std::min<uint64_t>(first_record, S.emitted.size()), k1 = k0 + std::min<uint64_t>(n_records, S.emitted.size() - k0);
+    std::string o;
+    char num[24];
+    auto put = [&](uint64_t v) { auto r = std::to_chars(num, num + sizeof num, v); o.append(num, r.ptr); };
+    for (uint64_t k = k0; k < k1; k++) {
+        const uint32_t r = S.emitted[k], t = S.ab.tx[r];
+        o += '+'; o += S.prefix; put(k); o += '\t'; put(S.mol_first[r + 1] - S.mol_first[r]); o += '\t';
+        tsb::append_comment(o, S.ab.text.data() + S.ab.cb_off[r], S.ab.cb_len[r], T.id_pool.data() + T.id_off[t], T.id_len[t]);
+        o += '\n';
+        for (uint32_t e = T.exon_first[t]; e < T.exon_first[t + 1]; e++) {
+            o += T.contig_names[T.ex_contig[e]]; o += '\t'; put(T.ex_start[e]); o += '\t'; put(T.ex_end[e]); o += T.ex_minus[e] ? "\t-\t\n" : "\t+\t\n";
+        }
+    }
+    char* buf = (char*)malloc(o.size() + 1);
+    if (!buf) return TKSMSEQ_ENOMEM;
+    memcpy(buf, o.data(), o.size()); buf[o.size()] = 0;
+    *text = buf; *len = o.size();
     return TKSMSEQ_OK;
 }
 

@@ -77,6 +77,14 @@ struct Args {
     long long wgs_base_count = 0; double wgs_depth = 0.0;
     uint64_t wgs_batch = 524288;                           // candidates per batch
     tksmseq_wgs_params wgs{};
+    // chained transcribe (src/transcribe.cpp:19-218) in place of -i: the molecules of the abundance tables' rows, made on the device of the
+    // context that sequences them.  tsb_texts: the tables themselves, read before any device is opened; tsb_w: every table's weight
+    bool tsb_on = false, tsb_have_count = false, tsb_use_whole_id = false;
+    std::vector<std::string> tsb_gtfs, tsb_abundances, tsb_texts;
+    std::vector<double> tsb_weights, tsb_w;
+    long long tsb_count = 0, tsb_default_depth = 0;
+    std::string tsb_prefix = "M";
+    uint64_t tsb_batch = 524288;                           // molecules per batch
 };
 
 void usage(FILE* f) {
@@ -90,7 +98,11 @@ void usage(FILE* f) {
             "                [--truncate-normal MU,SIGMA | --truncate-lognormal MU,SIGMA | --truncate-kde-model M.json\n"
             "                 [--truncate-always-end] [--truncate-kde-models-length]]\n"
             "       sequence -r REFERENCES --wgs-frag-len-dist \"NAME A [B]\" (--wgs-base-count N | --wgs-depth D) [--wgs-batch-molecules M]\n"
-            "                (no -i: whole-genome fragments made on the device; the other options as above)\n");
+            "                (no -i: whole-genome fragments made on the device; the other options as above)\n"
+            "       sequence -r REFERENCES --transcribe-gtf G[,G...] --transcribe-abundance A[,A...] --transcribe-molecule-count N\n"
+            "                [--transcribe-use-whole-id] [--transcribe-default-depth D] [--transcribe-molecule-prefix P]\n"
+            "                [--transcribe-weights W[,W...]] [--transcribe-batch-molecules M]\n"
+            "                (no -i: the molecules of `tksm transcribe` made on the device; not with --wgs-*, --pcr-* or --truncate-*)\n");
 }
 
 // argparse's parser.error(): the usage, the message, exit code 2
@@ -118,6 +130,15 @@ std::string truncate_mu_sigma(Args& a, const char* v, int mode) {
     if (!e || *e) return "expected MU,SIGMA";
     a.trc.mode = mode; a.trc_n++;
     return {};
+}
+
+void split_commas(const char* v, std::vector<std::string>& out) {       // cxxopts' vector<string>: every occurrence, split at ','
+    for (const char* q = v;;) {
+        const char* e = strchr(q, ',');
+        out.emplace_back(q, e ? (size_t)(e - q) : strlen(q));
+        if (!e) return;
+        q = e + 1;
+    }
 }
 
 #define SET(...) [](Args& a, const char* v) -> std::string { (void)v; __VA_ARGS__; return {}; }
@@ -163,6 +184,22 @@ const Option OPTIONS[] = {
     {"--wgs-batch-molecules", 0, true, nullptr, SET(
         if (!whole_number(v, a.wgs_batch) || a.wgs_batch < 1 || a.wgs_batch > (1ull << 28)) return "expected an integer between 1 and 268435456, got '" + std::string(v) + "'";
         a.wgs_on = true)},
+    {"--transcribe-gtf", 0, true, nullptr, SET(split_commas(v, a.tsb_gtfs); a.tsb_on = true)},
+    {"--transcribe-abundance", 0, true, nullptr, SET(split_commas(v, a.tsb_abundances); a.tsb_on = true)},
+    {"--transcribe-molecule-count", 0, true, nullptr, SET(
+        char* e = nullptr; a.tsb_count = strtoll(v, &e, 10);
+        if (e == v || *e || a.tsb_count < -2147483648ll || a.tsb_count > 2147483647ll) return "expected an integer, got '" + std::string(v) + "'";
+        a.tsb_have_count = true; a.tsb_on = true)},
+    {"--transcribe-use-whole-id", 0, false, nullptr, SET(a.tsb_use_whole_id = true; a.tsb_on = true)},
+    {"--transcribe-default-depth", 0, true, nullptr, SET(a.tsb_default_depth = atoll(v); a.tsb_on = true)},
+    {"--transcribe-molecule-prefix", 0, true, nullptr, SET(a.tsb_prefix = v; a.tsb_on = true)},
+    {"--transcribe-weights", 0, true, nullptr, SET(
+        std::vector<std::string> t; split_commas(v, t);
+        for (auto& x : t) { char* e = nullptr; const double w = strtod(x.c_str(), &e); if (e == x.c_str() || *e) return "expected numbers, got '" + std::string(v) + "'"; a.tsb_weights.push_back(w); }
+        a.tsb_on = true)},
+    {"--transcribe-batch-molecules", 0, true, nullptr, SET(
+        if (!whole_number(v, a.tsb_batch) || a.tsb_batch < 1 || a.tsb_batch > (1ull << 28)) return "expected an integer between 1 and 268435456, got '" + std::string(v) + "'";
+        a.tsb_on = true)},
     {"--verbosity", 0, true, "verbosity", SET(a.verbosity = v)},
     {"--log-file", 0, true, "log_file", SET(a.log_file = v)}};
 #undef SET
@@ -280,7 +317,7 @@ struct Writer {
     }
 };
 
-struct Chunk { uint64_t seq = 0, first_read = 0, n_reads = 0; std::vector<char> text; uint64_t t_begin = 0, t_end = 0; };   // text, or (chained PCR) a slice of the templates
+struct Chunk { uint64_t seq = 0, first_read = 0, n_reads = 0; std::vector<char> text; uint64_t t_begin = 0, t_end = 0; size_t table = 0; };   // text, or (chained PCR) a slice of the templates, or (chained transcribe) of an abundance table's molecules
 // a parsed batch on its way from a parser thread to a worker of the same device group
 struct Parsed { uint64_t seq = 0, first_read = 0, n_reads = 0; tksmseq_batch* b = nullptr; };
 struct GroupQueue {                                       // per device group: its parsers hand over in the order in which they took the chunks
@@ -344,6 +381,11 @@ struct Devices {
     std::vector<std::unique_ptr<Worker>> workers;
     std::vector<tksmseq_ctx*> pctx;                                      // the parser threads' contexts (clones)
     std::vector<tksmseq_batch*> templates;                               // chained PCR: the whole input, one batch per device group
+    // chained transcribe: every parser context's plan of every abundance table ([parser][table]; a group's tables are parsed once, its
+    // second parser shares the rows), and the tables' molecule counts
+    std::vector<std::vector<tksmseq_tsb_plan*>> tsb_plans;
+    std::vector<uint64_t> tsb_molecules;
+    std::vector<std::string> tsb_missing;                                // ids the GTFs lack, in row order
     std::string error;                                                   // why the set-up failed ("": it did not)
 
     Worker& first(int g) { return *workers[(size_t)g * per_group]; }
@@ -370,6 +412,36 @@ struct Devices {
         join_prefetch();
         for (auto& e : gerr) if (error.empty()) error = e;
         if (error.empty()) clone_parsers();
+        if (error.empty() && a.tsb_on) plan_transcribe();
+    }
+    void plan_transcribe() {
+        tsb_plans.assign(pctx.size(), std::vector<tksmseq_tsb_plan*>());
+        tsb_molecules.assign(a.tsb_texts.size(), 0);
+        uint64_t first_row = 0;
+        for (size_t f = 0; f < a.tsb_texts.size() && error.empty(); f++) {
+            tksmseq_tsb_params p{};
+            p.seed = (uint64_t)a.seed; p.molecule_count = a.tsb_count; p.weight = a.tsb_w[f]; p.first_row_index = first_row;
+            p.use_whole_id = a.tsb_use_whole_id ? 1 : 0; p.prefix = a.tsb_prefix.c_str();
+            uint64_t rows = 0;
+            for (size_t pi = 0; pi < pctx.size() && error.empty(); pi++) {
+                tksmseq_tsb_plan* plan = nullptr;
+                const bool first = pi % parsers_per_group == 0;
+                const int rc = first ? tksmseq_transcribe_plan_create(pctx[pi], nullptr, a.tsb_texts[f].data(), a.tsb_texts[f].size(), &p, &plan)
+                                     : tksmseq_transcribe_plan_clone(pctx[pi], tsb_plans[pi - pi % parsers_per_group][f], &plan);
+                if (rc) { error = std::string("Error: transcribe: ") + tksmseq_last_error(pctx[pi]); break; }
+                tsb_plans[pi].push_back(plan);
+                if (pi == 0) {
+                    uint64_t n_missing = 0;
+                    tksmseq_transcribe_plan_info(plan, &rows, nullptr, &tsb_molecules[f], &n_missing);
+                    for (uint64_t i = 0; i < n_missing; i++) {
+                        const char* id = nullptr; uint64_t len = 0;
+                        tksmseq_transcribe_plan_missing(plan, i, &id, &len);
+                        tsb_missing.emplace_back(id, (size_t)len);
+                    }
+                }
+            }
+            first_row += rows;
+        }
     }
     // the group's first context, with the reference and the models, and its clones; "": fine
     template <class Join> std::string load_group(int g, Join& join_prefetch) {
@@ -381,6 +453,8 @@ struct Devices {
             if (g == 0) { printf("Loading reference %s...\n", r.c_str()); fflush(stdout); }
             if (tksmseq_reference_add_fasta(ctx, r.c_str())) return fail("loading reference");
         }
+        for (auto& gtf : a.tsb_gtfs)                                      // (before the clones are made: they share the table)
+            if (tksmseq_transcripts_add_gtf(ctx, gtf.c_str(), a.tsb_default_depth != 0)) return fail("reading GTF");
         if (!a.badread.empty()) {
             join_prefetch();
             if (tksmseq_set_identity(ctx, a.mean, a.maxi, a.sd)) return fail("identity distribution");
@@ -408,6 +482,7 @@ struct Devices {
     // last back to the first (which holds the reference and the models)
     ~Devices() {
         for (int g = 0; g < n_groups; g++) if (templates[(size_t)g]) tksmseq_batch_free(parser(g), templates[(size_t)g]);
+        for (auto& plans : tsb_plans) for (auto* p : plans) tksmseq_transcribe_plan_free(p);
         for (auto& c : pctx) if (c) tksmseq_destroy(c);
         while (!workers.empty()) workers.pop_back();
     }
@@ -506,8 +581,8 @@ struct Stream {
     enum class Made { End, Nothing, Batch };             // End: the source is exhausted (or the run has failed)
     typedef void (Stream::*Feed)();
     typedef Made (Stream::*Next)(int pi, Parsed& pr, uint64_t& ticket);
-    Feed feed() const { return a.wgs_on ? &Stream::feed_wgs : a.pcr_on ? &Stream::feed_pcr_slices : &Stream::feed_text; }
-    Next next() const { return a.wgs_on ? &Stream::next_wgs : a.pcr_on ? &Stream::next_pcr_slice : &Stream::next_text; }
+    Feed feed() const { return a.wgs_on ? &Stream::feed_wgs : a.tsb_on ? &Stream::feed_transcribe : a.pcr_on ? &Stream::feed_pcr_slices : &Stream::feed_text; }
+    Next next() const { return a.wgs_on ? &Stream::next_wgs : a.tsb_on ? &Stream::next_transcribe : a.pcr_on ? &Stream::next_pcr_slice : &Stream::next_text; }
     GroupQueue& group_of_parser(int pi) { return *groups[(size_t)(pi / Devices::parsers_per_group)]; }
 
     // like fread(dst, 1, n, in): n bytes unless the input ends -- or the run has failed.  A pipe (Snakemake's `tksm ... | tksm sequence
@@ -573,6 +648,17 @@ struct Stream {
         if (!failed()) push_slice(u0, nt, acc);                  // the last slice (the only, empty one of an input without molecules)
     }
     void feed_wgs() {}                                           // nothing to read: the parser threads make the batches
+    // chained transcribe: consecutive slices of every table's unrolled molecules, tables in order; a read's global index is its
+    // molecule's position in that order, which is the order of the file `tksm transcribe` writes
+    void feed_transcribe() {
+        for (size_t f = 0; f < dev.tsb_molecules.size(); f++)
+            for (uint64_t m = 0; m < dev.tsb_molecules[f] && !failed(); m += a.tsb_batch) {
+                Chunk c;
+                c.table = f; c.t_begin = m; c.t_end = std::min(dev.tsb_molecules[f], m + a.tsb_batch);
+                const uint64_t n = c.t_end - c.t_begin;
+                push_chunk(std::move(c), n);
+            }
+    }
 
     bool take_chunk(int pi, Chunk& c, uint64_t& ticket) { return group_of_parser(pi).turn.take(ticket, [&] { return chunks.pop(c); }); }
     // --truncate-* behind the parse / the amplification; pr.b becomes the truncated batch
@@ -618,6 +704,17 @@ struct Stream {
         bool ok = !tksmseq_pcr(pc, dev.templates[(size_t)(pi / Devices::parsers_per_group)], &q, &pr.b) || ctx_error(pc);
         if (verbose2) fprintf(stderr, "[sequence] slice %llu parser %d: pcr %.3f s at %.3f s\n", (unsigned long long)c.seq, pi, seconds(t_parse), since_start());
         ok = ok && truncate(pc, pr);
+        return parsed(pi, pr, ok, t_parse);
+    }
+    Made next_transcribe(int pi, Parsed& pr, uint64_t& ticket) {
+        Chunk c;
+        if (!take_chunk(pi, c, ticket)) return Made::End;
+        if (failed()) return Made::Nothing;
+        pr.seq = c.seq; pr.first_read = c.first_read; pr.n_reads = c.n_reads;
+        tksmseq_ctx* pc = dev.pctx[(size_t)pi];
+        const auto t_parse = Clock::now();
+        // (Seq never reads header comments: no per-molecule text on the host)
+        const bool ok = !tksmseq_transcribe(pc, dev.tsb_plans[(size_t)pi][c.table], c.t_begin, c.t_end - c.t_begin, TKSMSEQ_MOL_NO_COMMENTS, &pr.b) || ctx_error(pc);
         return parsed(pi, pr, ok, t_parse);
     }
     // the next whole-genome batch, made under the lock of the serial state (the group's hand-over ticket is taken together with the
@@ -985,6 +1082,27 @@ class Sequencer_module::impl {
             if (bad_dist) return die(bad_dist == 1 ? "Invalid fragment length distribution" : "Invalid fragment length distribution parameters");
             a.wgs.dist = dist; a.wgs.seed = (uint64_t)a.seed;
         }
+        if (a.tsb_on) {
+            // validate_arguments (src/transcribe.cpp:90-108), process_file_weights (:65-77); the tables are read here, before any device
+            require(!a.tsb_gtfs.empty(), "Missing mandatory parameter gtf");
+            require(!a.tsb_abundances.empty(), "Missing mandatory parameter abundance");
+            require(a.tsb_have_count, "Missing mandatory parameter molecule-count");
+            if (missing) return 1;
+            if (a.tsb_weights.empty()) a.tsb_weights.push_back(1.0);
+            const size_t nf = a.tsb_abundances.size();
+            if (a.tsb_weights.size() != 1 && a.tsb_weights.size() != nf) return die("Error: --transcribe-weights takes one weight, or one per abundance file");
+            a.tsb_w.assign(nf, a.tsb_weights[0] / (double)nf);
+            if (a.tsb_weights.size() > 1) { double sum = 0.0; for (double w : a.tsb_weights) sum += w; for (size_t i = 0; i < nf; i++) a.tsb_w[i] = a.tsb_weights[i] / sum; }
+            for (auto& g : a.tsb_gtfs) { FILE* f = fopen(g.c_str(), "rb"); if (!f) return die("Could not open GTF file " + g + "!"); fclose(f); }
+            for (auto& t : a.tsb_abundances) {
+                FILE* f = fopen(t.c_str(), "rb");
+                if (!f) return die("Could not open abundance file " + t + "!");
+                a.tsb_texts.emplace_back();
+                char buf[1 << 16];
+                for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) a.tsb_texts.back().append(buf, n);
+                fclose(f);
+            }
+        }
         if (a.gzip != "host" && a.gzip != "device") return die("Error: --gzip must be 'host' or 'device', got '" + a.gzip + "'");
         if (a.trc_n > 1) return die("Only one of kde-model, normal or lognormal is allowed!");
         if (a.trc_n == 1) { a.trc.seed = (uint64_t)a.seed; if (a.trc.mode == TKSMSEQ_TRC_KDE) a.trc.kde_model_path = a.trc_kde.c_str(); }
@@ -998,7 +1116,10 @@ class Sequencer_module::impl {
         a.wgs_on = a.wgs_on || a.wgs_have_dist || a.wgs_have_bc || a.wgs_have_depth;
         if (a.wgs_on && !a.input.empty()) return usage_error("argument -i/--input: not allowed with the --wgs-* options (the molecules are made on the device)");
         if (a.wgs_on && (a.pcr_on || a.trc_n)) return usage_error("the --wgs-* options cannot be combined with --pcr-* / --truncate-*");
-        if (a.input.empty() && !a.wgs_on) return usage_error("the following arguments are required: -i/--input");
+        if (a.tsb_on && !a.input.empty()) return usage_error("argument -i/--input: not allowed with the --transcribe-* options (the molecules are made on the device)");
+        if (a.tsb_on && a.wgs_on) return usage_error("the --transcribe-* options cannot be combined with --wgs-*");
+        if (a.tsb_on && (a.pcr_on || a.trc_n)) return usage_error("the --transcribe-* options cannot be combined with --pcr-* / --truncate-*");
+        if (a.input.empty() && !a.wgs_on && !a.tsb_on) return usage_error("the following arguments are required: -i/--input");
         if (int rc = validate_identity(); rc != GO_ON) return rc;
         if (a.badread.empty() && a.perfect.empty()) return usage_error("Must specify either --output or --perfect.");
         if (int rc = validate_chained(); rc != GO_ON) return rc;
@@ -1043,7 +1164,8 @@ class Sequencer_module::impl {
             log.log(Logger::INFO, "Reference length: %llu; whole-genome fragments for %lld bases", (unsigned long long)ref_length, (long long)a.wgs.base_count);
         }
         Input in;
-        if (!a.wgs_on && !in.open(a.input)) return die("Error: cannot open " + a.input);
+        for (auto& id : dev.tsb_missing) log.log(Logger::WARN, "Isoform %s is not found in the input GTFs!", id.c_str());
+        if (!a.wgs_on && !a.tsb_on && !in.open(a.input)) return die("Error: cannot open " + a.input);
         std::string unopened;
         if (!out.open(a, unopened)) return die("Error: cannot open " + unopened);
         Stream s(a, log, dev, out, in, compute_q);

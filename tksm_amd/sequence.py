@@ -90,6 +90,50 @@ class RunResult:
         return ist, dst
 
 
+class TranscribePlan:
+    """One abundance table joined with the Sequencer's transcript table (tksmseq_transcribe_plan_create): .rows data rows, .records
+    emitted rows, .molecules the sum of their depths, .missing the ids the GTFs lack, in row order."""
+
+    def __init__(self, seq, handle):
+        self._seq, self._h = seq, handle
+        v = [C.c_uint64() for _ in range(4)]
+        seq._lib.tksmseq_transcribe_plan_info(handle, *[C.byref(x) for x in v])
+        self.rows, self.records, self.molecules, n_missing = [x.value for x in v]
+        self.missing = []
+        for i in range(n_missing):
+            p, n = C.c_void_p(), C.c_uint64()
+            seq._lib.tksmseq_transcribe_plan_missing(handle, i, C.byref(p), C.byref(n))
+            self.missing.append(C.string_at(p, n.value).decode())
+
+    def batch(self, first=0, n=None, comments=True):
+        """molecules [first, first + n) of the unrolled records as a batch on the device (tksmseq_transcribe); n None: all from first"""
+        n = max(0, self.molecules - first) if n is None else n
+        h = C.c_void_p()
+        self._seq._chk(self._seq._lib.tksmseq_transcribe(self._seq._ctx, self._h, int(first), int(n), 0 if comments else L.MOL_NO_COMMENTS, C.byref(h)))
+        return Batch(self._seq, h)
+
+    def mdf_text(self, first_record=0, n_records=None):
+        """the reference's own output: one record per emitted row with depth = its count (tksmseq_transcribe_text)"""
+        t, n = C.c_void_p(), C.c_uint64()
+        self._seq._chk(self._seq._lib.tksmseq_transcribe_text(self._h, int(first_record), self.records if n_records is None else int(n_records),
+                                                               C.byref(t), C.byref(n)))
+        try:
+            return C.string_at(t, n.value).decode()
+        finally:
+            self._seq._lib.tksmseq_text_free(t)
+
+    def close(self):
+        if self._h:
+            self._seq._lib.tksmseq_transcribe_plan_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Sequencer:
     """One context = one GPU (the reference's module globals: reference_seqs, identities, models).
 
@@ -392,6 +436,40 @@ class Sequencer:
         self._chk(self._lib.tksmseq_wgs(self._ctx, C.byref(p), C.byref(h), C.byref(pr)))
         return Batch(self, h), {"next_candidate": pr.next_candidate, "molecules": pr.molecules, "bases": pr.bases, "reached": bool(pr.reached)}
 
+    # ---- transcribe: GTF + abundance tables to molecules, expanded on the device
+    def add_gtf(self, path, skip_non_coding=False):
+        """read_gtf_transcripts_deep (src/gtf.h:274-304) into the context's transcript table (tksmseq_transcripts_add_gtf); ids the
+        table has stay.  skip_non_coding: what the reference passes --default-depth as (src/transcribe.cpp:136)."""
+        self._chk(self._lib.tksmseq_transcripts_add_gtf(self._ctx, str(path).encode(), 1 if skip_non_coding else 0))
+
+    def transcripts_info(self):
+        a, b = C.c_uint64(), C.c_uint64()
+        self._chk(self._lib.tksmseq_transcripts_info(self._ctx, C.byref(a), C.byref(b)))
+        return {"n_transcripts": a.value, "n_exons": b.value}
+
+    def clear_transcripts(self):
+        self._chk(self._lib.tksmseq_transcripts_clear(self._ctx))
+
+    def transcribe_plan(self, abundance, molecule_count, *, seed=42, weight=1.0, first_row_index=0, use_whole_id=False, prefix="M", text=None):
+        """The count loop of Splicer_module::run (src/transcribe.cpp:149-190) for one abundance table: `abundance` a path (or None with
+        text=: the table itself, str or bytes).  weight: this table's share (one table: 1); first_row_index: the data rows of the
+        tables before it.  Returns a TranscribePlan: .batch(first, n) makes molecules on the device, .mdf_text() the reference's file."""
+        p = L.TsbParams(int(seed), int(molecule_count), float(weight), int(first_row_index), 1 if use_whole_id else 0, 0, str(prefix).encode())
+        h = C.c_void_p()
+        if abundance is not None:
+            rc = self._lib.tksmseq_transcribe_plan_create(self._ctx, str(abundance).encode(), None, 0, C.byref(p), C.byref(h))
+        else:
+            raw = text.encode() if isinstance(text, str) else bytes(text)
+            rc = self._lib.tksmseq_transcribe_plan_create(self._ctx, None, raw, len(raw), C.byref(p), C.byref(h))
+        self._chk(rc)
+        return TranscribePlan(self, h)
+
+    def transcribe_device_ms(self):
+        """(plan ms, write ms): device time of the last transcribe_plan and of the last TranscribePlan.batch, with set_timing(True)"""
+        a, b = C.c_float(), C.c_float()
+        self._chk(self._lib.tksmseq_transcribe_device_ms(self._ctx, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def to_mdf_text(self, batch):
         """molecule_descriptor::operator<< of every molecule (src/interval.h:898-905)."""
         t, n = C.c_void_p(), C.c_uint64()
@@ -479,6 +557,13 @@ def random_wgs_main(argv):
     lib = L.load()
     arr = (C.c_char_p * len(argv))(*[a.encode() for a in argv])
     return lib.tksmseq_random_wgs_main(len(argv), arr)
+
+
+def transcribe_main(argv):
+    """`tksm transcribe ...` (src/tksm.cpp); argv[0] == "transcribe"."""
+    lib = L.load()
+    arr = (C.c_char_p * len(argv))(*[a.encode() for a in argv])
+    return lib.tksmseq_transcribe_main(len(argv), arr)
 
 
 def sequence_main(argv):
