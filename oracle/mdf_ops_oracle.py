@@ -149,6 +149,38 @@ def pcr_tables(cycles, efficiency, drop):
     return q, A
 
 
+PCR_TABLE_REL_ERR = 2.0 ** -24
+
+
+class PcrUnresolved(ValueError):
+    """the drop ratio is so small that the q / A tables do not resolve it: tksmseq_pcr answers TKSMSEQ_ELIMIT"""
+
+
+def pcr_table_error(cycles, efficiency, drop, tables=None):
+    """Bound on the relative error of the divisors 1 - q[t] and 1 - A[t] of the walk (pcr_setup in tksm_amd/csrc/mdf_ops.cpp has the same
+    recursion): every floating-point operation is exact up to a factor 1 +- u, u = 2^-53; eq, eA bound |computed - exact| of q[t], A[t].
+    Both divisors are differences of numbers near 1 -- 1 - q[cycles - 1] is the drop ratio itself -- so the bound is about
+    (5 / efficiency + 2) u / drop; at a drop ratio near u the divisors round to 0, pm / (1 - A[t]) is 0 / 0 and nothing is written."""
+    q, A = tables if tables is not None else pcr_tables(cycles, efficiency, drop)
+    # (the ratios below divide by the COMPUTED x and a, not the exact ones: with a ratio r the true relative error is at most r / (1 - r),
+    # which for r <= 2^-24 is r to 24 bits -- no matter for a limit that is a power of two chosen with two orders of magnitude to spare)
+    u = 2.0 ** -53
+    eA = rel = 0.0
+    for t in range(cycles - 1, -1, -1):
+        eq = eA + 2.0 * u
+        x = 1.0 - q[t]
+        ex = eq + u * x
+        y = efficiency * x
+        ey = efficiency * ex + u * y
+        z = 1.0 - y
+        ez = ey + u * abs(z)
+        eA = eA * abs(z) + (A[t + 1] + eA) * ez + u * A[t]
+        a = 1.0 - A[t]
+        if efficiency > 0.0 and drop > 0.0:                            # (else nothing is written, which is what the walk gives)
+            rel = max(rel, ex / x if x > 0.0 else math.inf, (eA + u * a) / a if a > 0.0 else math.inf)
+    return rel
+
+
 def pcr_mutations(seed, u, mask, rate, size):
     expected = rate * float(size)
     cnt = int(expected)
@@ -181,6 +213,10 @@ def pcr_spec(mols, cycles, efficiency, error_rate, target, seed, only=None):
     expected_after = math.pow(1 + efficiency, cycles) * float(len(keep))
     drop = min(1.0, target / expected_after) if expected_after > 0 else 0.0
     q, A = pcr_tables(cycles, efficiency, drop)
+    rel = pcr_table_error(cycles, efficiency, drop, (q, A))
+    if not rel <= PCR_TABLE_REL_ERR:
+        raise PcrUnresolved(f"{cycles} cycles at efficiency {efficiency} on {len(keep)} templates: drop ratio {drop:.3g}, relative error bound "
+                            f"{rel:.3g} of the probability tables above 2^-24")
     out = []
     for pos, u in enumerate(keep):
         if only is not None and not only[0] <= pos < only[1]:

@@ -10,6 +10,7 @@
 namespace tk {
 
 constexpr int PCR_MAX_CYCLES = 56;        // path masks are 56-bit (the RNG counter carries them)
+constexpr double PCR_TABLE_REL_ERR = 0x1p-24;   // bound on the relative error of 1 - q[t], 1 - A[t] above which a call is refused (pcr_setup)
 constexpr int PCR_MAX_MUT = 32;           // mutations of one copy event (rate x length is ~0.3 for Taq on 1 kb)
 
 struct PcrParams {

@@ -323,11 +323,37 @@ static int pcr_setup(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_pc
     if (P.drop > 1.0) P.drop = 1.0;
     const int c = p->cycles;
     P.A[c] = 1.0; P.A[c + 1] = 1.0;
+    // The kernels divide by 1 - q[t] and 1 - A[t].  Both are differences of numbers near 1, so the absolute rounding error of the tables
+    // becomes a RELATIVE error of those divisors that grows as the drop ratio shrinks (1 - q[cycles - 1] is the drop ratio itself); at a
+    // drop ratio near 2^-53 the divisors round to 0, pm / (1 - A[t]) is 0 / 0 and no copy is ever written.  A running bound of the
+    // absolute error goes along with the recursion (standard model: every operation is exact up to a factor 1 +- u, u = 2^-53; eq, eA
+    // bound |computed - exact| of q[t], A[t]), and a call whose divisors are not known to PCR_TABLE_REL_ERR = 2^-24 is refused.  A copy's
+    // path takes at most 2 x 56 decisions, so every expected count is then off by less than 112 x 2^-24 = 6.7e-6 of itself: one standard
+    // deviation of a count of 2.2e10 written copies (BASELINE config 5 writes 2e8).  The 32-bit uniforms the decisions are compared with
+    // quantise a probability p to 2^-32 / p of itself already, 7.7e-5 at config 5's drop ratio: far coarser.  ("PCR".)
+    // The ratios are taken against the COMPUTED divisors: with a ratio r the true relative error is at most r / (1 - r), r to 24 bits here.
+    // (Efficiency 0, or a drop ratio of 0 -- no templates, or a molecule count of 0: nothing is written, which is what the walk gives.)
+    const double u = 0x1p-53;
+    double eA = 0.0, rel = 0.0;
     for (int t = c - 1; t >= 0; t--) {
         P.q[t] = (1.0 - P.drop) * P.A[t + 1];
         P.A[t] = P.A[t + 1] * (1.0 - P.efficiency * (1.0 - P.q[t]));
+        const double eq = eA + 2.0 * u;                                 // 1 - drop: u; the product with A[t + 1] <= 1: eA + u
+        const double x = 1.0 - P.q[t], ex = eq + u * x;
+        const double y = P.efficiency * x, ey = P.efficiency * ex + u * y;
+        const double z = 1.0 - y, ez = ey + u * std::fabs(z);
+        eA = eA * std::fabs(z) + (P.A[t + 1] + eA) * ez + u * P.A[t];
+        const double a = 1.0 - P.A[t];
+        if (P.efficiency > 0.0 && P.drop > 0.0) rel = std::max(rel, std::max(x > 0.0 ? ex / x : INFINITY, a > 0.0 ? (eA + u * a) / a : INFINITY));
     }
     P.q[c] = 1.0;
+    if (!(rel <= tk::PCR_TABLE_REL_ERR)) {
+        char msg[320];
+        snprintf(msg, sizeof msg, "PCR: %d cycles at efficiency %g on %llu templates give a drop ratio of %.3g, which the copy-probability tables do not "
+                 "resolve (relative error bound %.3g, limit 2^-24): fewer cycles, or a larger molecule count", c, p->efficiency, (unsigned long long)n_kept, P.drop, rel);
+        ctx->err = msg;
+        return TKSMSEQ_ELIMIT;
+    }
     return TKSMSEQ_OK;
 }
 
