@@ -612,6 +612,78 @@ int tksmseq_model_truncation(tksmseq_ctx* ctx, const tksmseq_kde_model_params* p
  * --log-file.  Exit codes as argparse: 2 for a missing -i / -o or an unknown option, 1 for everything that fails later. */
 int tksmseq_model_truncation_main(int argc, char** argv);
 
+/* ---- abundance: transcript expression from a PAF by EM on the device -----------------------------------------------------------------------
+ * Replaces py/transcript_abundance.py (behind src/abundance.cpp): the table `tksm transcribe -a` reads.
+ *
+ * tksmseq_abundance is main() (:326-389).  The host reads the PAF (parse_paf :182-203: every line, columns 1, 2, 6, 8, 10, 11; reads and
+ * transcripts numbered in order of first appearance, a read's records all lines with its name in file order) and, per options, the lr-br
+ * table (parse_lr_bc_matches :166-179) or the whitelist.  On the device: get_compatibility (:210-256: the read length is the first record's;
+ * the best record is replaced on more matches, or as many and target_start < 20; a read whose best block length / read length is below 0.5
+ * is dropped; a record is a hit when matches / best matches > 0.95 in IEEE double and its full-length flag equals the best's; every hit
+ * starts at 1 / hits), em_iterations rounds of calculate_abundance + update_compatibility (:260-289), and calculate_split_abundance
+ * (:292-302) per (transcript, cell), rows in order of first appearance of the pair over the surviving reads and their hits.
+ *
+ * Ordered sums: no floating-point atomics anywhere.  The hits of a transcript (or pair), in read order, are cut into chunks of 1024; a chunk is
+ * 64 running sums (sum l takes positions l, l + 64, ...) folded by the tree 32, 16, ..., 1; a transcript's chunks are added in chunk order;
+ * the grand total is the transcripts' sums in transcript order through fixed trees of 256, their results in order the same way.  The result
+ * is a function of the input alone: the same bits on every run, device, clone and launch shape.  It is NOT the left-to-right order of the
+ * reference: abundances agree with it to rounding (tests: relative 1e-9), the printed %.3f values wherever no value sits on a rounding boundary.
+ *
+ * Cells: none of the options: every read is in cell ".".  lr_br_path: a read takes column 5 of the last line that names it with column 3
+ * == "1"; other reads ".".  cb_count > 0 (the reference draws from numpy's legacy generator in dict order; here counter-based, Philox4x32-10
+ * keyed by (seed, g, stream, n), words x, y, ...):
+ *   stream 57  barcode b, position p of cb_pattern: letter = set[umulhi32(x, |set|)], set the IUPAC letter's bases in the reference's order; (g, n) = (b, p)
+ *   stream 58  barcode b from the whitelist cb_txt_path (one per line): list[umulhi32(x, |list|)], with replacement; (g, n) = (b, 0)
+ *   stream 59  weight of barcode b: exp(mu + sigma z), z = sqrt(-2 ln((x + 1) / 2^32)) cos(2 pi y / 2^32); (g, n) = (b, 0)
+ *   stream 60  the cell of the k-th SURVIVING read: u = x / 2^32; the first barcode whose running weight sum (left to right; the last entry
+ *              is the dropout cell "." with (sum of weights x dropout) / (1 - dropout)) exceeds u x the total; (g, n) = (k, 0)
+ * Equal barcode strings are one cell.  dropout 1: every read is in ".".
+ *
+ * TKSMSEQ_EINVAL: the reference's argument checks (lr_br_path with cb_count; no pattern and no whitelist; a pattern letter outside IUPAC;
+ * dropout outside [0, 1]; sigma <= 0; a whitelist shorter than cb_count); a PAF line with fewer than 11 columns or a used column that is
+ * no integer in [0, 2^31) ("PAF line N: ..."); an lr-br line without exactly five columns; a read the reference ends on with a
+ * ZeroDivisionError -- a first record of length 0, or a best record with 0 matches behind the 0.5 gate -- named in tksmseq_last_error.
+ * TKSMSEQ_EIO: a file that cannot be read.  TKSMSEQ_ELIMIT: 2^31 reads, records, transcripts or barcodes, or more. */
+typedef struct tksmseq_abundance_result tksmseq_abundance_result;
+typedef struct tksmseq_abundance_params {
+    uint64_t seed;                   /* --random-seed (42): the --cb-count draws */
+    int32_t em_iterations;           /* -em/--em-iterations (10); 0 leaves the uniform split */
+    int32_t keep_hits;               /* != 0: the final hits stay readable through tksmseq_abundance_hits */
+    int64_t cb_count;                /* --cb-count (0) */
+    double cb_dropout;               /* --cb-dropout (0.2) */
+    double cb_mu, cb_sigma;          /* --cb-lognorm-params (10, 1) */
+    const char* cb_pattern;          /* --cb-pattern ("NNNNNNNNNNNN"); NULL: "" */
+    const char* cb_txt_path;         /* --cb-txt; NULL or "": none */
+    const char* lr_br_path;          /* -m/--lr-br; NULL or "": none */
+} tksmseq_abundance_params;
+int tksmseq_abundance(tksmseq_ctx* ctx, const tksmseq_abundance_params* params, const char* paf_path, tksmseq_abundance_result** out);
+/* rows: the rows the writer prints (tpm >= 0.001 and not "0.000"); surviving_reads: len(transcript_compatibility) (:371) */
+int tksmseq_abundance_info(const tksmseq_abundance_result* r, uint64_t* rows, uint64_t* surviving_reads, uint64_t* reads, uint64_t* transcripts, uint64_t* hits);
+/* row i: tpm = a x 1e6 as a double (the file has it as %.3f) */
+int tksmseq_abundance_row(const tksmseq_abundance_result* r, uint64_t i, const char** transcript, const char** cell, double* tpm);
+/* [transcripts], in order of first appearance in the PAF: the abundance of the last calculate_abundance of the EM loop, before the split
+ * (em_iterations 0: of the uniform split) */
+int tksmseq_abundance_vector(const tksmseq_abundance_result* r, const double** abundance);
+int tksmseq_abundance_transcript(const tksmseq_abundance_result* r, uint64_t t, const char** name);
+int tksmseq_abundance_cell(const tksmseq_abundance_result* r, uint64_t c, const char** name);
+/* read i in order of first appearance: its name, and whether it survived the 0.5 gate */
+int tksmseq_abundance_read(const tksmseq_abundance_result* r, uint64_t i, const char** name, int32_t* kept);
+/* keep_hits: surviving[k] = the read, cell[k] its cell (tksmseq_abundance_cell), and its hits [hit_offsets[k], hit_offsets[k + 1]) in record
+ * order: transcript and final weight.  TKSMSEQ_ESTATE without keep_hits. */
+int tksmseq_abundance_hits(const tksmseq_abundance_result* r, const uint32_t** surviving, const uint32_t** cell, const uint32_t** hit_offsets,
+                           const uint32_t** hit_transcript, const double** hit_weight);
+/* device time by HIP events: compatibility, index, the EM rounds and the split (uploads and downloads excluded) */
+int tksmseq_abundance_device_ms(const tksmseq_abundance_result* r, float* ms);
+/* "target_id\ttpm\tcell" and the rows (:373-388); gzipped (host zlib) when the name ends in .gz; written under a temporary name and renamed.
+ * TKSMSEQ_EIO when the file cannot be written; there is no context here, so tksmseq_last_error is NOT set: the caller names the path */
+int tksmseq_abundance_write(const tksmseq_abundance_result* r, const char* out_path);
+void tksmseq_abundance_free(tksmseq_abundance_result* r);
+/* `tksm abundance` (src/abundance.cpp, py/transcript_abundance.py:32-139): -p/--paf, -m/--lr-br, --cb-count, --cb-lognorm-params, --cb-pattern,
+ * --cb-dropout, --cb-txt, -o/--output, -em/--em-iterations, --random-seed, -v/--verbose, --list; here also --devices (the first entry is
+ * used), --verbosity, --log-file.  Exit codes as argparse: 2 for a missing -p / -o, an unknown option or a failed argument check
+ * ("abundance: error: ..."), 1 for everything that fails later.  Stdout: the reference's progress lines and "Parsed alignments for N reads". */
+int tksmseq_abundance_main(int argc, char** argv);
+
 /* The batch as MDF text, the way molecule_descriptor::operator<< writes it (src/interval.h:898-905): "+id<TAB>depth<TAB>comment",
  * then "chr<TAB>start<TAB>end<TAB>strand<TAB>pos<base>,..." per segment; depth 1 per molecule; comments re-serialised key-sorted
  * like dump_comment (:880-890).  *text is malloc'ed: release with tksmseq_text_free. */

@@ -118,6 +118,12 @@ class KdeModelParams(C.Structure):           # tksmseq_kde_model_params
                 ("end_ratio", C.c_double)]
 
 
+class AbundanceParams(C.Structure):        # tksmseq_abundance_params
+    _fields_ = [("seed", C.c_uint64), ("em_iterations", C.c_int32), ("keep_hits", C.c_int32), ("cb_count", C.c_int64), ("cb_dropout", C.c_double),
+                ("cb_mu", C.c_double), ("cb_sigma", C.c_double), ("cb_pattern", C.c_char_p), ("cb_txt_path", C.c_char_p), ("lr_br_path", C.c_char_p)]
+
+
+ABUND_CHUNK = 1024                           # hits per chunk partial of the abundance sums (abund_kernels.h)
 KDE_CHUNK = 4096                             # samples per partial grid of tksmseq_kde_grid (kde_kernels.h; doubled for large inputs)
 KDE_BANDWIDTHS = tuple(range(50, 1000, 100))
 
@@ -143,6 +149,9 @@ SYMBOLS = [
     "tksmseq_transcripts_add_gtf", "tksmseq_transcripts_info", "tksmseq_transcripts_clear", "tksmseq_transcribe_plan_create",
     "tksmseq_transcribe_plan_clone", "tksmseq_transcribe_plan_info", "tksmseq_transcribe_plan_missing", "tksmseq_transcribe_plan_free",
     "tksmseq_transcribe", "tksmseq_transcribe_text", "tksmseq_transcribe_main", "tksmseq_transcribe_device_ms",
+    "tksmseq_abundance", "tksmseq_abundance_info", "tksmseq_abundance_row", "tksmseq_abundance_vector", "tksmseq_abundance_transcript",
+    "tksmseq_abundance_cell", "tksmseq_abundance_read", "tksmseq_abundance_hits", "tksmseq_abundance_device_ms", "tksmseq_abundance_write",
+    "tksmseq_abundance_free", "tksmseq_abundance_main",
 ]
 
 _lib = None
@@ -240,6 +249,18 @@ def load():
         "tksmseq_transcribe_text": (C.c_int, [vp, u64, u64, P(vp), P(u64)]),
         "tksmseq_transcribe_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
         "tksmseq_transcribe_device_ms": (C.c_int, [vp, P(C.c_float), P(C.c_float)]),
+        "tksmseq_abundance": (C.c_int, [vp, P(AbundanceParams), C.c_char_p, P(vp)]),
+        "tksmseq_abundance_info": (C.c_int, [vp, P(u64), P(u64), P(u64), P(u64), P(u64)]),
+        "tksmseq_abundance_row": (C.c_int, [vp, u64, P(C.c_char_p), P(C.c_char_p), P(C.c_double)]),
+        "tksmseq_abundance_vector": (C.c_int, [vp, P(vp)]),
+        "tksmseq_abundance_transcript": (C.c_int, [vp, u64, P(C.c_char_p)]),
+        "tksmseq_abundance_cell": (C.c_int, [vp, u64, P(C.c_char_p)]),
+        "tksmseq_abundance_read": (C.c_int, [vp, u64, P(C.c_char_p), P(i32)]),
+        "tksmseq_abundance_hits": (C.c_int, [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]),
+        "tksmseq_abundance_device_ms": (C.c_int, [vp, P(C.c_float)]),
+        "tksmseq_abundance_write": (C.c_int, [vp, C.c_char_p]),
+        "tksmseq_abundance_free": (None, [vp]),
+        "tksmseq_abundance_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

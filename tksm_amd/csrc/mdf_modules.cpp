@@ -15,6 +15,7 @@
 //   AppendNoise_module      src/append_noise.cpp:131-229 --length-dist NAME,MU,SIGMA, --alphabet, --palindromic, --error-rate
 //   Splicer_module          src/transcribe.cpp:19-218 -g/--gtf, -a/--abundance, --molecule-count, -w/--weights, ... (no fusion submodule): GTF + TSV in, MDF out
 //   model-truncation        py/truncate_kde.py:36-112, :323-352 (behind src/model_truncation.cpp) PAF in, KDE model JSON out: no MDF, one context
+//   abundance               py/transcript_abundance.py:32-139, :326-389 (behind src/abundance.cpp) PAF in, expression TSV out: no MDF, one context
 //   utility flags           src/module.h:75-104      -s/--seed (default 42), --verbosity, --log-file, -h
 // All stream: `truncate` and the four segment edits read the input in batches of whole molecules (--batch-bytes), `pcr` amplifies its templates in slices
 // of about --slice-molecules output molecules (tksmseq_pcr_params::template_begin / _end); the pieces go round the entries of
@@ -39,6 +40,7 @@
 #include <vector>
 
 #include "../../include/tksmseq.h"
+#include "abund_host.h"
 #include "host.h"
 #include "kde_host.h"
 #include "module_log.h"
@@ -847,6 +849,90 @@ extern "C" int tksmseq_model_truncation_main(int argc, char** argv) {
         log.log(Logger::INFO, "model-truncation: %llu primary alignments, %llu end ratios, model written to %s in %.2f s", (unsigned long long)info.n_pairs,
                 (unsigned long long)info.n_ratios, c.output.c_str(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     }
+    tksmseq_destroy(ctx);
+    return rc ? 1 : 0;
+}
+
+// `tksm abundance`: the reference runs py/transcript_abundance.py (argparse: a missing -p / -o, an unknown option and a failed check of
+// parse_args :121-138 exit with 2 and "abundance: error: ..."; --list prints the option names and exits before anything is required).
+// One context on the first entry of --devices.  Stdout carries the script's progress lines (no progress bars).
+extern "C" int tksmseq_abundance_main(int argc, char** argv) {
+    Common c;
+    tksmseq_abundance_params p{};
+    p.seed = 42; p.em_iterations = 10; p.cb_dropout = 0.2; p.cb_mu = 10.0; p.cb_sigma = 1.0;
+    std::string paf, lr_br, pattern = "NNNNNNNNNNNN", txt, lognorm = "10,1";
+    long long verbose = 0;
+    bool list = false;
+    auto integer = [](const char* v, long long& out) { char* e = nullptr; out = strtoll(v, &e, 10); return e != v && !*e; };
+    auto real = [](const char* v, double& out) { char* e = nullptr; out = strtod(v, &e); return e != v && !*e; };
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            // (the common flags know -i, -s/--seed, --batch-bytes and --slice-molecules, which this module does not have)
+            if (o == "-i" || o == "--input" || o == "-s" || o == "--seed" || o == "--batch-bytes" || o == "--slice-molecules") return NO_SUCH;
+            if (o == "--list") { list = true; return TOOK_FLAG; }
+            long long iv = 0;
+            if ((o == "-p" || o == "--paf") && v) paf = v;
+            else if ((o == "-m" || o == "--lr-br") && v) lr_br = v;
+            else if (o == "--cb-count" && v) { if (!integer(v, iv)) return MALFORMED; p.cb_count = iv; }
+            else if (o == "--cb-lognorm-params" && v) lognorm = v;
+            else if (o == "--cb-pattern" && v) pattern = v;
+            else if (o == "--cb-dropout" && v) { if (!real(v, p.cb_dropout)) return MALFORMED; }
+            else if (o == "--cb-txt" && v) txt = v;
+            else if ((o == "-em" || o == "--em-iterations") && v) { if (!integer(v, iv) || iv < -2147483648ll || iv > 2147483647ll) return MALFORMED; p.em_iterations = (int32_t)iv; }
+            else if (o == "--random-seed" && v) { if (!integer(v, iv)) return MALFORMED; p.seed = (uint64_t)iv; }
+            else if ((o == "-v" || o == "--verbose") && v) { if (!integer(v, verbose)) return MALFORMED; }
+            else return NOT_MINE;
+            return TOOK_VALUE;
+        })) return 2;
+    if (list) { printf("help\npaf\nlr_br\ncb_count\ncb_lognorm_params\ncb_pattern\ncb_dropout\ncb_txt\noutput\nem_iterations\nrandom_seed\nverbose\nlist\ndevices\nverbosity\nlog_file\n"); return 0; }
+    if (c.help) { printf("Output a TSV file of the long-read trasncript expresion.\n"
+                         "usage: abundance -p PAF -o OUTPUT[.gz] [-m LR_BR] [--cb-count N] [--cb-lognorm-params MEAN,SD] [--cb-pattern NNNNNNNNNNNN] [--cb-dropout 0.2]\n"
+                         "                 [--cb-txt WHITELIST] [-em 10] [--random-seed 42] [-v 0] [--list] [--devices D] [--verbosity L] [--log-file F]\n"
+                         "--cb-count N > 0 splits the abundance over N simulated cell barcodes (seeded draws: include/tksmseq.h); not with --lr-br\n"); return 0; }
+    if (paf.empty() || c.output.empty()) {
+        fprintf(stderr, "abundance: error: the following arguments are required: %s%s%s\n", paf.empty() ? "-p/--paf" : "", paf.empty() && c.output.empty() ? ", " : "",
+                c.output.empty() ? "-o/--output" : "");
+        return 2;
+    }
+    if (p.cb_count > 0) {
+        const size_t comma = lognorm.find(',');
+        const bool two = comma != std::string::npos && lognorm.find(',', comma + 1) == std::string::npos;
+        if (!two || !real(lognorm.substr(0, comma).c_str(), p.cb_mu) || !real(lognorm.substr(comma + 1).c_str(), p.cb_sigma)) {
+            fprintf(stderr, "abundance: error: --cb-lognorm-params takes two comma-separated values: mean and standard deviation\n");
+            return 2;
+        }
+        std::string why;
+        if (!tkh::abund_check_args(p.cb_count, lr_br.c_str(), pattern.c_str(), txt.c_str(), p.cb_dropout, p.cb_mu, p.cb_sigma, why)) {
+            fprintf(stderr, "abundance: error: %s\n", why.c_str());
+            return 2;
+        }
+    }
+    Logger log;
+    if (!open_log(c, "abundance", log)) return 1;
+    p.cb_pattern = pattern.c_str(); p.cb_txt_path = txt.c_str(); p.lr_br_path = lr_br.c_str();
+    tksmseq_ctx* ctx = nullptr;
+    if (tksmseq_create(c.devices[0], &ctx)) { fprintf(stderr, "Error: %s\n", tksmseq_last_error(nullptr)); return 1; }
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!lr_br.empty() && p.cb_count <= 0) printf("Parsing LR barcode matches TSV...\n");
+    printf("Parsing PAF file...\n");
+    fflush(stdout);
+    tksmseq_abundance_result* res = nullptr;
+    int rc = tksmseq_abundance(ctx, &p, paf.c_str(), &res);
+    if (rc) fprintf(stderr, "Error: %s\n", tksmseq_last_error(ctx));
+    else {
+        uint64_t rows = 0, surviving = 0, reads = 0, transcripts = 0, hits = 0;
+        float ms = 0.f;
+        tksmseq_abundance_info(res, &rows, &surviving, &reads, &transcripts, &hits);
+        tksmseq_abundance_device_ms(res, &ms);
+        // (one library call does the three steps: their lines follow it, so a PAF that does not parse shows none of them)
+        printf("Computing compatibility of different alignments for each read...\nRunning EM...\nParsed alignments for %llu reads\n", (unsigned long long)surviving);
+        if ((rc = tksmseq_abundance_write(res, c.output.c_str()))) fprintf(stderr, "Error: cannot write %s\n", c.output.c_str());
+        else
+            log.log(Logger::INFO, "abundance: %llu reads (%llu kept, %llu hits) on %llu transcripts, %llu rows written to %s in %.2f s (device %.2f ms)",
+                    (unsigned long long)reads, (unsigned long long)surviving, (unsigned long long)hits, (unsigned long long)transcripts, (unsigned long long)rows,
+                    c.output.c_str(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), ms);
+        tksmseq_abundance_free(res);
+    }
+    fflush(stdout);
     tksmseq_destroy(ctx);
     return rc ? 1 : 0;
 }

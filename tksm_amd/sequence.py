@@ -417,6 +417,66 @@ class Sequencer:
                              float(end_ratio))
         self._chk(self._lib.tksmseq_model_truncation(self._ctx, C.byref(p), str(paf).encode(), str(out).encode()))
 
+    # ---- abundance: transcript expression from a PAF by EM on the device
+    def abundance(self, paf, out=None, em_iterations=10, lr_br=None, cb_count=0, cb_lognorm_params=(10.0, 1.0), cb_pattern="NNNNNNNNNNNN", cb_dropout=0.2,
+                  cb_txt=None, seed=42, keep_hits=False):
+        """main() of py/transcript_abundance.py (:326-389) on the device (tksmseq_abundance): the PAF of reads mapped to the transcriptome ->
+        {"names", "cells", "tpm": the rows the writer prints, in its order; "abundance": float64 per transcript (order of first appearance,
+        "transcripts") before the split; "surviving_reads"; "device_ms"}; the TSV (gzipped for .gz) is written when `out` is given.
+        keep_hits: also "reads" (names), "kept" (bool per read), "surviving" (read index), "read_cells" (cell string per surviving read),
+        "hit_offsets", "hit_transcripts", "hit_weights" (the final hits per surviving read, in record order)."""
+        mu, sigma = cb_lognorm_params
+        p = L.AbundanceParams(int(seed), int(em_iterations), 1 if keep_hits else 0, int(cb_count), float(cb_dropout), float(mu), float(sigma),
+                              str(cb_pattern).encode(), str(cb_txt).encode() if cb_txt else None, str(lr_br).encode() if lr_br else None)
+        h = C.c_void_p()
+        self._chk(self._lib.tksmseq_abundance(self._ctx, C.byref(p), str(paf).encode(), C.byref(h)))
+        try:
+            lib = self._lib
+            n = [C.c_uint64() for _ in range(5)]
+            lib.tksmseq_abundance_info(h, *[C.byref(v) for v in n])
+            rows, surviving, reads, transcripts, hits = [v.value for v in n]
+            names, cells, tpm = [], [], np.empty(rows, np.float64)
+            a, b, t = C.c_char_p(), C.c_char_p(), C.c_double()
+            for i in range(rows):
+                lib.tksmseq_abundance_row(h, i, C.byref(a), C.byref(b), C.byref(t))
+                names.append(a.value.decode()); cells.append(b.value.decode()); tpm[i] = t.value
+            tn = []
+            for i in range(transcripts):
+                lib.tksmseq_abundance_transcript(h, i, C.byref(a))
+                tn.append(a.value.decode())
+            vec = C.c_void_p()
+            lib.tksmseq_abundance_vector(h, C.byref(vec))
+            ms = C.c_float()
+            lib.tksmseq_abundance_device_ms(h, C.byref(ms))
+
+            def arr(ptr, count, dtype):
+                return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (count * np.dtype(dtype).itemsize,)).view(dtype).copy() if count else np.empty(0, dtype)
+            res = {"names": np.array(names, dtype=object), "cells": np.array(cells, dtype=object), "tpm": tpm, "transcripts": np.array(tn, dtype=object),
+                   "abundance": arr(vec, transcripts, np.float64), "surviving_reads": surviving, "device_ms": ms.value}
+            if keep_hits:
+                ptrs = [C.c_void_p() for _ in range(5)]
+                if lib.tksmseq_abundance_hits(h, *[C.byref(q) for q in ptrs]):
+                    raise TksmSeqError(L.ESTATE, "the hits were not kept")
+                k = C.c_int32()
+                rn, kept = [], np.zeros(reads, bool)
+                for i in range(reads):
+                    lib.tksmseq_abundance_read(h, i, C.byref(a), C.byref(k))
+                    rn.append(a.value.decode()); kept[i] = bool(k.value)
+                cell_ids = arr(ptrs[1], surviving, np.uint32)
+                cn = {}
+                for c in set(cell_ids.tolist()):
+                    lib.tksmseq_abundance_cell(h, c, C.byref(a))
+                    cn[c] = a.value.decode()
+                res.update(reads=np.array(rn, dtype=object), kept=kept, surviving=arr(ptrs[0], surviving, np.uint32),
+                           read_cells=np.array([cn[c] for c in cell_ids.tolist()], dtype=object),
+                           hit_offsets=arr(ptrs[2], surviving + 1 if surviving else 0, np.uint32), hit_transcripts=arr(ptrs[3], hits, np.uint32),
+                           hit_weights=arr(ptrs[4], hits, np.float64))
+            if out is not None and lib.tksmseq_abundance_write(h, str(out).encode()):
+                raise TksmSeqError(L.EIO, f"cannot write {out}")
+            return res
+        finally:
+            self._lib.tksmseq_abundance_free(h)
+
     # ---- random-wgs: whole-genome fragments made on the device
     def wgs(self, dist, a, b=0, base_count=None, depth=None, seed=42, first_candidate=0, n_candidates=1 << 20, state=None):
         """The loop of RWGS_module::run (src/random_wgs.cpp:181-207) for candidates [first_candidate, first_candidate + n_candidates)
