@@ -428,6 +428,60 @@ typedef struct {
 } tksmseq_flip_params;
 int tksmseq_flip(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_flip_params* params, tksmseq_batch** out);
 
+/* ---- filter and concat: split and join molecule batches on the device --------------------------------------------------------------------
+ * tksmseq_filter replaces the loop of Filter_module::run (src/filter.cpp:196-212) with FilterCondition (:21-117): a molecule of `in`
+ * (depth-unrolled, like every transform here; the predicate depends on the record alone, so the output is the unrolling of the
+ * reference's) goes to *out_true when ALL conditions hold -- inverted by negate -- and to *out_false otherwise, each side in input order,
+ * ids with their unroll suffix, each side with the input's literal table and its molecules' comments (none with
+ * TKSMSEQ_MOL_NO_COMMENTS).  out_false may be NULL: the false side is then neither sized nor written.  A side without molecules is an
+ * ordinary empty batch.  Conditions:
+ *   info KEY      the header comment has KEY with at least one value, the first of which is not "." (a bare key reads as ".");
+ *                 a batch without comments has no key
+ *   size OP N     OP one of < <= > >= == !=, against the sum of end - start over the molecule's segments (src/interval.h:876)
+ *   locus CHR     any segment's contig is CHR: a contig of the context, or a literal segment whose text is CHR
+ *   locus CHR:S-E, locus CHR:S   any segment on CHR with seg.overlap([S, E)) > 0, [S, S + 1) for the short form.  interval::overlap is
+ *                 kept as written (src/interval.h:38-58): a range that shares exactly one end with the segment and extends past the
+ *                 other (S < seg.start && E == seg.end, or S == seg.start && E > seg.end) overlaps by 0
+ * A condition is given parsed (kind INFO / SIZE / LOCUS) or as the reference's text (kind TEXT, e.g. "size >=200").  TKSMSEQ_EINVAL with
+ * "Invalid condition: <text>": a text that is not two space-separated fields, an unknown kind, a size expression shorter than two
+ * characters or with an unknown operator, a number std::stoi would not take, a negative size value or coordinate. */
+#define TKSMSEQ_FLT_TEXT 0
+#define TKSMSEQ_FLT_INFO 1
+#define TKSMSEQ_FLT_SIZE 2
+#define TKSMSEQ_FLT_LOCUS 3
+#define TKSMSEQ_FLT_LT 0
+#define TKSMSEQ_FLT_LE 1
+#define TKSMSEQ_FLT_GT 2
+#define TKSMSEQ_FLT_GE 3
+#define TKSMSEQ_FLT_EQ 4
+#define TKSMSEQ_FLT_NE 5
+typedef struct {
+    int32_t kind;                    /* TKSMSEQ_FLT_* */
+    int32_t cmp;                     /* SIZE: TKSMSEQ_FLT_LT .. TKSMSEQ_FLT_NE */
+    const char* text;                /* TEXT: the condition; INFO: the key; LOCUS: the contig name */
+    int64_t value;                   /* SIZE: N (0 .. 2^31 - 1) */
+    int64_t start, end;              /* LOCUS with ranged: [start, end) */
+    int32_t ranged;                  /* LOCUS: 0 any segment on the contig, 1 the range */
+    int32_t reserved;
+} tksmseq_filter_cond;
+typedef struct {
+    const tksmseq_filter_cond* conditions;
+    uint64_t n_conditions;           /* 0: every molecule is true (false with negate) */
+    int32_t negate;                  /* --negate */
+    int32_t flags;                   /* TKSMSEQ_MOL_NO_COMMENTS or 0 (`info` is still read from the input's comments) */
+} tksmseq_filter_params;
+int tksmseq_filter(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_filter_params* params, tksmseq_batch** out_true, tksmseq_batch** out_false);
+/* tksmseq_concat is what the Snakefile's Mrg rule does with `cat`: the molecules of in[0], then in[1], ... in one batch.  All inputs
+ * are batches of ctx.  Interval, substitution, literal and id indices are re-based, ids get their unroll suffix (the output has no
+ * depth > 1 molecule), the literal tables are concatenated.  Comments are concatenated unless flags has TKSMSEQ_MOL_NO_COMMENTS; an
+ * input without comments contributes empty ones when another input has them.  n_in 0 is TKSMSEQ_EINVAL, n_in 1 a copy; empty inputs
+ * may stand anywhere.  TKSMSEQ_ELIMIT: a result beyond the table limits of a batch. */
+int tksmseq_concat(tksmseq_ctx* ctx, const tksmseq_batch* const* in, uint64_t n_in, int32_t flags, tksmseq_batch** out);
+/* `tksm filter` (Filter_module src/filter.cpp:119-231): -i/--input, -t/--true-output, -f/--false-output, -c/--condition (repeatable,
+ * comma-separated), --negate; "Missing parameter: ..." and the help for a missing -i / -t / -c, exit codes 0 and 1; streamed in batches
+ * of --batch-bytes over --devices like `tksm polyA`.  There is no `tksm merge`: on files Mrg is `cat`. */
+int tksmseq_filter_main(int argc, char** argv);
+
 /* ---- tail-noise: random and hairpin noise appended on the device ----------------------------------------------------------------------
  * tksmseq_append_noise replaces NoiseAdder::operator() (src/append_noise.cpp:83-128; module AppendNoise_module :131-229) -- not to be
  * confused with the Badread tail-noise MODEL of tksmseq_load_tail_model.  Molecule i (depth-unrolled, like every segment edit; the

@@ -82,6 +82,18 @@ class FlipParams(C.Structure):
 PLA_GAMMA, PLA_POISSON, PLA_WEIBULL, PLA_NORMAL = 0, 1, 2, 3
 
 
+class FilterCond(C.Structure):               # tksmseq_filter_cond
+    _fields_ = [("kind", C.c_int32), ("cmp", C.c_int32), ("text", C.c_char_p), ("value", C.c_int64), ("start", C.c_int64), ("end", C.c_int64),
+                ("ranged", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FilterParams(C.Structure):             # tksmseq_filter_params
+    _fields_ = [("conditions", C.POINTER(FilterCond)), ("n_conditions", C.c_uint64), ("negate", C.c_int32), ("flags", C.c_int32)]
+
+
+FLT_TEXT, FLT_INFO, FLT_SIZE, FLT_LOCUS = 0, 1, 2, 3
+
+
 class WgsParams(C.Structure):                # tksmseq_wgs_params
     _fields_ = [("seed", C.c_uint64), ("dist", C.c_int32), ("reserved", C.c_int32), ("a", C.c_double), ("b", C.c_double),
                 ("base_count", C.c_int64), ("first_candidate", C.c_uint64), ("n_candidates", C.c_uint64),
@@ -152,6 +164,7 @@ SYMBOLS = [
     "tksmseq_abundance", "tksmseq_abundance_info", "tksmseq_abundance_row", "tksmseq_abundance_vector", "tksmseq_abundance_transcript",
     "tksmseq_abundance_cell", "tksmseq_abundance_read", "tksmseq_abundance_hits", "tksmseq_abundance_device_ms", "tksmseq_abundance_write",
     "tksmseq_abundance_free", "tksmseq_abundance_main",
+    "tksmseq_filter", "tksmseq_concat", "tksmseq_filter_main",
 ]
 
 _lib = None
@@ -261,6 +274,9 @@ def load():
         "tksmseq_abundance_write": (C.c_int, [vp, C.c_char_p]),
         "tksmseq_abundance_free": (None, [vp]),
         "tksmseq_abundance_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
+        "tksmseq_filter": (C.c_int, [vp, vp, P(FilterParams), P(vp), P(vp)]),
+        "tksmseq_concat": (C.c_int, [vp, P(vp), u64, i32, P(vp)]),
+        "tksmseq_filter_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

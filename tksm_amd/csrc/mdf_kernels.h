@@ -96,6 +96,32 @@ hipError_t launch_edit_count(const MolView& m, const uint32_t* pre, const uint32
 hipError_t launch_edit_write(const MolView& m, const uint32_t* pre, const uint32_t* post, const uint8_t* flip, const uint64_t* lits,
                              const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off, const MolOut& o, hipStream_t s);
 
+// filter (src/filter.cpp:21-117, :196-212): a two-way partition of a batch by a conjunction of conditions; see mdf_kernels.hip
+enum { FLT_SIZE = 1, FLT_LOCUS = 2 };     // (`info` conditions are read off the comments by the host: a byte per molecule)
+enum { FLT_LT = 0, FLT_LE = 1, FLT_GT = 2, FLT_GE = 3, FLT_EQ = 4, FLT_NE = 5 };
+struct FltCond {
+    int kind, cmp;                        // FLT_SIZE: cmp is FLT_LT .. FLT_NE, against value
+    long long value;
+    uint32_t contig;                      // FLT_LOCUS: the context's contig of that name, ~0: none
+    uint32_t name_len;                    // ... and the name itself, which a literal segment's text may equal (device)
+    const uint8_t* name;
+    int ranged;                           // 0: any segment on the contig; 1: one whose overlap with [start, end) is positive
+    long long start, end;
+};
+struct FltCounts { uint64_t *n_ivls, *n_mods, *n_idlen; };                    // per input molecule: its counts on this side, 0 on the other
+struct FltOffsets { const uint64_t *ivl, *mod, *id; };                        // their exclusive scans
+// side[r]: 1 when the conjunction (inverted by negate) holds; flag[r] the same as a scan input; f.n_ivls null: no false side is sized
+hipError_t launch_flt_pred(const MolView& m, const FltCond* conds, uint32_t n_conds, const uint8_t* info, int negate, uint8_t* side, uint64_t* flag,
+                           const FltCounts& t, const FltCounts& f, hipStream_t s);
+// rank: exclusive scan of flag; f.ivl null: molecules of the false side are not written (of is not touched)
+hipError_t launch_flt_write(const MolView& m, const uint8_t* side, const uint64_t* rank, const FltOffsets& t, const FltOffsets& f, const MolOut& ot,
+                            const MolOut& of, hipStream_t s);
+// concat: where one input's molecules, intervals, substitutions, id bytes, literal entries and literal pool bytes start in the output
+struct CatBase { uint64_t mol, ivl, mod, id; uint32_t lit; uint64_t pool; };
+// ivl_off / mod_off / id_off: scans of the input's own counts (launch_edit_count without literals); lits: the output's literal table
+hipError_t launch_cat_write(const MolView& m, const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off, const CatBase& base, uint64_t* lits,
+                            const MolOut& o, hipStream_t s);
+
 // random-wgs (src/random_wgs.cpp:181-207): fragments of the whole genome, one lane per candidate; see mdf_kernels.hip
 constexpr int WGS_LDS_CONTIGS = 2048;       // running sums of that many contigs are searched in LDS (16 KB), more in global memory
 enum { WGS_NORMAL = 0, WGS_UNIFORM = 1, WGS_LOGNORMAL = 2, WGS_EXPONENTIAL = 3 };

@@ -934,6 +934,109 @@ __global__ void __launch_bounds__(256) k_tsb_write(TsbPlanView V, uint64_t first
 }
 
 // ------------------------------------------------------------------------------------------------
+// filter (Flt, src/filter.cpp:21-117, :196-212) and concat (Mrg: `cat` of MDF files).  Both move whole molecules and draw nothing.
+// k_flt_pred: one lane per unrolled molecule evaluates the conjunction -- `info` comes in as a byte per molecule (the host reads the
+// comments), `size` and `locus` are computed here -- and writes the molecule's side, its rank flag and its three counts into the
+// arrays of its side (0 into the other side's).  The scans of those give every molecule its slot; k_flt_write copies it there.
+// k_cat_write copies one input of a concatenation behind the inputs before it: every index it carries is re-based.
+// Kept quirk of the reference: interval::overlap (src/interval.h:38-58) has six branches and falls through to 0 for a range that
+// shares exactly one end with the segment and sticks out on the other side (range.start < seg.start && range.end == seg.end;
+// range.start == seg.start && range.end > seg.end), so `locus` misses those two overlaps.
+// ------------------------------------------------------------------------------------------------
+// this = [s, e) the segment, other = [os, oe) the range of the condition
+DEV long long flt_overlap(long long s, long long e, long long os, long long oe) {
+    if (oe <= s) return 0;                                            // BEFORE
+    else if (os >= e) return 0;                                       // AFTER
+    else if (os >= s && oe <= e) return oe - os;                      // IN
+    else if (os < s && oe > e) return e - s;                          // AROUND
+    else if (os < s && oe < e && oe > s) return oe - s;               // LEFT OVERLAP
+    else if (os > s && os < e && oe > e) return e - os;               // RIGHT OVERLAP
+    return 0;
+}
+
+// seg.chr == chr: a contig by its index, a literal by its text (the reference compares strings)
+DEV bool flt_on_contig(const BatchView& B, uint32_t c, const FltCond& C) {
+    if (!(c >> 31)) return c == C.contig;
+    const uint32_t li = c & 0x7fffffffu;
+    if (B.literals[2ull * li + 1] != (uint64_t)C.name_len) return false;
+    const uint8_t* t = B.litpool + B.literals[2ull * li];
+    for (uint32_t k = 0; k < C.name_len; k++) if (t[k] != C.name[k]) return false;
+    return true;
+}
+
+DEV bool flt_holds(const BatchView& B, uint32_t r, const FltCond& C) {
+    const uint32_t ib = B.reads[2 * r], ic = B.reads[2 * r + 1];
+    if (C.kind == FLT_SIZE) {
+        unsigned long long sz = 0;                                     // molecule_descriptor::size, src/interval.h:876
+        for (uint32_t i = 0; i < ic; i++) sz += seg_size(B.intervals + 4ull * (ib + i));
+        const unsigned long long v = (unsigned long long)C.value;
+        switch (C.cmp) {
+            case FLT_LT: return sz < v;   case FLT_LE: return sz <= v;   case FLT_GT: return sz > v;
+            case FLT_GE: return sz >= v;  case FLT_EQ: return sz == v;   default: return sz != v;
+        }
+    }
+    for (uint32_t i = 0; i < ic; i++) {                               // FLT_LOCUS: any segment (src/filter.cpp:89-112)
+        const uint32_t* iv = B.intervals + 4ull * (ib + i);
+        if (!flt_on_contig(B, iv[0], C)) continue;
+        if (!C.ranged || flt_overlap((long long)iv[1], (long long)iv[2], C.start, C.end) > 0) return true;
+    }
+    return false;
+}
+
+__global__ void k_flt_pred(MolView M, const FltCond* __restrict__ conds, uint32_t n_conds, const uint8_t* __restrict__ info, int negate,
+                           uint8_t* __restrict__ side, uint64_t* __restrict__ flag, FltCounts T, FltCounts F) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= M.B.n_reads) return;
+    bool ok = info ? info[r] != 0 : true;
+    for (uint32_t c = 0; c < n_conds && ok; c++) ok = flt_holds(M.B, (uint32_t)r, conds[c]);
+    if (negate) ok = !ok;
+    side[r] = ok ? 1 : 0;
+    flag[r] = ok ? 1ull : 0ull;
+    const uint64_t ni = M.B.reads[2 * r + 1], nm = mol_mods(M.B, (uint32_t)r), nd = unrolled_id_len(M, r);
+    T.n_ivls[r] = ok ? ni : 0ull; T.n_mods[r] = ok ? nm : 0ull; T.n_idlen[r] = ok ? nd : 0ull;
+    if (F.n_ivls) { F.n_ivls[r] = ok ? 0ull : ni; F.n_mods[r] = ok ? 0ull : nm; F.n_idlen[r] = ok ? 0ull : nd; }
+}
+
+// molecule r of M becomes molecule j of O: intervals from io, substitutions from mo, id bytes (with the unroll suffix) at id_at;
+// literal indices move up by lit_shift
+DEV void copy_molecule(const MolView& M, uint64_t r, uint64_t j, uint64_t io, uint64_t mo, uint64_t id_at, uint32_t lit_shift, const MolOut& O) {
+    const BatchView& B = M.B;
+    const uint32_t ib = B.reads[2 * r], ic = B.reads[2 * r + 1];
+    O.reads[2 * j] = (uint32_t)io; O.reads[2 * j + 1] = ic;
+    {
+        uint8_t* d = O.idpool + id_at;
+        const uint32_t so = B.ids[2 * r], sl = B.ids[2 * r + 1];
+        uint32_t k = 0;
+        for (; k < sl; k++) d[k] = B.idpool[so + k];
+        if (M.dup && (M.dup[r] >> 31)) { d[k++] = '_'; k += (uint32_t)put_dec(d + k, M.dup[r] & 0x7fffffffu); }
+        O.ids[2 * j] = (uint32_t)id_at; O.ids[2 * j + 1] = k;
+    }
+    for (uint32_t i = 0; i < ic; i++) {
+        const uint32_t* iv = B.intervals + 4ull * (ib + i);
+        uint32_t* ov = O.intervals + 4ull * io++;
+        ov[0] = (iv[0] >> 31) ? iv[0] + lit_shift : iv[0]; ov[1] = iv[1]; ov[2] = iv[2]; ov[3] = (uint32_t)mo | (iv[3] & 0x80000000u);
+        const uint32_t mb = iv[3] & 0x7fffffffu, me = iv[7] & 0x7fffffffu;
+        for (uint32_t m = mb; m < me; m++) { O.mods[2 * mo] = B.mods[2ull * m]; O.mods[2 * mo + 1] = B.mods[2ull * m + 1]; mo++; }
+    }
+}
+
+// rank: exclusive scan of flag (molecules of the true side before r); T / F: the scans of the counts; OF is not touched without F
+__global__ void k_flt_write(MolView M, const uint8_t* __restrict__ side, const uint64_t* __restrict__ rank, FltOffsets T, FltOffsets F, MolOut OT, MolOut OF) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= M.B.n_reads) return;
+    if (side[r]) copy_molecule(M, r, rank[r], T.ivl[r], T.mod[r], T.id[r], 0u, OT);
+    else if (F.ivl) copy_molecule(M, r, r - rank[r], F.ivl[r], F.mod[r], F.id[r], 0u, OF);
+}
+
+// one input of a concatenation: its molecules (lanes below n_reads) and its literal entries (lanes below n_literals)
+__global__ void k_cat_write(MolView M, const uint64_t* __restrict__ ivl_off, const uint64_t* __restrict__ mod_off, const uint64_t* __restrict__ id_off,
+                            CatBase base, uint64_t* __restrict__ lits, MolOut O) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < M.B.n_reads) copy_molecule(M, r, base.mol + r, base.ivl + ivl_off[r], base.mod + mod_off[r], base.id + id_off[r], base.lit, O);
+    if (r < M.B.n_literals) { lits[2ull * (base.lit + r)] = M.B.literals[2 * r] + base.pool; lits[2ull * (base.lit + r) + 1] = M.B.literals[2 * r + 1]; }
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
 static inline unsigned nblk(uint64_t n) { return (unsigned)((n + 127) / 128); }
@@ -994,6 +1097,26 @@ hipError_t launch_edit_write(const MolView& m, const uint32_t* pre, const uint32
                              const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off, const MolOut& o, hipStream_t s) {
     if (!m.B.n_reads) return hipSuccess;
     hipLaunchKernelGGL(k_edit_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, pre, post, flip, lits, ivl_off, mod_off, id_off, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_flt_pred(const MolView& m, const FltCond* conds, uint32_t n_conds, const uint8_t* info, int negate, uint8_t* side, uint64_t* flag,
+                           const FltCounts& t, const FltCounts& f, hipStream_t s) {
+    if (!m.B.n_reads) return hipSuccess;
+    hipLaunchKernelGGL(k_flt_pred, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, conds, n_conds, info, negate, side, flag, t, f);
+    return hipGetLastError();
+}
+hipError_t launch_flt_write(const MolView& m, const uint8_t* side, const uint64_t* rank, const FltOffsets& t, const FltOffsets& f, const MolOut& ot,
+                            const MolOut& of, hipStream_t s) {
+    if (!m.B.n_reads) return hipSuccess;
+    hipLaunchKernelGGL(k_flt_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, side, rank, t, f, ot, of);
+    return hipGetLastError();
+}
+hipError_t launch_cat_write(const MolView& m, const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off, const CatBase& base, uint64_t* lits,
+                            const MolOut& o, hipStream_t s) {
+    const uint64_t n = m.B.n_reads > m.B.n_literals ? m.B.n_reads : (uint64_t)m.B.n_literals;
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_cat_write, dim3(nblk(n)), dim3(128), 0, s, m, ivl_off, mod_off, id_off, base, lits, o);
     return hipGetLastError();
 }
 

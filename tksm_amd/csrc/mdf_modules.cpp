@@ -1,5 +1,5 @@
-// mdf_modules.cpp -- the `tksm pcr`, `truncate`, `polyA`, `tag`, `scb`, `flip` and `tail-noise` modules on top of the C-ABI (MDF file in, MDF
-// file out), and `random-wgs` (no input: MDF file out).
+// mdf_modules.cpp -- the `tksm pcr`, `truncate`, `polyA`, `tag`, `scb`, `flip`, `tail-noise` and `filter` (two outputs) modules on top of the
+// C-ABI (MDF file in, MDF file out), and `random-wgs` (no input: MDF file out).
 //
 // Mirrors (file:line into vpc-ccg/tksm):
 //   PCR_module::impl        src/pcr.cpp:91-260       flags -i -o --molecule-count --cycles --error-rate --efficiency -x/--preset,
@@ -13,6 +13,7 @@
 //   StrandMan_module        src/strand_man.cpp:20-124 -p/--flip-probability (outside [0, 1]: logged, not refused)
 //   RWGS_module             src/random_wgs.cpp:24-229 -r/--reference, --frag-len-dist "NAME A [B]", -o, --base-count | --depth
 //   AppendNoise_module      src/append_noise.cpp:131-229 --length-dist NAME,MU,SIGMA, --alphabet, --palindromic, --error-rate
+//   Filter_module           src/filter.cpp:119-231   -i, -t/--true-output, -f/--false-output, -c/--condition (comma-separated, repeatable), --negate
 //   Splicer_module          src/transcribe.cpp:19-218 -g/--gtf, -a/--abundance, --molecule-count, -w/--weights, ... (no fusion submodule): GTF + TSV in, MDF out
 //   model-truncation        py/truncate_kde.py:36-112, :323-352 (behind src/model_truncation.cpp) PAF in, KDE model JSON out: no MDF, one context
 //   abundance               py/transcript_abundance.py:32-139, :326-389 (behind src/abundance.cpp) PAF in, expression TSV out: no MDF, one context
@@ -41,6 +42,7 @@
 
 #include "../../include/tksmseq.h"
 #include "abund_host.h"
+#include "filter_host.h"
 #include "host.h"
 #include "kde_host.h"
 #include "module_log.h"
@@ -130,7 +132,8 @@ struct OrderedOut {
 };
 
 // truncate: text + first molecule index; pcr: template slice; error: set by a work() that fails for a reason of its own (not the library's)
-struct Piece { uint64_t seq = 0, first = 0, begin = 0, end = 0; std::vector<char> text; std::string error; };
+// second: filter's false side, written to the second output (null: nothing for it)
+struct Piece { uint64_t seq = 0, first = 0, begin = 0, end = 0; std::vector<char> text; std::string error; tksmseq_batch* second = nullptr; };
 
 // The common engine: `n_ctx` worker threads (two per entry of --devices), each with a context of its own; prepare() runs once per
 // context (pcr: parse the templates), pieces come from next_piece() (serialised), work() turns one into a batch, whose MDF text is
@@ -138,13 +141,14 @@ struct Piece { uint64_t seq = 0, first = 0, begin = 0, end = 0; std::vector<char
 // ended; only the text is made in parallel).  summary(): what the closing log line says between the molecule count and the time.
 template <class Prepare, class Next, class Work>
 int run_pieces(const Common& c, Logger& log, const char* what, Prepare prepare, Next next_piece, Work work, bool serial_work = false,
-               std::function<std::string()> summary = nullptr) {
-    OrderedOut out;
+               std::function<std::string()> summary = nullptr, const std::string* second_output = nullptr) {
+    OrderedOut out, out2;                                       // out2: the second ordered sink (filter's false side), same piece numbers
     out.f = fopen(c.output.c_str(), "wb");
     if (!out.f) { fprintf(stderr, "Error: cannot write %s\n", c.output.c_str()); return 1; }
+    if (second_output && !(out2.f = fopen(second_output->c_str(), "wb"))) { fprintf(stderr, "Error: cannot write %s\n", second_output->c_str()); fclose(out.f); return 1; }
     const int per_device = 2, n_ctx = (int)c.devices.size() * per_device;
     std::mutex err_m, next_m; std::string first_error; std::atomic<bool> failed{false};
-    auto set_error = [&](const std::string& e) { std::lock_guard<std::mutex> l(err_m); if (!failed.exchange(true)) first_error = e; out.fail(); };
+    auto set_error = [&](const std::string& e) { std::lock_guard<std::mutex> l(err_m); if (!failed.exchange(true)) first_error = e; out.fail(); out2.fail(); };
     std::atomic<uint64_t> molecules{0};
     const auto t0 = std::chrono::steady_clock::now();
     auto worker = [&](int wi) {
@@ -173,9 +177,16 @@ int run_pieces(const Common& c, Logger& log, const char* what, Prepare prepare, 
                 molecules += n;
                 log.log(Logger::DEBUG, "piece %llu: %llu molecules, %.1f MB of text (context %d)", (unsigned long long)p.seq, (unsigned long long)n, len / 1e6, wi);
                 if (!out.put(p.seq, text, len) && !failed) set_error("cannot write " + c.output);
+                if (out2.f && !failed) {
+                    char* text2 = nullptr; uint64_t len2 = 0;
+                    if (p.second && tksmseq_batch_to_mdf_text(ctx, p.second, &text2, &len2)) set_error(std::string(what) + ": " + tksmseq_last_error(ctx));
+                    else if (!out2.put(p.seq, text2, len2) && !failed) set_error("cannot write " + *second_output);
+                    tksmseq_text_free(text2);
+                }
             }
             tksmseq_text_free(text);
             if (b) tksmseq_batch_free(ctx, b);
+            if (p.second) tksmseq_batch_free(ctx, p.second);
         }
         if (state) prepare(ctx, &state);                        // (second call: releases what the first one made)
         tksmseq_destroy(ctx);
@@ -183,20 +194,19 @@ int run_pieces(const Common& c, Logger& log, const char* what, Prepare prepare, 
     std::vector<std::thread> th;
     for (int w = 0; w < n_ctx; w++) th.emplace_back(worker, w);
     for (auto& t : th) t.join();
-    const bool close_ok = fclose(out.f) == 0;
+    bool close_ok = fclose(out.f) == 0;
+    if (out2.f && fclose(out2.f) != 0) close_ok = false;
     if (failed) { fprintf(stderr, "Error: %s\n", first_error.c_str()); return 1; }
-    if (!close_ok || out.failed) { fprintf(stderr, "Error: cannot write %s\n", c.output.c_str()); return 1; }
+    if (!close_ok || out.failed || out2.failed) { fprintf(stderr, "Error: cannot write %s\n", c.output.c_str()); return 1; }
     log.log(Logger::INFO, "%s: %llu molecules%s written in %.2f s (%d device group(s))", what, (unsigned long long)molecules.load(), summary ? summary().c_str() : "",
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), (int)c.devices.size());
     return 0;
 }
 
-// A stream transform (truncate, polyA, tag, scb, flip, tail-noise): the input in pieces of whole molecules, fn(ctx, batch, parameters, out)
-// on each -- the parameters are p with the index of the piece's first molecule in p.*first_index (null: fn numbers nothing) -- and the
-// outputs written in input order.
-template <class P>
-int stream_transform(const Common& c, Logger& log, const char* what, const P& p, int (*fn)(tksmseq_ctx*, const tksmseq_batch*, const P*, tksmseq_batch**),
-                     uint64_t P::*first_index = &P::first_molecule_index) {
+// The input in pieces of whole molecules, on_batch(ctx, batch, piece, out) on each (piece.first: the index of its first molecule in the whole
+// input; piece.second: a second output batch for second_output), and the outputs written in input order.
+template <class OnBatch>
+int stream_batches(const Common& c, Logger& log, const char* what, OnBatch on_batch, const std::string* second_output = nullptr) {
     // a reader thread of its own cuts the input into pieces of whole molecules and numbers them (input order), a few pieces ahead of the
     // workers: what the engine serialises is a pop from this queue, not the read + scan of a piece.  Its state lives on the heap and is
     // shared with the thread: after an error the module returns without waiting for a reader that may sit in a read() on a pipe nobody
@@ -238,23 +248,33 @@ int stream_transform(const Common& c, Logger& log, const char* what, const P& p,
         rs->put.notify_one();
         return true;
     };
-    auto work = [&](tksmseq_ctx* ctx, void*, const Piece& pc, tksmseq_batch** out) -> int {
+    auto work = [&](tksmseq_ctx* ctx, void*, Piece& pc, tksmseq_batch** out) -> int {
         tksmseq_batch* in = nullptr;
         int rc = tksmseq_molecules_from_mdf_text(ctx, pc.text.data(), pc.text.size(), &in);
         if (rc) return rc;
-        P q = p;
-        if (first_index) q.*first_index = pc.first;
-        rc = fn(ctx, in, &q, out);
+        rc = on_batch(ctx, in, pc, out);
         tksmseq_batch_free(ctx, in);
         return rc;
     };
-    const int rc = run_pieces(c, log, what, prepare, next_piece, work);
+    const int rc = run_pieces(c, log, what, prepare, next_piece, work, false, nullptr, second_output);
     bool finished;
     { std::lock_guard<std::mutex> l(rs->m); rs->stop = true; finished = rs->done; }      // (an error: the reader may be waiting for room, or for input)
     rs->put.notify_all();
     if (rc == 0 || finished) { reader.join(); fclose(rs->rd.in); }
     else reader.detach();
     return rc;
+}
+
+// A stream transform (truncate, polyA, tag, scb, flip, tail-noise): fn(ctx, batch, parameters, out) on each piece -- the parameters are p
+// with the index of the piece's first molecule in p.*first_index (null: fn numbers nothing).
+template <class P>
+int stream_transform(const Common& c, Logger& log, const char* what, const P& p, int (*fn)(tksmseq_ctx*, const tksmseq_batch*, const P*, tksmseq_batch**),
+                     uint64_t P::*first_index = &P::first_molecule_index) {
+    return stream_batches(c, log, what, [&](tksmseq_ctx* ctx, const tksmseq_batch* in, Piece& pc, tksmseq_batch** out) -> int {
+        P q = p;
+        if (first_index) q.*first_index = pc.first;
+        return fn(ctx, in, &q, out);
+    });
 }
 
 }  // namespace
@@ -787,6 +807,51 @@ extern "C" int tksmseq_transcribe_main(int argc, char** argv) {
         log.log(Logger::INFO, "transcribe: %llu records (%llu molecules) written in %.2f s", (unsigned long long)n_records, (unsigned long long)n_molecules,
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return rc;
+}
+
+// `tksm filter` (Filter_module, src/filter.cpp:119-231): the conditions are checked before anything is opened; the two sides are written
+// through two ordered sinks, piece for piece.  Without -f the false side is not made.
+extern "C" int tksmseq_filter_main(int argc, char** argv) {
+    Common c;
+    std::string false_output;
+    std::vector<std::string> conditions;
+    int32_t negate = 0;
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            // (the common flags know -o and --slice-molecules, which this module does not have)
+            if (o == "-o" || o == "--output" || o == "--slice-molecules") return NO_SUCH;
+            if (o == "--negate") return bool_flag(v, negate);
+            if ((o == "-t" || o == "--true-output") && v) c.output = v;
+            else if ((o == "-f" || o == "--false-output") && v) false_output = v;
+            else if ((o == "-c" || o == "--condition") && v) split_commas(v, conditions);
+            else return NOT_MINE;
+            return TOOK_VALUE;
+        })) return 1;
+    static const char* help =
+        "Filter module: Splits the input to 2 files w.r.t. condition\nusage: filter -i INPUT -t TRUE_OUTPUT [-f FALSE_OUTPUT] -c CONDITION[,CONDITION...] [--negate]\n"
+        "              [--devices D[,D...]] [--batch-bytes B] [--verbosity L] [--log-file F]\n"
+        "CONDITION (all must hold; -c may be repeated): \"info KEY\" | \"size OP N\" with OP one of < <= > >= == != (no space before N) |\n"
+        "\"locus CHR\" | \"locus CHR:START-END\" | \"locus CHR:POSITION\"\n";
+    if (c.help) { printf("%s", help); return 0; }
+    // validate_arguments (src/filter.cpp:157-173)
+    int missing = 0;
+    if (c.input.empty()) { fprintf(stderr, "Missing parameter: input\n"); missing++; }
+    if (c.output.empty()) { fprintf(stderr, "Missing parameter: true-output\n"); missing++; }
+    if (conditions.empty()) { fprintf(stderr, "Missing parameter: condition\n"); missing++; }
+    if (missing) { fprintf(stderr, "%s\n", help); return 1; }
+    for (auto& t : conditions) {
+        tkh::FilterCond parsed;
+        if (!tkh::parse_filter_condition(t, parsed)) { fprintf(stderr, "Invalid condition: %s\n", t.c_str()); return 1; }
+    }
+    Logger log;
+    if (!open_log(c, "filter", log)) return 1;
+    std::vector<tksmseq_filter_cond> conds(conditions.size());
+    for (size_t k = 0; k < conds.size(); k++) { conds[k] = tksmseq_filter_cond{}; conds[k].kind = TKSMSEQ_FLT_TEXT; conds[k].text = conditions[k].c_str(); }
+    tksmseq_filter_params p{};
+    p.conditions = conds.data(); p.n_conditions = conds.size(); p.negate = negate;
+    const bool both = !false_output.empty();
+    return stream_batches(c, log, "filter", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, Piece& pc, tksmseq_batch** out) -> int {
+        return tksmseq_filter(ctx, in, &p, out, both ? &pc.second : nullptr);
+    }, both ? &false_output : nullptr);
 }
 
 // `tksm model-truncation`: the reference runs py/truncate_kde.py (argparse: a missing -i / -o and an unknown option exit with 2; --list

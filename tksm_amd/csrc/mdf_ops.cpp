@@ -2,6 +2,7 @@
 //   tksmseq_pcr            src/pcr.cpp:22-89, :138 (presets), :215-229 (whole input in memory, at most 2 x target templates)
 //   tksmseq_truncate       src/truncate.cpp:23-65, :77-227, :322-351, :362-404
 //   tksmseq_polya / _tag / _scb / _flip   src/polyA.cpp:133-148, src/tag.cpp:70-113, src/scb.cpp:57-80, src/interval.h:908-920
+//   tksmseq_filter / _concat   src/filter.cpp:21-117, :196-212 (a two-way partition); Mrg = `cat` of MDF files (batches joined)
 //   tksmseq_wgs            src/random_wgs.cpp:181-207 (no input: the molecules are made on the device)
 //   tksmseq_append_noise   src/append_noise.cpp:83-128 (tail-noise: a random literal or a hairpin behind every molecule)
 //   tksmseq_transcribe     src/transcribe.cpp:170-197 (no input batch: abundance rows x the context's transcript table)
@@ -18,6 +19,7 @@
 
 #include "ctx.h"
 #include <thread>
+#include "filter_host.h"
 #include "mdf_kernels.h"
 
 namespace {
@@ -743,6 +745,190 @@ int tksmseq_flip(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_flip_p
     HIPCHK(ctx, tk::launch_flip_plan(n, p->seed, p->flip_probability, p->first_molecule_index, d_flip.as<uint8_t>(), s));
     if ((rc = edit_apply(ctx, in, nullptr, nullptr, d_flip.as<uint8_t>(), b))) return rc;
     edit_comments(in, b, p->flags);
+    return b.finish(out);
+}
+
+// ---- filter and concat -----------------------------------------------------------------------------------------------------------
+// the conditions of a call, parsed and checked; false: ctx->err says "Invalid condition: <text>"
+static bool filter_conditions(tksmseq_ctx* ctx, const tksmseq_filter_params* p, std::vector<tkh::FilterCond>& out) {
+    static const char* ops[6] = {"<", "<=", ">", ">=", "==", "!="};
+    for (uint64_t k = 0; k < p->n_conditions; k++) {
+        const tksmseq_filter_cond& q = p->conditions[k];
+        tkh::FilterCond c;
+        std::string shown;
+        bool ok = q.text || q.kind == TKSMSEQ_FLT_SIZE;
+        if (q.kind == TKSMSEQ_FLT_TEXT) { shown = q.text ? q.text : ""; ok = ok && tkh::parse_filter_condition(shown, c); }
+        else if (q.kind == TKSMSEQ_FLT_INFO) { c.kind = q.kind; c.key = q.text ? q.text : ""; shown = "info " + c.key; }
+        else if (q.kind == TKSMSEQ_FLT_SIZE) {
+            c.kind = q.kind; c.cmp = q.cmp; c.value = q.value;
+            ok = q.cmp >= TKSMSEQ_FLT_LT && q.cmp <= TKSMSEQ_FLT_NE && q.value >= 0 && q.value <= 0x7fffffffll;
+            shown = std::string("size ") + (q.cmp >= 0 && q.cmp < 6 ? ops[q.cmp] : "?") + std::to_string(q.value);
+        } else if (q.kind == TKSMSEQ_FLT_LOCUS) {
+            c.kind = q.kind; c.key = q.text ? q.text : ""; c.ranged = q.ranged != 0; c.start = q.start; c.end = q.end;
+            shown = "locus " + c.key + (c.ranged ? ":" + std::to_string(q.start) + "-" + std::to_string(q.end) : std::string());
+            ok = ok && (!c.ranged || (q.start >= 0 && q.end >= 0 && q.start <= 0x7fffffffll && q.end <= 0x80000000ll));
+        } else { ok = false; shown = "kind " + std::to_string(q.kind); }
+        if (!ok) { ctx->err = "Invalid condition: " + shown; return false; }
+        out.push_back(std::move(c));
+    }
+    return true;
+}
+
+// the header comments of one side of a partition, or of one input of a concatenation: entry (off, len) of `in`'s pool goes behind b's;
+// the copies of a record, which follow one another and share an entry, share the new one too
+struct CommentCopier {
+    uint32_t last_off = 0, last_len = 0, last_new = 0; bool any = false;
+    int put(tksmseq_ctx* ctx, tksmseq_batch* b, const tksmseq_batch* in, uint64_t r, const char* who) {
+        const uint32_t off = in->h_comments[2 * r], len = in->h_comments[2 * r + 1];
+        if (any && off == last_off && len == last_len) { b->h_comments.push_back(last_new); b->h_comments.push_back(len); return TKSMSEQ_OK; }
+        if (b->h_comment_pool.size() + len >= 0xffffffffull) { ctx->err = std::string(who) + ": more than 4 GB of header comments in one batch (split the input)"; return TKSMSEQ_ELIMIT; }
+        any = true; last_off = off; last_len = len; last_new = (uint32_t)b->h_comment_pool.size();
+        b->h_comments.push_back(last_new); b->h_comments.push_back(len);
+        b->h_comment_pool.insert(b->h_comment_pool.end(), in->h_comment_pool.begin() + off, in->h_comment_pool.begin() + off + len);
+        return TKSMSEQ_OK;
+    }
+};
+
+int tksmseq_filter(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_filter_params* p, tksmseq_batch** out_true, tksmseq_batch** out_false) {
+    if (!ctx || !in || !p || !out_true || (p->n_conditions && !p->conditions)) return TKSMSEQ_EINVAL;
+    *out_true = nullptr;
+    if (out_false) *out_false = nullptr;
+    std::vector<tkh::FilterCond> conds;
+    if (!filter_conditions(ctx, p, conds)) return TKSMSEQ_EINVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint64_t n = in->n_reads;
+    const bool both = out_false != nullptr;
+    // `info`: the conjunction of the info conditions, a byte per molecule; the copies of a record follow one another and share a
+    // comment entry, which is read once
+    std::vector<const std::string*> keys;
+    for (auto& c : conds) if (c.kind == TKSMSEQ_FLT_INFO) keys.push_back(&c.key);
+    std::vector<uint8_t> info;
+    if (!keys.empty()) {
+        info.assign(n, 0);
+        if (!in->h_comments.empty()) {
+            for (uint64_t r = 0; r < n; r++) {
+                const uint32_t off = in->h_comments[2 * r], len = in->h_comments[2 * r + 1];
+                if (r && off == in->h_comments[2 * r - 2] && len == in->h_comments[2 * r - 1]) { info[r] = info[r - 1]; continue; }
+                const Meta meta = parse_meta(in->h_comment_pool.data() + off, len);
+                bool ok = true;
+                for (const std::string* k : keys) {                      // (src/filter.cpp:32-44)
+                    auto f = meta.find(*k);
+                    ok = ok && f != meta.end() && !f->second.empty() && f->second[0] != ".";
+                }
+                info[r] = ok ? 1 : 0;
+            }
+        }
+    }
+    // the device's conditions: size and locus, the contig resolved here, its name uploaded for the literal segments
+    std::vector<tk::FltCond> dc;
+    std::string names;
+    for (auto& c : conds) {
+        if (c.kind == TKSMSEQ_FLT_INFO) continue;
+        tk::FltCond d{};
+        if (c.kind == TKSMSEQ_FLT_SIZE) { d.kind = tk::FLT_SIZE; d.cmp = c.cmp; d.value = c.value; }
+        else {
+            d.kind = tk::FLT_LOCUS;
+            const int ci = ctx->find(c.key);
+            d.contig = ci >= 0 ? (uint32_t)ci : 0xffffffffu;
+            d.name_len = (uint32_t)c.key.size(); d.value = (long long)names.size();      // (offset into `names` until the upload)
+            names += c.key;
+            d.ranged = c.ranged ? 1 : 0; d.start = c.start; d.end = c.end;
+        }
+        dc.push_back(d);
+    }
+    TmpBuf d_conds(s), d_names(s), d_info(s), d_side(s), d_flag(s), d_rank(s), cnt[6] = {TmpBuf(s), TmpBuf(s), TmpBuf(s), TmpBuf(s), TmpBuf(s), TmpBuf(s)};
+    HIPCHK(ctx, d_names.ensure(names.size() + 16));
+    if (!names.empty()) HIPCHK(ctx, hipMemcpyAsync(d_names.p, names.data(), names.size(), hipMemcpyHostToDevice, s));
+    for (auto& d : dc) if (d.kind == tk::FLT_LOCUS) { d.name = d_names.as<uint8_t>() + d.value; d.value = 0; }
+    HIPCHK(ctx, d_conds.ensure(dc.size() * sizeof(tk::FltCond) + 16));
+    if (!dc.empty()) HIPCHK(ctx, hipMemcpyAsync(d_conds.p, dc.data(), dc.size() * sizeof(tk::FltCond), hipMemcpyHostToDevice, s));
+    if (!keys.empty()) {
+        HIPCHK(ctx, d_info.ensure(n + 16));
+        if (n) HIPCHK(ctx, hipMemcpyAsync(d_info.p, info.data(), n, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(ctx, d_side.ensure(n + 16));
+    HIPCHK(ctx, d_flag.ensure(n * 8 + 16));
+    for (int k = 0; k < (both ? 6 : 3); k++) HIPCHK(ctx, cnt[k].ensure(n * 8 + 16));
+    const tk::MolView M = mol_view(in);
+    const tk::FltCounts CT{cnt[0].as<uint64_t>(), cnt[1].as<uint64_t>(), cnt[2].as<uint64_t>()};
+    const tk::FltCounts CF = both ? tk::FltCounts{cnt[3].as<uint64_t>(), cnt[4].as<uint64_t>(), cnt[5].as<uint64_t>()} : tk::FltCounts{nullptr, nullptr, nullptr};
+    HIPCHK(ctx, tk::launch_flt_pred(M, d_conds.as<tk::FltCond>(), (uint32_t)dc.size(), keys.empty() ? nullptr : d_info.as<uint8_t>(), p->negate ? 1 : 0,
+                                    d_side.as<uint8_t>(), d_flag.as<uint64_t>(), CT, CF, s));
+    OutBatch bt(ctx), bf(ctx);
+    uint64_t n_true = 0;
+    int rc;
+    if ((rc = scan_async(ctx, d_flag, d_rank, n, &n_true)) || (rc = bt.scan(cnt[0], cnt[1], cnt[2], n))) return rc;      // (the second drains the stream: n_true is there)
+    if (both && (rc = bf.scan(cnt[3], cnt[4], cnt[5], n))) return rc;
+    if ((rc = bt.alloc(n_true, "filter: ")) || (rc = bt.literals(in))) return rc;
+    if (both && ((rc = bf.alloc(n - n_true, "filter: ")) || (rc = bf.literals(in)))) return rc;
+    const tk::FltOffsets OT{bt.o_ivl.as<uint64_t>(), bt.o_mod.as<uint64_t>(), bt.o_id.as<uint64_t>()};
+    const tk::FltOffsets OF = both ? tk::FltOffsets{bf.o_ivl.as<uint64_t>(), bf.o_mod.as<uint64_t>(), bf.o_id.as<uint64_t>()} : tk::FltOffsets{nullptr, nullptr, nullptr};
+    HIPCHK(ctx, tk::launch_flt_write(M, d_side.as<uint8_t>(), d_rank.as<uint64_t>(), OT, OF, bt.tables(), both ? bf.tables() : tk::MolOut{}, s));
+    if (!in->h_comments.empty() && !(p->flags & TKSMSEQ_MOL_NO_COMMENTS)) {
+        std::vector<uint8_t> side(n);
+        if (n) HIPCHK(ctx, hipMemcpyAsync(side.data(), d_side.p, n, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        CommentCopier ct, cf;
+        for (uint64_t r = 0; r < n; r++) {
+            if (side[r]) rc = ct.put(ctx, bt.get(), in, r, "filter");
+            else rc = both ? cf.put(ctx, bf.get(), in, r, "filter") : TKSMSEQ_OK;
+            if (rc) return rc;
+        }
+    }
+    tksmseq_batch *t = nullptr, *f = nullptr;
+    if ((rc = bt.finish(&t))) return rc;
+    if (both && (rc = bf.finish(&f))) { tksmseq_batch_free(ctx, t); return rc; }
+    *out_true = t;
+    if (both) *out_false = f;
+    return TKSMSEQ_OK;
+}
+
+int tksmseq_concat(tksmseq_ctx* ctx, const tksmseq_batch* const* in, uint64_t n_in, int32_t flags, tksmseq_batch** out) {
+    if (!ctx || !in || !out) return TKSMSEQ_EINVAL;
+    *out = nullptr;
+    if (n_in == 0) { ctx->err = "concat: no input batches"; return TKSMSEQ_EINVAL; }
+    for (uint64_t k = 0; k < n_in; k++) if (!in[k]) return TKSMSEQ_EINVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // every input's counts (ids with their unroll suffix) and their scans; one synchronisation for all
+    struct Part { std::unique_ptr<TmpBuf> cnt[3], off[3]; uint64_t total[3] = {0, 0, 0}; };
+    std::vector<Part> parts(n_in);
+    int rc;
+    for (uint64_t k = 0; k < n_in; k++) {
+        const uint64_t n = in[k]->n_reads;
+        for (int q = 0; q < 3; q++) { parts[k].cnt[q].reset(new TmpBuf(s)); parts[k].off[q].reset(new TmpBuf(s)); HIPCHK(ctx, parts[k].cnt[q]->ensure(n * 8 + 16)); }
+        HIPCHK(ctx, tk::launch_edit_count(mol_view(in[k]), nullptr, nullptr, parts[k].cnt[0]->as<uint64_t>(), parts[k].cnt[1]->as<uint64_t>(), parts[k].cnt[2]->as<uint64_t>(), s));
+        for (int q = 0; q < 3; q++) if ((rc = scan_async(ctx, *parts[k].cnt[q], *parts[k].off[q], n, &parts[k].total[q]))) return rc;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    OutBatch b(ctx);
+    uint64_t n_mol = 0, n_lit = 0, pool = 0;
+    for (uint64_t k = 0; k < n_in; k++) {
+        n_mol += in[k]->n_reads; b.t_ivl += parts[k].total[0]; b.t_mod += parts[k].total[1]; b.t_id += parts[k].total[2];
+        n_lit += in[k]->n_literals; pool += in[k]->litpool.cap;
+    }
+    if ((rc = b.alloc(n_mol, "concat: ", "fewer or smaller inputs")) || (rc = b.literals(nullptr, n_lit, pool))) return rc;
+    tk::CatBase base{0, 0, 0, 0, 0u, 0};
+    for (uint64_t k = 0; k < n_in; k++) {
+        if (in[k]->litpool.cap) HIPCHK(ctx, hipMemcpyAsync(b->litpool.as<uint8_t>() + base.pool, in[k]->litpool.p, in[k]->litpool.cap, hipMemcpyDeviceToDevice, s));
+        HIPCHK(ctx, tk::launch_cat_write(mol_view(in[k]), parts[k].off[0]->as<uint64_t>(), parts[k].off[1]->as<uint64_t>(), parts[k].off[2]->as<uint64_t>(), base,
+                                         b->literals.as<uint64_t>(), b.tables(), s));
+        base.mol += in[k]->n_reads; base.ivl += parts[k].total[0]; base.mod += parts[k].total[1]; base.id += parts[k].total[2];
+        base.lit += (uint32_t)in[k]->n_literals; base.pool += in[k]->litpool.cap;
+    }
+    bool any_comments = false;
+    for (uint64_t k = 0; k < n_in; k++) any_comments = any_comments || !in[k]->h_comments.empty();
+    if (any_comments && !(flags & TKSMSEQ_MOL_NO_COMMENTS)) {
+        b->h_comments.reserve(2 * n_mol);
+        for (uint64_t k = 0; k < n_in; k++) {
+            CommentCopier cc;
+            for (uint64_t r = 0; r < in[k]->n_reads; r++) {
+                if (in[k]->h_comments.empty()) { b->h_comments.push_back((uint32_t)b->h_comment_pool.size()); b->h_comments.push_back(0u); }
+                else if ((rc = cc.put(ctx, b.get(), in[k], r, "concat"))) return rc;
+            }
+        }
+    }
     return b.finish(out);
 }
 

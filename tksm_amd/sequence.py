@@ -379,6 +379,29 @@ class Sequencer:
         self._chk(self._lib.tksmseq_flip(self._ctx, batch._h, C.byref(q), C.byref(h)))
         return Batch(self, h)
 
+    # ---- filter and merge: split and join batches (device to device)
+    def filter(self, batch, conditions, negate=False, want_false=True, comments=True):
+        """The loop of Filter_module::run (src/filter.cpp:196-212) on the device: conditions as `tksm filter -c` takes them ("info CB",
+        "size >=200", "locus chr1:100-200"; one string or a list: all must hold, inverted by negate).  Returns (true_batch, false_batch);
+        false_batch is None with want_false=False (that side is then not made)."""
+        conditions = [conditions] if isinstance(conditions, (str, bytes)) else list(conditions)
+        raw = [c.encode() if isinstance(c, str) else bytes(c) for c in conditions]
+        arr = (L.FilterCond * max(1, len(raw)))()
+        for k, t in enumerate(raw):
+            arr[k].kind, arr[k].text = L.FLT_TEXT, t
+        p = L.FilterParams(arr, len(raw), 1 if negate else 0, 0 if comments else L.MOL_NO_COMMENTS)
+        ht, hf = C.c_void_p(), C.c_void_p()
+        self._chk(self._lib.tksmseq_filter(self._ctx, batch._h, C.byref(p), C.byref(ht), C.byref(hf) if want_false else None))
+        return Batch(self, ht), (Batch(self, hf) if want_false else None)
+
+    def merge(self, batches, comments=True):
+        """Mrg (`cat` of MDF files) on the device: the molecules of batches[0], then batches[1], ... in one batch (tksmseq_concat)."""
+        batches = list(batches)
+        arr = (C.c_void_p * max(1, len(batches)))(*[b._h for b in batches])
+        h = C.c_void_p()
+        self._chk(self._lib.tksmseq_concat(self._ctx, arr, len(batches), 0 if comments else L.MOL_NO_COMMENTS, C.byref(h)))
+        return Batch(self, h)
+
     def append_noise(self, batch, dist, mu, sigma, *, palindromic=False, error_rate=0.5, alphabet="AGTC", seed=42, first=0, comments=True):
         """NoiseAdder::operator() (src/append_noise.cpp:83-128) on the device: a noise length from dist "normal" | "lognormal" (mu, sigma)
         per molecule; a random literal over `alphabet` behind the molecule, or (palindromic) its last segments again, strands toggled,
