@@ -191,3 +191,130 @@ def run(paf, em_iterations=10, lr_br=None, cb_count=0, cb_lognorm_params=(10.0, 
         vec[t] = a
     return {"transcripts": tnames, "reads": list(reads), "kept": [r in comp for r in reads], "surviving": list(comp), "uniform_hits": first, "hits": comp,
             "read_cells": [cell_of(r) for r in comp], "abundance": vec, "rows": rows, "tsv": tsv_of(rows), "barcodes": barcodes, "weights": weights}
+
+
+# ---- the order of addition (abundance, "The round" and "The split"), restated ------------------------------------------
+# `run` above adds left to right, as the reference does.  The device adds in another order, documented as a function of the input alone.
+# `ordered_run` performs every addition and division of that document in numpy float64, in that order, so its results can be compared
+# with the device's bit for bit.  It is written from the document: chunks of CHUNK positions, WAVE lanes, BLOCK threads.
+CHUNK, WAVE, BLOCK = 1024, 64, 256
+
+
+def _wave_tree(v):
+    """v[..., 64] -> what lane 0 holds after the steps 32, 16, 8, 4, 2, 1: at step d, lane l < d adds lane l + d to its own"""
+    for d in (32, 16, 8, 4, 2, 1):
+        v = v[..., :d] + v[..., d:2 * d]
+    return v[..., 0]
+
+
+def _block_tree(v):
+    """v[..., 256] -> the four wave trees, then (0 + 1) + (2 + 3)"""
+    w = _wave_tree(v.reshape(v.shape[:-1] + (BLOCK // WAVE, WAVE)))
+    return (w[..., 0] + w[..., 1]) + (w[..., 2] + w[..., 3])
+
+
+def _strided(x, width):
+    """lane l of `width` adds x[l], x[l + width], ... in order, from 0.0; x's last axis is padded with 0.0 (x + 0.0 == x for x >= 0)"""
+    rows = max(1, -(-x.shape[-1] // width))
+    padded = np.zeros(x.shape[:-1] + (rows * width,))
+    padded[..., :x.shape[-1]] = x
+    padded = padded.reshape(x.shape[:-1] + (rows, width))
+    acc = np.zeros(x.shape[:-1] + (width,))
+    for j in range(rows):
+        acc = acc + padded[..., j, :]
+    return acc
+
+
+def segment_sums(x, off):
+    """x: the weights in segment order; off[segments + 1].  (sum per segment, total): a segment is cut into chunks of CHUNK positions; in
+    a chunk lane l adds positions l, l + 64, ... in order, then the wave tree; a segment's chunk partials are added in chunk order; the
+    segments' sums fold by blocks of BLOCK (absent segments and the places past the last one count 0.0), and the block results by ONE
+    block whose thread t adds parts t, t + 256, ... in order before the same tree"""
+    off = np.asarray(off, np.int64)
+    n_seg = len(off) - 1
+    n_chunks = (np.diff(off) + CHUNK - 1) // CHUNK
+    chunk_off = np.concatenate([[0], np.cumsum(n_chunks)])
+    chunk_seg = np.repeat(np.arange(n_seg), n_chunks)
+    lo = off[chunk_seg] + (np.arange(len(chunk_seg)) - chunk_off[chunk_seg]) * CHUNK
+    hi = np.minimum(off[chunk_seg + 1], lo + CHUNK)
+    rows = (hi - lo + WAVE - 1) // WAVE
+    partial = np.zeros(len(chunk_seg))
+    for r in np.unique(rows):                                       # the chunks of r rows of 64 together (most segments are short)
+        sel = np.flatnonzero(rows == r)
+        at = lo[sel][:, None] + np.arange(r * WAVE)[None, :]
+        vals = np.where(at < hi[sel][:, None], x[np.minimum(at, len(x) - 1)], 0.0)
+        partial[sel] = _wave_tree(_strided(vals, WAVE))
+    sums = np.zeros(n_seg)
+    for j in range(int(n_chunks.max()) if n_seg else 0):
+        has = np.flatnonzero(n_chunks > j)
+        sums[has] = sums[has] + partial[chunk_off[has] + j]
+    n_blocks = (n_seg + BLOCK - 1) // BLOCK
+    padded = np.zeros(n_blocks * BLOCK)
+    padded[:n_seg] = sums
+    parts = _block_tree(padded.reshape(n_blocks, BLOCK))
+    return sums, float(_block_tree(_strided(parts, BLOCK)))
+
+
+def _segments(keys):
+    """(perm, off, first key of each segment) of a stable sort by key, equal keys forming a segment"""
+    perm = np.argsort(keys, kind="stable")
+    s = keys[perm]
+    start = np.flatnonzero(np.concatenate([[True], s[1:] != s[:-1]]))
+    return perm, np.concatenate([start, [len(keys)]]), s[start]
+
+
+def ordered_run(paf, em_iterations=10, lr_br=None):
+    """`run` in the device's documented order of addition: {"abundance", "hit_weights" (flat, surviving reads and their hits in order),
+    "uniform_weights", "rows", "tpm"}.  Hits in read and record order; a stable sort by tid; per round the segment sums and their total
+    (segment_sums), then per read acc = the sum over its hits, in hit order, of sum[tid] / total and w = (sum[tid] / total) / acc."""
+    tnames, reads = parse_paf(paf)
+    comp = compatibility(reads)
+    T = len(tnames)
+    hit_tid = np.array([t for hits in comp.values() for t, _ in hits], np.int64)
+    hit_read = np.array([k for k, hits in enumerate(comp.values()) for _ in hits], np.int64)
+    w = np.array([x for hits in comp.values() for _, x in hits], np.float64)
+    out = {"uniform_weights": w.copy(), "abundance": np.zeros(T), "hit_weights": w, "rows": [], "tpm": np.zeros(0)}
+    if not len(w):
+        return out
+    hit_off = np.concatenate([[0], np.cumsum(np.bincount(hit_read, minlength=len(comp)))])
+    nth = np.arange(len(w)) - hit_off[hit_read]                     # a hit's place among its read's hits
+    by_place = [np.flatnonzero(nth == j) for j in range(int(nth.max()) + 1)]
+    perm = np.argsort(hit_tid, kind="stable")
+    off = np.searchsorted(hit_tid[perm], np.arange(T + 1), side="left")
+    abundance = None
+    for _ in range(em_iterations):
+        sums, total = segment_sums(w[perm], off)
+        abundance = sums / total
+        share = sums[hit_tid] / total
+        acc = np.zeros(len(comp))
+        for sel in by_place:
+            acc[hit_read[sel]] = acc[hit_read[sel]] + share[sel]
+        w = share / acc[hit_read]
+    # the split: cells are numbered as the reads of the PAF (dropped ones too) first name them, "." is cell 0
+    cells, cell_no = ["."], {".": 0}
+    named = parse_lr_br(lr_br) if lr_br else {}
+    read_cell = {}
+    for rid in reads:
+        if rid in named:
+            read_cell[rid] = cell_no.setdefault(named[rid], len(cell_no))
+            if read_cell[rid] == len(cells):
+                cells.append(named[rid])
+    one_cell = len(cells) == 1
+    if one_cell or em_iterations == 0:
+        sums, total = segment_sums(w[perm], off)
+        if em_iterations == 0:
+            abundance = sums / total
+        seg_perm, seg_off, seg_key = perm, off, np.arange(T, dtype=np.int64) << 32
+    if not one_cell:
+        cell = np.array([read_cell.get(rid, 0) for rid in comp], np.int64)
+        seg_perm, seg_off, seg_key = _segments((hit_tid << 32) | cell[hit_read])
+        sums, total = segment_sums(w[seg_perm], seg_off)
+    rows = []
+    present = np.flatnonzero(seg_off[1:] > seg_off[:-1])
+    for g in present[np.argsort(seg_perm[seg_off[present]], kind="stable")]:      # by the segment's lowest hit index
+        tpm = (sums[g] / total) * 1000000.0
+        if tpm < 0.001 or f"{tpm:.3f}" == "0.000":
+            continue
+        rows.append((tnames[int(seg_key[g]) >> 32], cells[int(seg_key[g]) & 0xFFFFFFFF], float(tpm)))
+    out.update(abundance=abundance, hit_weights=w, rows=rows, tpm=np.array([t for _, _, t in rows], np.float64))
+    return out

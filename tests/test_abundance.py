@@ -76,6 +76,70 @@ def test_spec_cell_draws():
     assert np.abs(share - w / cdf[-1]).max() < 0.02
 
 
+def _ordered_against_the_specification(paf, what, **kw):
+    """abundance_spec.ordered_run (the device's documented order of addition) against abundance_spec.run (left to right): the same rows,
+    every number within the 1e-9 gate of tests/test_abundance_gpu.py"""
+    spec, got = A.run(paf, **kw), A.ordered_run(paf, **kw)
+    assert [(n, c) for n, c, _ in got["rows"]] == [(n, c) for n, c, _ in spec["rows"]] and len(spec["rows"]) > 0
+    pairs = {"abundance": (got["abundance"], spec["abundance"]), "tpm": (got["tpm"], np.array([t for _, _, t in spec["rows"]])),
+             "final weights": (got["hit_weights"], np.array([w for hits in spec["hits"].values() for _, w in hits])),
+             "uniform weights": (got["uniform_weights"], np.array([w for hits in spec["uniform_hits"].values() for _, w in hits]))}
+    for k, (a, b) in pairs.items():
+        assert a.shape == b.shape and np.isfinite(a).all(), k
+        rel = np.abs(a - b)[b > 0] / b[b > 0]
+        print(f"{what}: {k}: worst relative difference {rel.max():.3g}")
+        assert rel.max() <= 1e-9 and (a[b == 0] == 0).all(), k
+    assert (pairs["uniform weights"][0] == pairs["uniform weights"][1]).all()
+    return got
+
+
+@pytest.mark.parametrize("name", list(RUNS))
+def test_ordered_run_agrees_with_the_specification_on_the_fixture(name):
+    _ordered_against_the_specification(PAF, name, **RUNS[name])
+
+
+def test_ordered_run_agrees_with_the_specification_on_a_synthetic_case(tmp_path):
+    """a (transcript, cell) segment of three chunks, 700 transcripts (three blocks), a run of transcripts without hits, unnamed reads"""
+    def line(rid, t, matches, block=950):
+        return f"{rid}\t1000\t0\t{block}\t+\t{t}\t9000\t0\t{block}\t{matches}\t{block}\t60\n"
+    lines, cells = [], []
+    for i in range(2600):
+        lines.append(line(f"b{i}", "big", 900))
+        if i % 5 == 0:
+            lines.append(line(f"b{i}", f"s{i // 5 % 300}", 870 + i % 25))
+        if i % 4:
+            cells.append(f"b{i}\t0\t1\t0\tC{i % 3 % (1 + i % 2)}\n")
+        if i == 1300:
+            lines += [line(f"d{j}", f"h{j}", 390, 400) for j in range(30)]
+    lines += [line(f"u{i}", f"v{i}", 900) for i in range(400)]
+    paf, lr = tmp_path / "a.paf", tmp_path / "cells.tsv"
+    paf.write_text("".join(lines))
+    lr.write_text("".join(cells))
+    for kw in ({}, {"lr_br": lr}, {"lr_br": lr, "em_iterations": 0}, {"em_iterations": 1}):
+        got = _ordered_against_the_specification(paf, f"synthetic {sorted(kw)}", **kw)
+        assert len(got["abundance"]) == 731 and (got["abundance"][[t for t, n in enumerate(A.parse_paf(paf)[0]) if n.startswith("h")]] == 0).all()
+
+
+def test_ordered_runs_trees_are_the_documented_ones():
+    """inputs on which another pairing gives another double: 2^53 + 1 rounds to 2^53, 2^53 + 2 is exact"""
+    big = 2.0 ** 53
+    v = np.zeros(64)
+    v[[0, 32, 48]] = big, 1.0, 1.0
+    assert A._wave_tree(v) == big                                    # (0 + 32) loses the 1, then (16 + 48) = 1 is lost too; neighbours first gives 2^53 + 2
+    v = np.zeros(256)
+    v[[0, 128, 192]] = big, 1.0, 1.0
+    assert A._block_tree(v) == big + 2.0                             # (w0 + w1) + (w2 + w3); (w0 + w2) + (w1 + w3) gives 2^53
+    x = np.zeros(1025)
+    x[[0, 64, 1024]] = big, 1.0, 1.0                                 # lane 0 adds 0, 64, ... in order: the 1 is lost; position 1024 is the second chunk
+    sums, total = A.segment_sums(x, [0, 1025])
+    assert sums[0] == big and total == big
+    sums, total = A.segment_sums(np.ones(600), np.arange(601))       # 600 segments: three blocks, the total by one block
+    assert (sums == 1.0).all() and total == 600.0
+    parts = np.zeros(257)
+    parts[[0, 256]] = big, 1.0                                       # thread 0 adds parts 0 and 256
+    assert A._block_tree(A._strided(parts, 256)) == big
+
+
 @pytest.fixture(scope="module")
 def host_program(tmp_path_factory):
     """tools/sanitize_abund_host.cpp built with ASan + UBSan and run on the fixtures: {key: [lines]} of what it printed"""
