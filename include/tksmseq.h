@@ -38,6 +38,9 @@
  *   TKSMSEQ_DEFER_LEN=L    reads longer than L wait with their q-score alignment until the regular rounds are over (default 0: all)
  *   TKSMSEQ_BUCKETS=N      length buckets of the last visit's launches (default 16)
  *   TKSMSEQ_TAIL_CUT=N     diagnostic: once fewer than N reads are left, they finish in the wave-wide kernel (default 0: off)
+ *   TKSMSEQ_FULL_ROWS_CAP=N diagnostic: the full-width alignment pass sees a pool of at most N rows (a multiple of 64, at least 64; default 0:
+ *                          no cap).  Which rounds align at full width does not change, so a round with more jobs than rows leaves waves without
+ *                          rows: their jobs are counted as fall-backs (reason bit 0x02) and their reads finish in the exact kernel
  *   TKSMSEQ_FULL_POOL_MB=M memory for the unbanded alignment fallback of the wave-wide kernel (default 1024)
  *   TKSMSEQ_STATS_FILE=P   (CLI) `tksm sequence` writes one JSON object with the run's stage clocks to P: reads, batches, MDF bytes in, record
  *                          bytes out, seconds of set-up (devices, references, models), of streaming (first chunk read -> last record byte

@@ -475,10 +475,12 @@ def test_edge_cases_empty_short_constant_identity_and_limits(po, oracle_models):
     s.close()
 
 
-def test_output_slot_overflow_triggers_rerun(tmp_path, po):
+def test_output_slot_overflow_triggers_rerun(tmp_path, po, monkeypatch, capfd):
     """an insertion-heavy error model outgrows the default 1.5x output slot: the library reruns with the worst-case
-    slot and still matches the oracle"""
+    slot and still matches the oracle.  The rerun is the device's doing: a kernel of the round pipeline set the overflow bit of a
+    read's status, so the verbose text shows two passes of the rounds over the batch, and the diagnostics are those of the second"""
     import gzip
+    monkeypatch.setenv("TKSMSEQ_FORCE_SLOW", "0"); monkeypatch.setenv("TKSMSEQ_VERBOSE", "1")
     path = tmp_path / "ins.error.gz"
     rs = np.random.RandomState(0)
     with gzip.open(path, "wt") as f:
@@ -495,7 +497,12 @@ def test_output_slot_overflow_triggers_rerun(tmp_path, po):
     assert em.k == 3
     mols = [(f"m{i}", [("chr1", 100 * i, 100 * i + 300, "+", "")]) for i in range(12)]
     text = "".join(f"+{m}\t1\t\n" + "".join(f"{c}\t{a}\t{b}\t{st}\t{md}\n" for c, a, b, st, md in ivs) for m, ivs in mols)
+    capfd.readouterr()
     recs = s.run(s.batch_from_mdf(text), target="badread", fastq=True, compute_qual=True, seed=8).records()
+    err = capfd.readouterr().err
+    diag = s.run_diagnostics()
+    assert len(re.findall(r"\[tksmseq\] reads 12 rounds \d+ slow-path reads", err)) == 2, err[-1500:]
+    assert diag["rounds"] > 0 and diag["jobs_all_rounds"] > 0, diag
     ident = po.Identities(55.0, 1.0, 60.0)
     grew = 0
     for i, (mid, ivs) in enumerate(mols):
@@ -602,6 +609,13 @@ def test_band_failure_falls_back_to_the_unbanded_alignment(oracle_models, po, mo
         assert st.band_fail > 0
         assert res.records()[0] == want
         assert res.stats()[0][0, 7] & 16                    # the run reports that it took the unbanded path
+        # ... and the diagnostics say how: the round pipeline gave the read up at a band exit and the exact kernel finished it; with the
+        # exact kernel forced there are no rounds and nothing to give up
+        diag = s.run_diagnostics()
+        if path == "fast":
+            assert diag["rounds"] > 0 and diag["band_exits"] == 1 and diag["exact_kernel_reads"] == 1, diag     # (a batch of one read)
+        else:
+            assert diag["rounds"] == 0 and diag["band_exits"] == 0 and diag["fallbacks"] == 0, diag
     s.close()
 
 

@@ -275,6 +275,7 @@ struct tksmseq_ctx : ContigLookup {
     int tail_wcap = 2048;                 // columns of a re-estimation window the straggler kernel aligns itself (its LDS holds 2048; smaller: tests)
     uint32_t tail_wave = 4096;            // rounds with at most this many reads left: one launch that runs every remaining visit of a read on a wave of its own (k_loopw<true>); 0: never
     uint32_t wave_loop = 16384;           // rounds with at most this many reads left run the error loop one wave per read (k_loopw)
+    uint32_t full_rows_cap = 0;           // diagnostic: the full-width pass sees at most this many pool rows (0: all of them); what does not fit is handed to the exact kernel
     uint32_t small_aln = 131072;          // rounds with at most this many alignment jobs are latency-bound: every job with all 64 rows in one launch
     uint32_t n_buckets = 16;
     int defer_len = 0;          // reads longer than this align for their q-scores after the regular rounds, all together

@@ -170,7 +170,7 @@ enum Counter {
 // why a read left the fast pipeline: an alignment left the band (in an error loop / in the last visit), a window shift > 15 (likewise)
 enum ExitCause { EXIT_BAND_LOOP = 0, EXIT_SHIFT_LOOP = 1, EXIT_SHIFT_ERR = 2, EXIT_BAND_ERR = 3 };
 // reason bits of a fused alignment's failure: queue / reservoir overflow, shift > 31, shift > 14, end cell, walk
-enum FailBit { FAIL_QUEUE = 0, FAIL_SHIFT31 = 3, FAIL_SHIFT14 = 4, FAIL_END_CELL = 5, FAIL_WALK = 6 };
+enum FailBit { FAIL_QUEUE = 0, FAIL_NOROW = 1, FAIL_SHIFT31 = 3, FAIL_SHIFT14 = 4, FAIL_END_CELL = 5, FAIL_WALK = 6 };
 
 struct FastBuffers {
     ReadState* state;                 // [n_reads]

@@ -2572,11 +2572,11 @@ __global__ __launch_bounds__(64, ROWS == 64 ? 3 : ALNF_WAVES) ALNF_VGPR_CAP void
         J.act = act && !straight_to_list;
         AlnResF R = aln_fused<MODE, ROWS>(J, trl, tg, (int)FB.full_cl, ls, mcap);
         if (straight_to_list) { R.fail = false; R.needfull = true; R.overflow = false; }
-        if (norow) { R.fail = true; R.needfull = false; R.overflow = false; }
+        if (norow) { R.fail = true; R.needfull = false; R.overflow = false; R.why = 1u << FAIL_NOROW; }
         if (act && R.overflow) { job_overflow(FB, O, r); return; }
         if (ROWS != 64) list_append(FB.redo_list, FB.counters + CNT_REDO_LIST, act && R.needfull, job, lane);
         if ((act || norow) && !R.needfull) store_result_f(FB, r, R);
-        if (act && R.fail) { atomicAdd(&FB.counters[CNT_FAIL], 1u); atomicOr(&FB.counters[CNT_FAIL_OR], R.why & 255u); FB.counters[CNT_FAIL_LAST] = R.why; FB.counters[CNT_FAIL_NM] = (uint32_t)J.n | ((uint32_t)R.m << 16);
+        if ((act || norow) && R.fail) { atomicAdd(&FB.counters[CNT_FAIL], 1u); atomicOr(&FB.counters[CNT_FAIL_OR], R.why & 255u); FB.counters[CNT_FAIL_LAST] = R.why; FB.counters[CNT_FAIL_NM] = (uint32_t)J.n | ((uint32_t)R.m << 16);
               for (int b = 0; b < 8; b++) if ((R.why >> b) & 1u) atomicAdd(&FB.counters[CNT_FAIL_REASON + b], 1u); if (MODE) atomicAdd(&FB.counters[CNT_FAIL_QJOB], 1u); if (LIST) atomicAdd(&FB.counters[CNT_FAIL_LIST], 1u); }
     } else {
         static_assert(!LIST || ROWS == 64, "the list holds the jobs of the full-width pass");

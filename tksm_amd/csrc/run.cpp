@@ -184,6 +184,7 @@ struct FastRun {
     const uint32_t* hcnt = nullptr;       // in h_round: this round's job counts
     std::vector<Bucket> buckets;
     uint32_t n_side = 0, side_launches = 0;                   // reads handed to / launches of the exact kernel on the side streams
+    uint32_t full_rows_fit = 0;           // FB.full_rows before TKSMSEQ_FULL_ROWS_CAP
     bool late_flushed = false, early_on = false, early_active = false, revive = false, revived = false;
     uint32_t n_early = 0, n_rounds = 0, n_deferred = 0;
     uint64_t jobs_all = 0, jobs_14 = 0;                       // alignment jobs launched (diagnostics)
@@ -235,6 +236,10 @@ struct FastRun {
         FB.full_cl = ((((uint32_t)pl.ncap + 31) & ~31u) / 4 + 16 + 3) & ~3u;
         FB.full_tg = FB.full_cl + (FB.full_cl / 4 + 3) / 4 + 1;
         FB.full_rows = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(jcap, (4ull << 30) / ((uint64_t)FB.full_tg * 64)) & ~63ull);
+        // rounds of at most this many jobs align at full width; the diagnostic cap shrinks the pool behind that choice (never the choice), so
+        // that a round can ask for more rows than there are: the waves that find none report their jobs as failures (k_alnf: norow)
+        full_rows_fit = FB.full_rows;
+        if (ctx->full_rows_cap) FB.full_rows = std::min(FB.full_rows, std::max(64u, ctx->full_rows_cap & ~63u));
         early_on = ctx->early_tail > 0 && ctx->tail_cut == 0 && ctx->tail_wave > 0 && tk::tail_lds_bytes(pl.lcap) <= 65536 && n >= 16ull * ctx->early_tail;
     }
     // the device and page-locked buffers at those sizes, and the kernels' view of them (FB)
@@ -487,7 +492,7 @@ struct FastRun {
     int align(bool qround) {
         const uint32_t jobs = cnt[tk::CNT_JOBS];
         const uint32_t n_jobs = hbase_cur[FB.n_ranges - 1] + ((hcnt[(size_t)(FB.n_ranges - 1) * 32] + 63) & ~63u);
-        const bool full_only = jobs <= std::min(ctx->small_aln, FB.full_rows);
+        const bool full_only = jobs <= std::min(ctx->small_aln, full_rows_fit);
         jobs_all += jobs; if (!full_only) jobs_14 += jobs;
         HIPCHK(ctx, tk::launch_alnf(pl.P, FB, pl.O, n_jobs, full_only, qround ? 1 : 0, s));
         return tick(ALN);
@@ -552,7 +557,7 @@ struct FastRun {
             fprintf(stderr, "[tksmseq] reads %llu rounds %u slow-path reads %u (band exit %u/%u, shift %u/%u), full-width redo: %u jobs in %u waves; predicted stragglers on their own stream: %u\n",
                     (unsigned long long)n, n_rounds, cnt[tk::CNT_SLOW], ex[tk::EXIT_BAND_LOOP], ex[tk::EXIT_BAND_ERR], ex[tk::EXIT_SHIFT_LOOP], ex[tk::EXIT_SHIFT_ERR], cc[tk::CNT_REDO_JOBS], cc[tk::CNT_REDO_WAVES], n_early);
             fprintf(stderr, "[tksmseq] fused alignment failures: %u, reasons or-ed 0x%x, last 0x%x (n %u, m %u)\n", cc[tk::CNT_FAIL], cc[tk::CNT_FAIL_OR], cc[tk::CNT_FAIL_LAST], cc[tk::CNT_FAIL_NM] & 0xffffu, cc[tk::CNT_FAIL_NM] >> 16);
-            fprintf(stderr, "[tksmseq]   per reason: queue / reservoir overflow %u - - shift>31 %u shift>14 %u end cell %u walk %u | q-score jobs %u, list pass %u\n", why[tk::FAIL_QUEUE], why[tk::FAIL_SHIFT31], why[tk::FAIL_SHIFT14], why[tk::FAIL_END_CELL], why[tk::FAIL_WALK], cc[tk::CNT_FAIL_QJOB], cc[tk::CNT_FAIL_LIST]);
+            fprintf(stderr, "[tksmseq]   per reason: queue / reservoir overflow %u no pool rows %u - shift>31 %u shift>14 %u end cell %u walk %u | q-score jobs %u, list pass %u\n", why[tk::FAIL_QUEUE], why[tk::FAIL_NOROW], why[tk::FAIL_SHIFT31], why[tk::FAIL_SHIFT14], why[tk::FAIL_END_CELL], why[tk::FAIL_WALK], cc[tk::CNT_FAIL_QJOB], cc[tk::CNT_FAIL_LIST]);
         }
         for (HelperStream& h : ctx->side) if (h.used) HIPCHK(ctx, h.join_into(s));
         if (cnt[tk::CNT_SLOW] > n_side) {
