@@ -12,6 +12,7 @@
 #include <string>
 
 #include "ctx.h"
+#include "loop_filter.h"
 
 static thread_local std::string g_create_error;
 
@@ -73,7 +74,7 @@ int tksmseq_clone(const tksmseq_ctx* src, tksmseq_ctx** out) {
     c->tsb = src->tsb;                                       // (the transcript table of transcribe: immutable, shared)
     c->d_packed.borrow(src->d_packed); c->d_blocktab.borrow(src->d_blocktab); c->d_pool.borrow(src->d_pool); c->d_contigs.borrow(src->d_contigs);
     c->em = src->em; c->qm = src->qm; c->idm = src->idm; c->em_uniform = src->em_uniform; c->em_alt0 = src->em_alt0;
-    c->d_pself.borrow(src->d_pself); c->d_pseg.borrow(src->d_pseg); c->d_pt0.borrow(src->d_pt0); c->d_cdf32.borrow(src->d_cdf32); c->d_cdf.borrow(src->d_cdf); c->d_alts.borrow(src->d_alts); c->d_altenc.borrow(src->d_altenc);
+    c->d_pself.borrow(src->d_pself); c->d_pseg.borrow(src->d_pseg); c->d_pt0.borrow(src->d_pt0); c->d_pt0b.borrow(src->d_pt0b); c->d_cdf32.borrow(src->d_cdf32); c->d_cdf.borrow(src->d_cdf); c->d_alts.borrow(src->d_alts); c->d_altenc.borrow(src->d_altenc);
     c->d_nalts.borrow(src->d_nalts); c->d_qkeys.borrow(src->d_qkeys); c->d_qoff.borrow(src->d_qoff); c->d_qcnt.borrow(src->d_qcnt);
     c->d_qcdf.borrow(src->d_qcdf); c->d_qq.borrow(src->d_qq); c->d_qtab.borrow(src->d_qtab); c->d_qent.borrow(src->d_qent);
     c->d_qpairs.borrow(src->d_qpairs); c->d_qguide.borrow(src->d_qguide);
@@ -278,6 +279,9 @@ int tksmseq_load_error_model(tksmseq_ctx* ctx, const char* name_or_path) {
         std::vector<uint32_t> t0(nk);
         for (size_t i = 0; i < nk; i++) t0[i] = c32[i * 32];
         if ((rc = upload(ctx, ctx->d_pt0, t0))) return rc;
+        std::vector<uint16_t> t0b(tklf::LOOP_FILTER_KEYS);    // per coarse key the byte bounds of t0: k_loop's copy in LDS (loop_filter.h)
+        tklf::loop_filter_build(t0.data(), nk, t0b.data());
+        if ((rc = upload(ctx, ctx->d_pt0b, t0b))) return rc;
     }
     if ((rc = upload(ctx, ctx->d_alts, ctx->em.alts))) return rc;
     {

@@ -41,6 +41,8 @@ struct ErrModelView {
     const uint4* pseg;      // [4^k] thresholds 0, 8, 16 and 24 of every row: a draw's first-level lookup in k_loop (k-mer itself /
                             // which 8-threshold segment of cdf32 to read)
     const uint32_t* pt0;    // [4^k] threshold 0 alone (64 KB): what EVERY draw of k_loop looks at first (four times as many entries per cache line as pseg)
+    const uint4* pt0b;      // [256] = 2048 x {lo, hi} bytes (4 KB): per coarse key of a k-mer the top bytes of the smallest and the largest
+                            // threshold 0 under it (loop_filter.h); k_loop keeps a copy in LDS and asks pt0 only where it does not decide
     const uint4* alts_enc;  // [4^k][max_alts] the alternatives as the fast pipeline applies them: eight 16-bit slot
                             // encodings (length << 12 | 2-bit codes), bit 15 = the slot differs from the k-mer's base
 };

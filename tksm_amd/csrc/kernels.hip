@@ -20,6 +20,7 @@
 // Integer/byte work throughout: no MFMA.  fp64 is used only for the scalar identity bookkeeping
 // and is compiled with -ffp-contract=off so it matches the CPU oracle bit for bit.
 #include "kernels.h"
+#include "loop_filter.h"
 #include <type_traits>
 
 namespace tk {
@@ -1240,7 +1241,10 @@ DEV void join_out(const uint8_t* frag, const uint16_t* nb, int n, uint8_t* out_s
 #define TKSM_LOOP_K 3
 #endif
 constexpr int LOOP_N = TKSM_LOOP_N, LOOP_K = TKSM_LOOP_K;      // draws per pass of k_loop; changing draws applied per pass
-__global__ __launch_bounds__(64) void k_loop(ErrModelView EM, SimParams P, FastBuffers FB, const uint32_t* __restrict__ order,
+// 128 registers: four waves per SIMD, so that a wave still fits beside three of the alignment pass's.  Asked for as a register count, not as
+// waves per SIMD: with `__launch_bounds__(64, 4)` the scheduler gave up the batches of phase 1 (one wait per draw's fragment words, same
+// registers) and the kernel took as long as without the bounds table; left alone the compiler takes 129 - 133.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(128))) void k_loop(ErrModelView EM, SimParams P, FastBuffers FB, const uint32_t* __restrict__ order,
                                               uint32_t begin, uint32_t count, int Wl, int from_jobs, uint32_t c0, uint32_t c1) {
 #ifndef TKSM_ABLATE
     __builtin_amdgcn_s_setprio(2);                            // (a latency-bound kernel beside the alignment kernel's always-ready waves: see k_loopw)
@@ -1279,6 +1283,17 @@ __global__ __launch_bounds__(64) void k_loop(ErrModelView EM, SimParams P, FastB
             lf[(ww + 0) * 64 + lane] = v[q].x; lf[(ww + 1) * 64 + lane] = v[q].y; lf[(ww + 2) * 64 + lane] = v[q].z; lf[(ww + 3) * 64 + lane] = v[q].w;
         }
     }
+    // behind the fragment words, once per wave: the bounds table of the first thresholds (loop_filter.h; 4 KB, 64 bytes per lane)
+    uint32_t* lfb = lf + (size_t)Wl * 64;
+    {
+        uint4 v[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) v[q] = EM.pt0b[q * 64 + lane];
+#pragma unroll
+        for (int q = 0; q < 4; q++) *reinterpret_cast<uint4*>(lfb + 4 * (q * 64 + lane)) = v[q];
+    }
+    __syncthreads();                                          // (one wave: orders the table's stores before the other lanes' reads)
+    const uint16_t* lfe = reinterpret_cast<const uint16_t*>(lfb);      // [LOOP_FILTER_KEYS] lo | hi << 8
     uint16_t* gnb = nb_row(FB, r);
     const uint64_t g = P.first_read + (uint64_t)r * P.stride;
     const double frag_len = (double)L, target = S.target;
@@ -1316,21 +1331,23 @@ __global__ __launch_bounds__(64) void k_loop(ErrModelView EM, SimParams P, FastB
 #ifdef TKSM_ABLATE
     if (P.ablate == 33) st = IDLE;                              // timing experiment: prologue only
 #endif
-    // ---- passes of LOOP_N draws.  Phase 1, all LOOP_N draws: generator, k-mer, the k-mer's own threshold t0 (one round of gathers
-    // for all of them) -> which draws change something (~19 %).  Phase 2, the first LOOP_K of those only: the generator once more
+    // ---- passes of LOOP_N draws.  Phase 1, all LOOP_N draws: generator, k-mer, the bounds of t0 under the k-mer's coarse key from
+    // LDS -- they decide ~9 draws of 10 -- and the k-mer's own threshold t0 for the rest (one round of gathers for all of them; a
+    // decided draw reads the common dummy line) -> which draws change something (~19 %).  Phase 2, the first LOOP_K of those only: the generator once more
     // (its other words), then segment thresholds + the slot codes under the k-mer, then the alternative -- the rounds of dependent
     // gathers that go to the read's own rows and the big tables are paid once per pass, not once per four draws.  Phase 3 applies
     // them in draw order; the no-op draws in between only advance the draw counter (the stop rules move with applied changes
     // alone).  Draws behind the LOOP_K-th changing one, a re-estimation point or the end of the loop are dropped and drawn again.
-    // (the k-mer index of a chosen draw is cut out of the fragment words again in phase 2: a second array for the indices would make
-    // the wave's LDS 22 KB -- seven waves per CU; at 20 KB it is eight, two on every SIMD)
-    uint32_t* ldi = lf + (size_t)Wl * 64;                     // [LOOP_N][64] draw positions of the pass
+    // (position and k-mer index of a chosen draw are made again in phase 2, from the generator call it needs anyway and from the
+    // fragment words: arrays for them would make the wave's LDS 24 or 28 KB -- six waves per CU; at 20 KB it is eight, two on every SIMD)
+    const bool use_tab = EM.type != 0 && EM.alt0_noop;        // otherwise every draw changes something: the table is not consulted
     while (__ballot(st == RUN) != 0ull) {
         if (st != RUN) continue;
         const uint32_t navail = (uint32_t)max(0ll, min((long long)LOOP_N, loop_limit - (long long)n));     // draws of this pass below the loop limit
         uint32_t mask = 0u;                                    // draws of the pass that change something
         {
-            uint32_t dwv[LOOP_N], t0v[LOOP_N];
+            // (three straight-line stages, each a batch of loads: fragment words -> k-mers; bounds from LDS; thresholds of the undecided)
+            uint32_t dwv[LOOP_N], kxv[LOOP_N];
 #pragma unroll
             for (int b = 0; b < LOOP_N; b++) {
                 const Ph4 d = philox(P.seed, g, ST_DRAW, n + (uint32_t)b);
@@ -1339,24 +1356,42 @@ __global__ __launch_bounds__(64) void k_loop(ErrModelView EM, SimParams P, FastB
                 const int w = di1 >> 4, o = di1 & 15;
 #ifdef TKSM_ABLATE
                 // timing experiments (results are wrong): 35 / 36: every k-mer from the words in LDS; 34 / 36: no first-level threshold gather
-                const bool abl_lds = P.ablate == 35 || P.ablate == 36, abl_t0 = P.ablate == 34 || P.ablate == 36;
+                const bool abl_lds = P.ablate == 35 || P.ablate == 36;
                 const uint32_t hi = (abl_lds || w < Wl) ? lf[min(w, Wl - 1) * 64 + lane] : f2[w], lo = (abl_lds || w + 1 < Wl) ? lf[min(w + 1, Wl - 1) * 64 + lane] : f2[w + 1];
 #else
                 const uint32_t hi = w < Wl ? lf[w * 64 + lane] : f2[w], lo = w + 1 < Wl ? lf[(w + 1) * 64 + lane] : f2[w + 1];
 #endif
-                const uint32_t kx = (uint32_t)(mk64(hi, lo) >> (64 - 2 * o - 2 * k)) & kmask;
-                ldi[b * 64 + lane] = (uint32_t)di1;
+                kxv[b] = (uint32_t)(mk64(hi, lo) >> (64 - 2 * o - 2 * k)) & kmask;
+            }
+            uint32_t ev[LOOP_N];
+#pragma unroll
+            for (int b = 0; b < LOOP_N; b++) ev[b] = lfe[tklf::loop_filter_key(kxv[b])];
+            uint32_t sure = 0u, und = 0u;                      // draws the bounds prove changing; draws they leave to t0
+#pragma unroll
+            for (int b = 0; b < LOOP_N; b++) {
+                const int c = tklf::loop_filter_classify(ev[b], dwv[b]);
+                sure |= c == tklf::DRAW_CHANGE ? 1u << b : 0u;
+                und |= c == tklf::DRAW_UNDECIDED ? 1u << b : 0u;
+            }
+            if (!use_tab) { sure = (1u << LOOP_N) - 1u; und = 0u; }
 #ifdef TKSM_ABLATE
-                t0v[b] = abl_t0 ? 0xCF000000u : EM.pt0[kx];
+            const bool abl_t0 = P.ablate == 34 || P.ablate == 36;
+            if (abl_t0 && use_tab) { sure = 0u; und = (1u << LOOP_N) - 1u; }
+#endif
+            uint32_t t0v[LOOP_N];
+#pragma unroll
+            for (int b = 0; b < LOOP_N; b++) {
+                // (a 32-bit byte offset from the table's uniform base: half the address registers of an indexed pointer)
+                const uint32_t off = (und >> b) & 1u ? kxv[b] << 2 : 0u;
+#ifdef TKSM_ABLATE
+                t0v[b] = abl_t0 ? 0xCF000000u : *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(EM.pt0) + off);
 #else
-                t0v[b] = EM.pt0[kx];
+                t0v[b] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(EM.pt0) + off);
 #endif
             }
 #pragma unroll
-            for (int b = 0; b < LOOP_N; b++) {
-                const bool chg = EM.type == 0 || !EM.alt0_noop || !(dwv[b] < t0v[b]);
-                mask |= (chg && (uint32_t)b < navail) ? 1u << b : 0u;
-            }
+            for (int b = 0; b < LOOP_N; b++) mask |= !(dwv[b] < t0v[b]) ? 1u << b : 0u;
+            mask = (sure | (und & mask)) & ((1u << navail) - 1u);
         }
         // ---- the first LOOP_K changing draws (relative index LOOP_N: none)
         int di[LOOP_K], kidx[LOOP_K];
@@ -1371,7 +1406,7 @@ __global__ __launch_bounds__(64) void k_loop(ErrModelView EM, SimParams P, FastB
                 const uint32_t bb = min(bj[j], (uint32_t)LOOP_N - 1u);
                 const Ph4 d = philox(P.seed, g, ST_DRAW, n + bb);
                 dw[j] = d.y;
-                di[j] = (int)ldi[bb * 64 + lane];
+                di[j] = (int)__umulhi(d.x, kmer_range);
                 const int w = di[j] >> 4, o = di[j] & 15;
                 const uint32_t hi = w < Wl ? lf[w * 64 + lane] : f2[w], lo = w + 1 < Wl ? lf[(w + 1) * 64 + lane] : f2[w + 1];
                 kidx[j] = (int)((uint32_t)(mk64(hi, lo) >> (64 - 2 * o - 2 * k)) & kmask);
@@ -1533,7 +1568,10 @@ __global__ __launch_bounds__(64) void k_loop(ErrModelView EM, SimParams P, FastB
         st_aligns++;
         uint32_t p0 = 0, nrows = (uint32_t)L;
         if (L > 1000) {
-            p0 = __umulhi(philox(P.seed, g, ST_ALNPOS, aln_no).x, (uint32_t)(L - 1000 + 1));
+            // (the read's generator index made again from r: kept from the prologue it is the one value that goes to scratch at 128 registers)
+            uint32_t r2 = r;
+            asm volatile("" : "+v"(r2));
+            p0 = __umulhi(philox(P.seed, P.first_read + (uint64_t)r2 * P.stride, ST_ALNPOS, aln_no).x, (uint32_t)(L - 1000 + 1));
             nrows = 1000u;
         }
         *reinterpret_cast<uint4*>(FB.job_meta + 4ull * job) = make_uint4(r, p0, nrows, 0u);
@@ -3090,7 +3128,7 @@ hipError_t launch_loop(const ErrModelView& em, const SimParams& p, const FastBuf
                        uint32_t count, int lcap, int from_jobs, uint32_t c0, uint32_t c1, hipStream_t s) {
     if (!count) return hipSuccess;
     const int Wl = loop_lds_words(lcap);
-    hipLaunchKernelGGL(k_loop, dim3((count + 63) / 64), dim3(64), (size_t)Wl * 256 + (size_t)LOOP_N * 64 * 4, s, em, p, fb, order, begin, count, Wl, from_jobs, c0, c1);
+    hipLaunchKernelGGL(k_loop, dim3((count + 63) / 64), dim3(64), (size_t)Wl * 256 + tklf::LOOP_FILTER_BYTES, s, em, p, fb, order, begin, count, Wl, from_jobs, c0, c1);
     return hipGetLastError();
 }
 hipError_t launch_loopw(const ErrModelView& em, const SimParams& p, const FastBuffers& fb, const uint32_t* order, uint32_t begin,
