@@ -485,6 +485,54 @@ int tksmseq_concat(tksmseq_ctx* ctx, const tksmseq_batch* const* in, uint64_t n_
  * of --batch-bytes over --devices like `tksm polyA`.  There is no `tksm merge`: on files Mrg is `cat`. */
 int tksmseq_filter_main(int argc, char** argv);
 
+/* ---- unsegment and shuffle: glue and reorder molecules on the device -------------------------------------------------------------------
+ * tksmseq_glue replaces the loop of Unsegment_module::run (src/unsegment.cpp:88-105) and molecule_descriptor::concat (src/interval.h:893-896).
+ * Molecule i of `in` (depth-unrolled, like every transform here) joins its predecessor iff i > 0 and joins(first_molecule_index + i), with
+ *   joins(g) = g > 0 && Philox(seed, g, stream 30, block 0).x / 2^32 < probability
+ * (g: the molecule's index in the whole input; the first molecule of a call is always a head).  Any probability is taken: <= 0 and NaN glue
+ * nothing, >= 1 glues the batch into one molecule.  A chain -- a head and the maximal run of joiners behind it -- becomes one molecule with the
+ * head's id, depth 1, and the segments of all members in order, strands and substitutions unchanged.  Comments: the head's is parsed, the
+ * written id of every joiner is appended to key Cat in order (add_comment("Cat", md.get_id()), :99), and the result is dumped key-sorted
+ * (a head with a bare "Cat;" keeps "Cat;", one with "Cat=x;" gets "Cat=x,<ids>;"); a joiner's own comment is dropped, as in the reference;
+ * a head without joiners keeps its comment; an input without comments still gets "Cat=...;" on glued heads; none, and no id fetch, with
+ * TKSMSEQ_MOL_NO_COMMENTS.  An empty input gives an empty batch.  TKSMSEQ_ELIMIT ("glue: ..."): a result beyond the table limits of a batch.
+ * Two deliberate departures from the reference:
+ *   - the last chain is written.  The reference never writes its last `current` (there is no `output << current` behind the loop at :91-105),
+ *     so every run of it silently loses its final molecule or chain;
+ *   - unrolled molecules draw for themselves.  The reference glues records: a depth-3 head gives three identical chimeras and a joiner's depth
+ *     is lost.  Here every unrolled molecule draws for itself, as in every other transform.
+ * The reference draws from one mt19937, so agreement with it is distributional only. */
+typedef struct {
+    uint64_t seed;
+    uint64_t first_molecule_index;   /* index of molecule 0 of `in` in the whole input (streaming in pieces) */
+    double probability;              /* -p/--probability */
+    int32_t flags;                   /* TKSMSEQ_MOL_NO_COMMENTS or 0 */
+    int32_t reserved;
+} tksmseq_glue_params;
+int tksmseq_glue(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_glue_params* params, tksmseq_batch** out);
+/* joins(g) on the host: 1 / 0, the device's draw bit for bit (needs no context) */
+int tksmseq_glue_joins(uint64_t seed, double probability, uint64_t molecule_index);
+/* tksmseq_shuffle replaces Shuffle_module::shuffle_stream (src/shuffle.cpp:23-44) on the n unrolled molecules of `in`; one call is one stream.
+ * key(s) = x << 32 | y of Philox(seed, s, stream 31, block 0).  buffer_size 0 or >= n: the molecules in the order of (key(i), i) ascending, a
+ * uniformly random permutation.  1 <= buffer_size = B < n: the reference's buffer, step for step -- slots 0 .. B-1 hold molecules 0 .. B-1; for
+ * t = B .. n-1, slot = umulhi(Philox(seed, t, stream 35, block 0).x, B), output t - B is the occupant of slot, and t takes the slot; the last B
+ * outputs are the slots' final occupants in the order of (key(s), s) over the slots -- computed with two sorts, not a sequential loop.  B = 1
+ * is the identity.  buffer_size chooses the ORDER the reference would give; it does not bound memory.  Ids get their unroll suffix; comments
+ * follow their molecules (none with TKSMSEQ_MOL_NO_COMMENTS).  TKSMSEQ_ELIMIT ("shuffle: ...") as above. */
+typedef struct {
+    uint64_t seed;
+    uint64_t buffer_size;            /* --buffer-size; 0: the whole input */
+    int32_t flags;                   /* TKSMSEQ_MOL_NO_COMMENTS or 0 */
+    int32_t reserved;
+} tksmseq_shuffle_params;
+int tksmseq_shuffle(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_shuffle_params* params, tksmseq_batch** out);
+/* `tksm unsegment` (Unsegment_module src/unsegment.cpp:22-116): -i, -o, -p/--probability; "<name> is required!" per missing one, the help, exit
+ * 1; streamed in batches of --batch-bytes over --devices, a piece ending only in front of a record whose first molecule does not join, so the
+ * output depends on neither.  `tksm shuffle` (Shuffle_module src/shuffle.cpp:22-125): -i, -o, --buffer-size B (long only; 0 is refused); the
+ * whole input is one batch on the first entry of --devices. */
+int tksmseq_unsegment_main(int argc, char** argv);
+int tksmseq_shuffle_main(int argc, char** argv);
+
 /* ---- tail-noise: random and hairpin noise appended on the device ----------------------------------------------------------------------
  * tksmseq_append_noise replaces NoiseAdder::operator() (src/append_noise.cpp:83-128; module AppendNoise_module :131-229) -- not to be
  * confused with the Badread tail-noise MODEL of tksmseq_load_tail_model.  Molecule i (depth-unrolled, like every segment edit; the

@@ -94,6 +94,14 @@ class FilterParams(C.Structure):             # tksmseq_filter_params
 FLT_TEXT, FLT_INFO, FLT_SIZE, FLT_LOCUS = 0, 1, 2, 3
 
 
+class GlueParams(C.Structure):               # tksmseq_glue_params
+    _fields_ = [("seed", C.c_uint64), ("first_molecule_index", C.c_uint64), ("probability", C.c_double), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ShuffleParams(C.Structure):            # tksmseq_shuffle_params
+    _fields_ = [("seed", C.c_uint64), ("buffer_size", C.c_uint64), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class WgsParams(C.Structure):                # tksmseq_wgs_params
     _fields_ = [("seed", C.c_uint64), ("dist", C.c_int32), ("reserved", C.c_int32), ("a", C.c_double), ("b", C.c_double),
                 ("base_count", C.c_int64), ("first_candidate", C.c_uint64), ("n_candidates", C.c_uint64),
@@ -165,6 +173,7 @@ SYMBOLS = [
     "tksmseq_abundance_cell", "tksmseq_abundance_read", "tksmseq_abundance_hits", "tksmseq_abundance_device_ms", "tksmseq_abundance_write",
     "tksmseq_abundance_free", "tksmseq_abundance_main",
     "tksmseq_filter", "tksmseq_concat", "tksmseq_filter_main",
+    "tksmseq_glue", "tksmseq_glue_joins", "tksmseq_shuffle", "tksmseq_unsegment_main", "tksmseq_shuffle_main",
 ]
 
 _lib = None
@@ -277,6 +286,11 @@ def load():
         "tksmseq_filter": (C.c_int, [vp, vp, P(FilterParams), P(vp), P(vp)]),
         "tksmseq_concat": (C.c_int, [vp, P(vp), u64, i32, P(vp)]),
         "tksmseq_filter_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
+        "tksmseq_glue": (C.c_int, [vp, vp, P(GlueParams), P(vp)]),
+        "tksmseq_glue_joins": (C.c_int, [u64, C.c_double, u64]),
+        "tksmseq_shuffle": (C.c_int, [vp, vp, P(ShuffleParams), P(vp)]),
+        "tksmseq_unsegment_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
+        "tksmseq_shuffle_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

@@ -40,20 +40,6 @@ int scan_u64(tksmseq_ctx* ctx, const uint64_t* in, uint64_t* out, uint64_t n) {
     return TKSMSEQ_OK;
 }
 
-// the permutation that orders n keys (stable), and the sorted keys
-template <class K, class Sort>
-int sort_pairs(tksmseq_ctx* ctx, Sort sort, const K* keys, K* keys_sorted, uint32_t* perm, uint32_t n, int end_bit) {
-    hipStream_t s = ctx->stream;
-    TmpBuf d_iota(s), d_temp(s);
-    HIPCHK(ctx, d_iota.ensure((size_t)n * 4));
-    HIPCHK(ctx, tk::launch_abund_iota(d_iota.as<uint32_t>(), n, s));
-    size_t bytes = 0;
-    HIPCHK(ctx, sort(nullptr, &bytes, keys, keys_sorted, d_iota.as<uint32_t>(), perm, n, end_bit, s));
-    HIPCHK(ctx, d_temp.ensure(bytes + 256));
-    HIPCHK(ctx, sort(d_temp.p, &bytes, keys, keys_sorted, d_iota.as<uint32_t>(), perm, n, end_bit, s));
-    return TKSMSEQ_OK;
-}
-
 // a segmented sum over perm: the chunk list (made once per index) and the buffers of a round
 struct SegSum {
     TmpBuf chunk_off, chunk_seg, partial, sum, block_part, total;

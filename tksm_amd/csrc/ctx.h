@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/tksmseq.h"
+#include "abund_kernels.h"
 #include "host.h"
 #include "kernels.h"
 #include "tsb_host.h"
@@ -299,6 +300,21 @@ struct tksmseq_ctx : ContigLookup {
         return it == contig_index.end() ? -1 : it->second;
     }
 };
+
+// the permutation that orders n keys (stable; sort: abund_sort_u32 / abund_sort_u64 over bits [0, end_bit)), and the sorted keys; queued on
+// the context's stream (abundance; shuffle)
+template <class K, class Sort>
+int sort_pairs(tksmseq_ctx* ctx, Sort sort, const K* keys, K* keys_sorted, uint32_t* perm, uint32_t n, int end_bit) {
+    hipStream_t s = ctx->stream;
+    TmpBuf d_iota(s), d_temp(s);
+    HIPCHK(ctx, d_iota.ensure((size_t)n * 4));
+    HIPCHK(ctx, tk::launch_abund_iota(d_iota.as<uint32_t>(), n, s));
+    size_t bytes = 0;
+    HIPCHK(ctx, sort(nullptr, &bytes, keys, keys_sorted, d_iota.as<uint32_t>(), perm, n, end_bit, s));
+    HIPCHK(ctx, d_temp.ensure(bytes + 256));
+    HIPCHK(ctx, sort(d_temp.p, &bytes, keys, keys_sorted, d_iota.as<uint32_t>(), perm, n, end_bit, s));
+    return TKSMSEQ_OK;
+}
 
 // a batch whose tables were written on the device (PCR, truncation): lengths, sorted order and sizing on the host
 int finalize_device_batch(tksmseq_ctx* ctx, tksmseq_batch* b);

@@ -122,6 +122,28 @@ struct CatBase { uint64_t mol, ivl, mod, id; uint32_t lit; uint64_t pool; };
 hipError_t launch_cat_write(const MolView& m, const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off, const CatBase& base, uint64_t* lits,
                             const MolOut& o, hipStream_t s);
 
+// unsegment (src/unsegment.cpp:88-105): glue a molecule behind its predecessor with probability p; see mdf_kernels.hip
+// join[r]: 1 when molecule r (index first_index + r of the whole input) joins its predecessor, never for r = 0; head[r] = 1 - join[r] as a scan
+// input; the three counts of molecule r on its own, the id length 0 for a joiner
+hipError_t launch_glue_plan(const MolView& m, uint64_t seed, double p, uint64_t first_index, uint8_t* join, uint64_t* head, uint64_t* n_ivls, uint64_t* n_mods,
+                            uint64_t* n_idlen, hipStream_t s);
+// rank: exclusive scan of head ([n_reads + 1]); the offsets: scans of the counts.  Output molecule rank[r] is the chain that head r opens
+hipError_t launch_glue_write(const MolView& m, const uint8_t* join, const uint64_t* rank, const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off,
+                             const MolOut& o, hipStream_t s);
+
+// shuffle (src/shuffle.cpp:23-44): the buffer of n_slots molecules as a sort; see mdf_kernels.hip.  n_arrivals = n - n_slots
+hipError_t launch_shf_key(uint64_t n_slots, uint64_t seed, uint64_t* key, hipStream_t s);                       // key[s] of slot s
+hipError_t launch_shf_slot(uint64_t n_arrivals, uint32_t n_slots, uint64_t seed, uint32_t* slot, hipStream_t s);   // slot[a] of molecule n_slots + a
+// slot_sorted / arrival_sorted: the arrivals after a stable sort by slot; src[a]: the molecule written when arrival a comes
+hipError_t launch_shf_evict(uint64_t n_arrivals, uint32_t n_slots, const uint32_t* slot_sorted, const uint32_t* arrival_sorted, uint32_t* src, hipStream_t s);
+// order: the slots sorted by (key, slot); src_tail[q] (= src[n_arrivals + q]): the final occupant of slot order[q]
+hipError_t launch_shf_occupant(uint32_t n_slots, uint64_t n_arrivals, const uint32_t* order, const uint32_t* slot_sorted, const uint32_t* arrival_sorted,
+                               uint32_t* src_tail, hipStream_t s);
+// a gather: output molecule j is input molecule src[j] (unrolled: ids with their suffix); counts, then -- with their scans -- the copy
+hipError_t launch_gather_count(const MolView& m, const uint32_t* src, uint64_t n, uint64_t* n_ivls, uint64_t* n_mods, uint64_t* n_idlen, hipStream_t s);
+hipError_t launch_gather_write(const MolView& m, const uint32_t* src, uint64_t n, const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off,
+                               const MolOut& o, hipStream_t s);
+
 // random-wgs (src/random_wgs.cpp:181-207): fragments of the whole genome, one lane per candidate; see mdf_kernels.hip
 constexpr int WGS_LDS_CONTIGS = 2048;       // running sums of that many contigs are searched in LDS (16 KB), more in global memory
 enum { WGS_NORMAL = 0, WGS_UNIFORM = 1, WGS_LOGNORMAL = 2, WGS_EXPONENTIAL = 3 };

@@ -14,6 +14,8 @@
 //   RWGS_module::run             src/random_wgs.cpp:181-207 whole-genome fragments: position, length and strand draws, no input
 //   NoiseAdder::operator()       src/append_noise.cpp:83-128 tail noise: a random literal, or the last segments again as a hairpin
 //   Splicer_module::run          src/transcribe.cpp:170-197 an abundance row becomes `depth` copies of its transcript's exons, no input batch
+//   Unsegment_module::run        src/unsegment.cpp:88-105  a molecule is glued behind its predecessor with a probability (concat, src/interval.h:893-896)
+//   Shuffle_module::shuffle_stream  src/shuffle.cpp:23-44  the molecules in a random order, whole or through a buffer of B slots
 // Integer / byte work, one LANE per molecule (tail-noise alone spreads its per-base work: one wave per molecule, or a flat grid): the tables of a molecule are a few dozen bytes, the work per molecule is a short
 // serial walk (tree of copies; list of segments).  The reference draws from a sequential Mersenne Twister; here every
 // decision has its own Philox counter (template molecule, path of copy cycles, purpose), so the result does not depend on
@@ -26,7 +28,8 @@ namespace tk {
 
 struct Ph4m { uint32_t x, y, z, w; };
 enum { ST_PCR_PICK = 16, ST_PCR_EMIT = 17, ST_PCR_CHILD = 18, ST_PCR_MUT = 19, ST_TRC_LEN = 24, ST_TRC_SIDE = 25,
-       ST_PLA_LEN = 26, ST_TAG5 = 27, ST_TAG3 = 28, ST_FLIP = 29, ST_WGS_POS = 32, ST_WGS_LEN = 33, ST_WGS_STRAND = 34,
+       ST_PLA_LEN = 26, ST_TAG5 = 27, ST_TAG3 = 28, ST_FLIP = 29, ST_GLUE = 30, ST_SHF_KEY = 31, ST_WGS_POS = 32, ST_WGS_LEN = 33, ST_WGS_STRAND = 34,
+       ST_SHF_SLOT = 35,
        ST_NOISE_LEN = 40, ST_NOISE_SEQ = 41, ST_NOISE_ERR = 42, ST_TSB = 56 };
 
 DEV Ph4m philox_raw(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
@@ -997,20 +1000,20 @@ __global__ void k_flt_pred(MolView M, const FltCond* __restrict__ conds, uint32_
     if (F.n_ivls) { F.n_ivls[r] = ok ? 0ull : ni; F.n_mods[r] = ok ? 0ull : nm; F.n_idlen[r] = ok ? 0ull : nd; }
 }
 
-// molecule r of M becomes molecule j of O: intervals from io, substitutions from mo, id bytes (with the unroll suffix) at id_at;
-// literal indices move up by lit_shift
-DEV void copy_molecule(const MolView& M, uint64_t r, uint64_t j, uint64_t io, uint64_t mo, uint64_t id_at, uint32_t lit_shift, const MolOut& O) {
+// the id of molecule r of M (with the unroll suffix) becomes the id of molecule j of O, its bytes at id_at
+DEV void copy_id(const MolView& M, uint64_t r, uint64_t j, uint64_t id_at, const MolOut& O) {
+    const BatchView& B = M.B;
+    uint8_t* d = O.idpool + id_at;
+    const uint32_t so = B.ids[2 * r], sl = B.ids[2 * r + 1];
+    uint32_t k = 0;
+    for (; k < sl; k++) d[k] = B.idpool[so + k];
+    if (M.dup && (M.dup[r] >> 31)) { d[k++] = '_'; k += (uint32_t)put_dec(d + k, M.dup[r] & 0x7fffffffu); }
+    O.ids[2 * j] = (uint32_t)id_at; O.ids[2 * j + 1] = k;
+}
+// the segments of molecule r of M become the intervals of O from io on, their substitutions from mo on; literal indices move up by lit_shift
+DEV void copy_segments(const MolView& M, uint64_t r, uint64_t io, uint64_t mo, uint32_t lit_shift, const MolOut& O) {
     const BatchView& B = M.B;
     const uint32_t ib = B.reads[2 * r], ic = B.reads[2 * r + 1];
-    O.reads[2 * j] = (uint32_t)io; O.reads[2 * j + 1] = ic;
-    {
-        uint8_t* d = O.idpool + id_at;
-        const uint32_t so = B.ids[2 * r], sl = B.ids[2 * r + 1];
-        uint32_t k = 0;
-        for (; k < sl; k++) d[k] = B.idpool[so + k];
-        if (M.dup && (M.dup[r] >> 31)) { d[k++] = '_'; k += (uint32_t)put_dec(d + k, M.dup[r] & 0x7fffffffu); }
-        O.ids[2 * j] = (uint32_t)id_at; O.ids[2 * j + 1] = k;
-    }
     for (uint32_t i = 0; i < ic; i++) {
         const uint32_t* iv = B.intervals + 4ull * (ib + i);
         uint32_t* ov = O.intervals + 4ull * io++;
@@ -1018,6 +1021,13 @@ DEV void copy_molecule(const MolView& M, uint64_t r, uint64_t j, uint64_t io, ui
         const uint32_t mb = iv[3] & 0x7fffffffu, me = iv[7] & 0x7fffffffu;
         for (uint32_t m = mb; m < me; m++) { O.mods[2 * mo] = B.mods[2ull * m]; O.mods[2 * mo + 1] = B.mods[2ull * m + 1]; mo++; }
     }
+}
+// molecule r of M becomes molecule j of O: intervals from io, substitutions from mo, id bytes (with the unroll suffix) at id_at;
+// literal indices move up by lit_shift
+DEV void copy_molecule(const MolView& M, uint64_t r, uint64_t j, uint64_t io, uint64_t mo, uint64_t id_at, uint32_t lit_shift, const MolOut& O) {
+    O.reads[2 * j] = (uint32_t)io; O.reads[2 * j + 1] = M.B.reads[2 * r + 1];
+    copy_id(M, r, j, id_at, O);
+    copy_segments(M, r, io, mo, lit_shift, O);
 }
 
 // rank: exclusive scan of flag (molecules of the true side before r); T / F: the scans of the counts; OF is not touched without F
@@ -1034,6 +1044,108 @@ __global__ void k_cat_write(MolView M, const uint64_t* __restrict__ ivl_off, con
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r < M.B.n_reads) copy_molecule(M, r, base.mol + r, base.ivl + ivl_off[r], base.mod + mod_off[r], base.id + id_off[r], base.lit, O);
     if (r < M.B.n_literals) { lits[2ull * (base.lit + r)] = M.B.literals[2 * r] + base.pool; lits[2ull * (base.lit + r) + 1] = M.B.literals[2 * r + 1]; }
+}
+
+// ------------------------------------------------------------------------------------------------
+// unsegment (Glu, src/unsegment.cpp:88-105 with molecule_descriptor::concat, src/interval.h:893-896): a molecule is glued behind its
+// predecessor with a probability.  Unrolled molecule g of the whole input joins when g > 0 and u01(Philox(seed, g, ST_GLUE, 0).x) <
+// probability; the first molecule of a call is a head whatever it draws.  A chain -- a head and the joiners behind it -- becomes ONE
+// molecule: the head's id, the segments of all members in order.  Chains are contiguous, so the output's interval and substitution
+// tables are the input's unrolled ones in the same order: every lane copies its own molecule's segments to the offsets the scans give
+// it, however long its chain is, and only the heads write a reads entry and an id.  A head finds the end of its chain without walking
+// it: rank is the exclusive scan of the head flags, non-decreasing, so the next head is the last index whose rank is still this head's
+// rank + 1 (n when there is none) -- a binary search, the same whether the chain has two members or spans many blocks.
+// Two departures from the reference, both deliberate: the last chain IS written (the reference's loop never writes its
+// last `current`), and every unrolled molecule draws for itself (the reference glues records, so a depth-3 head gives three equal
+// chimeras and a joiner's depth is lost).
+// ------------------------------------------------------------------------------------------------
+__global__ void k_glue_plan(MolView M, uint64_t seed, double p, uint64_t first_index, uint8_t* __restrict__ join, uint64_t* __restrict__ head,
+                            uint64_t* __restrict__ n_ivls, uint64_t* __restrict__ n_mods, uint64_t* __restrict__ n_idlen) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= M.B.n_reads) return;
+    const bool j = r > 0 && u01(philox_mol(seed, first_index + r, ST_GLUE, 0).x) < p;      // (NaN compares false: nothing joins)
+    join[r] = j ? 1 : 0;
+    head[r] = j ? 0ull : 1ull;
+    n_ivls[r] = M.B.reads[2 * r + 1];
+    n_mods[r] = mol_mods(M.B, (uint32_t)r);
+    n_idlen[r] = j ? 0ull : (uint64_t)unrolled_id_len(M, r);
+}
+
+// rank: exclusive scan of head ([n + 1]); ivl_off / mod_off / id_off: the scans of the counts
+__global__ void k_glue_write(MolView M, const uint8_t* __restrict__ join, const uint64_t* __restrict__ rank, const uint64_t* __restrict__ ivl_off,
+                             const uint64_t* __restrict__ mod_off, const uint64_t* __restrict__ id_off, MolOut O) {
+    const uint64_t n = M.B.n_reads;
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    copy_segments(M, r, ivl_off[r], mod_off[r], 0u, O);
+    if (join[r]) return;
+    const uint64_t j = rank[r];
+    uint64_t lo = r + 1, hi = n;                                      // the last index in [r + 1, n] with rank <= j + 1 (rank[r + 1] = j + 1)
+    while (lo < hi) { const uint64_t mid = (lo + hi + 1) >> 1; if (rank[mid] <= j + 1) lo = mid; else hi = mid - 1; }
+    O.reads[2 * j] = (uint32_t)ivl_off[r]; O.reads[2 * j + 1] = (uint32_t)(ivl_off[lo] - ivl_off[r]);
+    copy_id(M, r, j, id_off[r], O);
+}
+
+// ------------------------------------------------------------------------------------------------
+// shuffle (Shf, Shuffle_module::shuffle_stream, src/shuffle.cpp:23-44).  The reference keeps a buffer of B molecules: molecule t >= B
+// draws a slot, the slot's occupant is written and t takes its place; at the end the buffer is shuffled and written.  Here the draws are
+// counter-based -- slot_t = umulhi(Philox(seed, t, ST_SHF_SLOT, 0).x, B), and the final order of the slots is that of (key(s), s) with
+// key(s) = x << 32 | y of Philox(seed, s, ST_SHF_KEY, 0) -- so the loop need not be run in sequence: after a STABLE sort of the arrivals
+// (slot_t, t) by slot the arrivals of one slot stand together in t order, the molecule written at step t is the arrival before it in
+// that run (the molecule numbered slot_t, the slot's first occupant, when t opens the run), and the slot's final occupant is the last
+// arrival of its run (s itself for a slot nothing arrived in).  Without a buffer size (or B >= n) every molecule has a slot of its
+// own, there are no arrivals, and the output is the order of (key(i), i): a uniformly random permutation up to key collisions.
+// k_shf_key: one lane per slot; k_shf_slot: one lane per arrival; the sorts are rocprim's radix sort (launch_abund_iota / abund_sort_*);
+// k_shf_evict: one lane per sorted arrival fills src[0, n - B); k_shf_occupant: one lane per slot in key order fills src[n - B, n).
+// src[j] is the input molecule that becomes output molecule j; k_gather_count / k_gather_write size and copy in that order.
+// ------------------------------------------------------------------------------------------------
+__global__ void k_shf_key(uint64_t n_slots, uint64_t seed, uint64_t* __restrict__ key) {
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_slots) return;
+    const Ph4m w = philox_mol(seed, s, ST_SHF_KEY, 0);
+    key[s] = ((uint64_t)w.x << 32) | w.y;
+}
+
+// arrival a is molecule t = B + a
+__global__ void k_shf_slot(uint64_t n_arrivals, uint32_t B, uint64_t seed, uint32_t* __restrict__ slot) {
+    const uint64_t a = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n_arrivals) return;
+    slot[a] = __umulhi(philox_mol(seed, (uint64_t)B + a, ST_SHF_SLOT, 0).x, B);
+}
+
+// slot_s / arr_s: the arrivals' slots and indices after the stable sort by slot
+__global__ void k_shf_evict(uint64_t n_arrivals, uint32_t B, const uint32_t* __restrict__ slot_s, const uint32_t* __restrict__ arr_s,
+                            uint32_t* __restrict__ src) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_arrivals) return;
+    const uint32_t s = slot_s[k];
+    src[arr_s[k]] = (k > 0 && slot_s[k - 1] == s) ? B + arr_s[k - 1] : s;
+}
+
+// order[q]: the slot at place q of the (key, slot) order; src_tail = src + n_arrivals
+__global__ void k_shf_occupant(uint64_t n_slots, uint64_t n_arrivals, uint32_t B, const uint32_t* __restrict__ order, const uint32_t* __restrict__ slot_s,
+                               const uint32_t* __restrict__ arr_s, uint32_t* __restrict__ src_tail) {
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_slots) return;
+    const uint32_t s = order[q];
+    uint64_t lo = 0, hi = n_arrivals;                                 // the first sorted arrival whose slot is above s
+    while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (slot_s[mid] <= s) lo = mid + 1; else hi = mid; }
+    src_tail[q] = (lo > 0 && slot_s[lo - 1] == s) ? B + arr_s[lo - 1] : s;
+}
+
+__global__ void k_gather_count(MolView M, const uint32_t* __restrict__ src, uint64_t n, uint64_t* __restrict__ n_ivls, uint64_t* __restrict__ n_mods,
+                               uint64_t* __restrict__ n_idlen) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t r = src[j];
+    n_ivls[j] = M.B.reads[2 * r + 1]; n_mods[j] = mol_mods(M.B, r); n_idlen[j] = unrolled_id_len(M, r);
+}
+
+__global__ void k_gather_write(MolView M, const uint32_t* __restrict__ src, uint64_t n, const uint64_t* __restrict__ ivl_off,
+                               const uint64_t* __restrict__ mod_off, const uint64_t* __restrict__ id_off, MolOut O) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    copy_molecule(M, src[j], j, ivl_off[j], mod_off[j], id_off[j], 0u, O);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1117,6 +1229,51 @@ hipError_t launch_cat_write(const MolView& m, const uint64_t* ivl_off, const uin
     const uint64_t n = m.B.n_reads > m.B.n_literals ? m.B.n_reads : (uint64_t)m.B.n_literals;
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(k_cat_write, dim3(nblk(n)), dim3(128), 0, s, m, ivl_off, mod_off, id_off, base, lits, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_glue_plan(const MolView& m, uint64_t seed, double p, uint64_t first_index, uint8_t* join, uint64_t* head, uint64_t* n_ivls, uint64_t* n_mods,
+                            uint64_t* n_idlen, hipStream_t s) {
+    if (!m.B.n_reads) return hipSuccess;
+    hipLaunchKernelGGL(k_glue_plan, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, seed, p, first_index, join, head, n_ivls, n_mods, n_idlen);
+    return hipGetLastError();
+}
+hipError_t launch_glue_write(const MolView& m, const uint8_t* join, const uint64_t* rank, const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off,
+                             const MolOut& o, hipStream_t s) {
+    if (!m.B.n_reads) return hipSuccess;
+    hipLaunchKernelGGL(k_glue_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, join, rank, ivl_off, mod_off, id_off, o);
+    return hipGetLastError();
+}
+hipError_t launch_shf_key(uint64_t n_slots, uint64_t seed, uint64_t* key, hipStream_t s) {
+    if (!n_slots) return hipSuccess;
+    hipLaunchKernelGGL(k_shf_key, dim3(nblk(n_slots)), dim3(128), 0, s, n_slots, seed, key);
+    return hipGetLastError();
+}
+hipError_t launch_shf_slot(uint64_t n_arrivals, uint32_t n_slots, uint64_t seed, uint32_t* slot, hipStream_t s) {
+    if (!n_arrivals) return hipSuccess;
+    hipLaunchKernelGGL(k_shf_slot, dim3(nblk(n_arrivals)), dim3(128), 0, s, n_arrivals, n_slots, seed, slot);
+    return hipGetLastError();
+}
+hipError_t launch_shf_evict(uint64_t n_arrivals, uint32_t n_slots, const uint32_t* slot_sorted, const uint32_t* arrival_sorted, uint32_t* src, hipStream_t s) {
+    if (!n_arrivals) return hipSuccess;
+    hipLaunchKernelGGL(k_shf_evict, dim3(nblk(n_arrivals)), dim3(128), 0, s, n_arrivals, n_slots, slot_sorted, arrival_sorted, src);
+    return hipGetLastError();
+}
+hipError_t launch_shf_occupant(uint32_t n_slots, uint64_t n_arrivals, const uint32_t* order, const uint32_t* slot_sorted, const uint32_t* arrival_sorted,
+                               uint32_t* src_tail, hipStream_t s) {
+    if (!n_slots) return hipSuccess;
+    hipLaunchKernelGGL(k_shf_occupant, dim3(nblk(n_slots)), dim3(128), 0, s, (uint64_t)n_slots, n_arrivals, n_slots, order, slot_sorted, arrival_sorted, src_tail);
+    return hipGetLastError();
+}
+hipError_t launch_gather_count(const MolView& m, const uint32_t* src, uint64_t n, uint64_t* n_ivls, uint64_t* n_mods, uint64_t* n_idlen, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_gather_count, dim3(nblk(n)), dim3(128), 0, s, m, src, n, n_ivls, n_mods, n_idlen);
+    return hipGetLastError();
+}
+hipError_t launch_gather_write(const MolView& m, const uint32_t* src, uint64_t n, const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off,
+                               const MolOut& o, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_gather_write, dim3(nblk(n)), dim3(128), 0, s, m, src, n, ivl_off, mod_off, id_off, o);
     return hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-// mdf_modules.cpp -- the `tksm pcr`, `truncate`, `polyA`, `tag`, `scb`, `flip`, `tail-noise` and `filter` (two outputs) modules on top of the
+// mdf_modules.cpp -- the `tksm pcr`, `truncate`, `polyA`, `tag`, `scb`, `flip`, `tail-noise`, `filter` (two outputs), `unsegment` and `shuffle` modules on top of the
 // C-ABI (MDF file in, MDF file out), and `random-wgs` (no input: MDF file out).
 //
 // Mirrors (file:line into vpc-ccg/tksm):
@@ -14,6 +14,8 @@
 //   RWGS_module             src/random_wgs.cpp:24-229 -r/--reference, --frag-len-dist "NAME A [B]", -o, --base-count | --depth
 //   AppendNoise_module      src/append_noise.cpp:131-229 --length-dist NAME,MU,SIGMA, --alphabet, --palindromic, --error-rate
 //   Filter_module           src/filter.cpp:119-231   -i, -t/--true-output, -f/--false-output, -c/--condition (comma-separated, repeatable), --negate
+//   Unsegment_module        src/unsegment.cpp:22-116 -i, -o, -p/--probability ("<name> is required!", the help, exit 1)
+//   Shuffle_module          src/shuffle.cpp:22-125   -i, -o, --buffer-size (long only); the whole input is one batch
 //   Splicer_module          src/transcribe.cpp:19-218 -g/--gtf, -a/--abundance, --molecule-count, -w/--weights, ... (no fusion submodule): GTF + TSV in, MDF out
 //   model-truncation        py/truncate_kde.py:36-112, :323-352 (behind src/model_truncation.cpp) PAF in, KDE model JSON out: no MDF, one context
 //   abundance               py/transcript_abundance.py:32-139, :326-389 (behind src/abundance.cpp) PAF in, expression TSV out: no MDF, one context
@@ -43,6 +45,7 @@
 #include "../../include/tksmseq.h"
 #include "abund_host.h"
 #include "filter_host.h"
+#include "glue_cut.h"
 #include "host.h"
 #include "kde_host.h"
 #include "module_log.h"
@@ -205,8 +208,11 @@ int run_pieces(const Common& c, Logger& log, const char* what, Prepare prepare, 
 
 // The input in pieces of whole molecules, on_batch(ctx, batch, piece, out) on each (piece.first: the index of its first molecule in the whole
 // input; piece.second: a second output batch for second_output), and the outputs written in input order.
+// joins (unsegment): a piece ends only in front of a record whose first molecule g has joins(g) == 0 (glue_cut.h) -- the reader holds the text
+// behind the last such record back and puts it in front of the next chunk, and reads on while a chunk has none.
 template <class OnBatch>
-int stream_batches(const Common& c, Logger& log, const char* what, OnBatch on_batch, const std::string* second_output = nullptr) {
+int stream_batches(const Common& c, Logger& log, const char* what, OnBatch on_batch, const std::string* second_output = nullptr,
+                   std::function<bool(uint64_t)> joins = nullptr) {
     // a reader thread of its own cuts the input into pieces of whole molecules and numbers them (input order), a few pieces ahead of the
     // workers: what the engine serialises is a pop from this queue, not the read + scan of a piece.  Its state lives on the heap and is
     // shared with the thread: after an error the module returns without waiting for a reader that may sit in a read() on a pipe nobody
@@ -220,16 +226,26 @@ int stream_batches(const Common& c, Logger& log, const char* what, OnBatch on_ba
     if (!rs->rd.in) { fprintf(stderr, "Could not open file %s\n", c.input.c_str()); return 1; }
     rs->rd.bytes = c.batch_bytes;
     rs->cap = c.devices.size() * 2 + 1;
-    std::thread reader([rs]() {
+    std::thread reader([rs, joins]() {
         uint64_t seq = 0, first = 0;
+        tkmod::GlueHold hold;                                     // (joins) the text behind the last cut
+        std::vector<char> chunk;
         for (;;) {
             Piece pc;
-            if (!rs->rd.next(pc.text)) {
-                if (seq) break;
-                pc.text.clear();                                  // an empty input still makes an (empty) output
+            uint64_t molecules = 0;
+            if (joins) {
+                if (rs->rd.next(chunk)) { if (!hold.push(chunk, first, joins, pc.text, molecules)) continue; }
+                else if (seq && hold.held.empty()) break;
+                else hold.flush(pc.text, molecules);              // (an empty input still makes an (empty) output)
+            } else {
+                if (!rs->rd.next(pc.text)) {
+                    if (seq) break;
+                    pc.text.clear();                              // an empty input still makes an (empty) output
+                }
+                molecules = tkmod::count_reads(pc.text.data(), pc.text.size());
             }
             pc.seq = seq++; pc.first = first;
-            first += tkmod::count_reads(pc.text.data(), pc.text.size());
+            first += molecules;
             std::unique_lock<std::mutex> l(rs->m);
             rs->put.wait(l, [&] { return rs->pieces.size() < rs->cap || rs->stop; });
             if (rs->stop) break;
@@ -852,6 +868,95 @@ extern "C" int tksmseq_filter_main(int argc, char** argv) {
     return stream_batches(c, log, "filter", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, Piece& pc, tksmseq_batch** out) -> int {
         return tksmseq_filter(ctx, in, &p, out, both ? &pc.second : nullptr);
     }, both ? &false_output : nullptr);
+}
+
+// `tksm unsegment` (Unsegment_module, src/unsegment.cpp:22-116).  Pieces end only where no chain crosses (glue_cut.h), so the output is
+// that of one call on the whole input whatever --batch-bytes and --devices are; with a probability of 1 or more the whole input is one piece.
+extern "C" int tksmseq_unsegment_main(int argc, char** argv) {
+    Common c;
+    tksmseq_glue_params p{};
+    bool have_p = false;
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            if ((o != "-p" && o != "--probability") || !v) return NOT_MINE;
+            p.probability = atof(v); have_p = true;
+            return TOOK_VALUE;
+        })) return 1;
+    static const char* help =
+        "Unsegment module: Concatenate adjacent molecules with a probability\nusage: unsegment -i INPUT -o OUTPUT -p PROBABILITY [-s SEED]\n"
+        "                 [--devices D[,D...]] [--batch-bytes B] [--verbosity L] [--log-file F]\n"
+        "Every molecule but the first is glued behind its predecessor with probability PROBABILITY; the glued ids are listed under Cat.\n";
+    if (c.help) { printf("%s", help); return 0; }
+    // validate_arguments (src/unsegment.cpp:52-68)
+    int missing = 0;
+    if (c.input.empty()) { fprintf(stderr, "input is required!\n"); missing++; }
+    if (c.output.empty()) { fprintf(stderr, "output is required!\n"); missing++; }
+    if (!have_p) { fprintf(stderr, "probability is required!\n"); missing++; }
+    if (missing) { fprintf(stderr, "%s\n", help); return 1; }
+    Logger log;
+    if (!open_log(c, "unsegment", log)) return 1;
+    p.seed = (uint64_t)c.seed;
+    return stream_batches(c, log, "unsegment", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, Piece& pc, tksmseq_batch** out) -> int {
+        tksmseq_glue_params q = p;
+        q.first_molecule_index = pc.first;
+        return tksmseq_glue(ctx, in, &q, out);
+    }, nullptr, [p](uint64_t g) { return tksmseq_glue_joins(p.seed, p.probability, g) != 0; });
+}
+
+// `tksm shuffle` (Shuffle_module, src/shuffle.cpp:22-125): the whole input is one batch on the first entry of --devices, as the reference
+// without --buffer-size (and `tksm pcr` here) holds it; --buffer-size chooses the order the reference's buffer would give, not the memory.
+extern "C" int tksmseq_shuffle_main(int argc, char** argv) {
+    Common c;
+    tksmseq_shuffle_params p{};
+    bool have_b = false;
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            if (o == "--batch-bytes" || o == "--slice-molecules") return NO_SUCH;      // (common flags this module does not have)
+            if (o != "--buffer-size" || !v) return NOT_MINE;
+            char* e = nullptr;
+            p.buffer_size = strtoull(v, &e, 10);
+            if (e == v || *e || v[0] == '-') return MALFORMED;
+            have_b = true;
+            return TOOK_VALUE;
+        })) return 1;
+    static const char* help =
+        "Shuffle module: shuffles mdfs\nusage: shuffle -i INPUT -o OUTPUT [--buffer-size B] [-s SEED]\n"
+        "               [--devices D[,D...]] [--verbosity L] [--log-file F]\n"
+        "Without --buffer-size the molecules come out in a uniformly random order.  --buffer-size B gives the order of the reference's buffer of\n"
+        "B molecules (a molecule moves at most about B places forward); it does NOT bound memory: the whole input is one batch on the first device.\n";
+    if (c.help) { printf("%s", help); return 0; }
+    // validate_arguments (src/shuffle.cpp:74-90)
+    int missing = 0;
+    if (c.input.empty()) { fprintf(stderr, "input is required!\n"); missing++; }
+    if (c.output.empty()) { fprintf(stderr, "output is required!\n"); missing++; }
+    if (missing) { fprintf(stderr, "%s\n", help); return 1; }
+    // (the reference builds uniform_int_distribution(0, buffer_size - 1) there: undefined)
+    if (have_b && p.buffer_size == 0) { fprintf(stderr, "buffer-size must be at least 1 (leave it out to shuffle the whole input)\n"); return 1; }
+    Logger log;
+    if (!open_log(c, "shuffle", log)) return 1;
+    p.seed = (uint64_t)c.seed;
+    std::string text;
+    if (!read_file(c.input, text)) { fprintf(stderr, "Could not open file %s\n", c.input.c_str()); return 1; }
+    FILE* out = fopen(c.output.c_str(), "wb");
+    if (!out) { fprintf(stderr, "Error: cannot write %s\n", c.output.c_str()); return 1; }
+    tksmseq_ctx* ctx = nullptr;
+    if (tksmseq_create(c.devices[0], &ctx)) { fprintf(stderr, "Error: %s\n", tksmseq_last_error(nullptr)); fclose(out); return 1; }
+    tksmseq_set_host_threads(ctx, (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency())));
+    const auto t0 = std::chrono::steady_clock::now();
+    tksmseq_batch *in = nullptr, *b = nullptr;
+    char* mdf = nullptr; uint64_t len = 0, n = 0;
+    int rc = tksmseq_molecules_from_mdf_text(ctx, text.data(), text.size(), &in);
+    if (!rc) rc = tksmseq_shuffle(ctx, in, &p, &b);
+    if (!rc) rc = tksmseq_batch_to_mdf_text(ctx, b, &mdf, &len);
+    if (rc) fprintf(stderr, "Error: shuffle: %s\n", tksmseq_last_error(ctx));
+    else if (len && fwrite(mdf, 1, len, out) != len) { fprintf(stderr, "Error: cannot write %s\n", c.output.c_str()); rc = 1; }
+    if (b) tksmseq_batch_info(b, &n, nullptr, nullptr);
+    tksmseq_text_free(mdf);
+    if (b) tksmseq_batch_free(ctx, b);
+    if (in) tksmseq_batch_free(ctx, in);
+    tksmseq_destroy(ctx);
+    if (fclose(out) != 0 && !rc) { fprintf(stderr, "Error: cannot write %s\n", c.output.c_str()); rc = 1; }
+    if (rc) return 1;
+    log.log(Logger::INFO, "shuffle: %llu molecules written in %.2f s", (unsigned long long)n, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return 0;
 }
 
 // `tksm model-truncation`: the reference runs py/truncate_kde.py (argparse: a missing -i / -o and an unknown option exit with 2; --list

@@ -3,6 +3,7 @@
 //   tksmseq_truncate       src/truncate.cpp:23-65, :77-227, :322-351, :362-404
 //   tksmseq_polya / _tag / _scb / _flip   src/polyA.cpp:133-148, src/tag.cpp:70-113, src/scb.cpp:57-80, src/interval.h:908-920
 //   tksmseq_filter / _concat   src/filter.cpp:21-117, :196-212 (a two-way partition); Mrg = `cat` of MDF files (batches joined)
+//   tksmseq_glue / _shuffle    src/unsegment.cpp:88-105 (chains of glued molecules), src/shuffle.cpp:23-44 (the buffer as two sorts and a gather)
 //   tksmseq_wgs            src/random_wgs.cpp:181-207 (no input: the molecules are made on the device)
 //   tksmseq_append_noise   src/append_noise.cpp:83-128 (tail-noise: a random literal or a hairpin behind every molecule)
 //   tksmseq_transcribe     src/transcribe.cpp:170-197 (no input batch: abundance rows x the context's transcript table)
@@ -928,6 +929,111 @@ int tksmseq_concat(tksmseq_ctx* ctx, const tksmseq_batch* const* in, uint64_t n_
                 else if ((rc = cc.put(ctx, b.get(), in[k], r, "concat"))) return rc;
             }
         }
+    }
+    return b.finish(out);
+}
+
+// ---- unsegment and shuffle -------------------------------------------------------------------------------------------------------
+// joins(g) of the glue definition on the host: the draw of k_glue_plan (ST_GLUE = 30), word for word
+int tksmseq_glue_joins(uint64_t seed, double probability, uint64_t molecule_index) {
+    if (molecule_index == 0) return 0;
+    const Ph4h w = philox_host(seed, (uint32_t)molecule_index, (uint32_t)(molecule_index >> 32), 30u, 0u);
+    return (double)w.x * (1.0 / 4294967296.0) < probability ? 1 : 0;
+}
+
+int tksmseq_glue(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_glue_params* p, tksmseq_batch** out) {
+    if (!ctx || !in || !p || !out) return TKSMSEQ_EINVAL;
+    *out = nullptr;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint64_t n = in->n_reads;
+    const tk::MolView M = mol_view(in);
+    TmpBuf d_join(s), d_head(s), d_rank(s), n_ivl(s), n_mod(s), n_idl(s);
+    HIPCHK(ctx, d_join.ensure(n + 16));
+    for (DevBuf* x : {(DevBuf*)&d_head, (DevBuf*)&n_ivl, (DevBuf*)&n_mod, (DevBuf*)&n_idl}) HIPCHK(ctx, x->ensure(n * 8 + 16));
+    HIPCHK(ctx, tk::launch_glue_plan(M, p->seed, p->probability, p->first_molecule_index, d_join.as<uint8_t>(), d_head.as<uint64_t>(), n_ivl.as<uint64_t>(),
+                                     n_mod.as<uint64_t>(), n_idl.as<uint64_t>(), s));
+    OutBatch b(ctx);
+    uint64_t n_heads = 0;
+    int rc;
+    if ((rc = scan_async(ctx, d_head, d_rank, n, &n_heads)) || (rc = b.scan(n_ivl, n_mod, n_idl, n))) return rc;      // (the second drains the stream: n_heads is there)
+    if ((rc = b.alloc(n_heads, "glue: ")) || (rc = b.literals(in))) return rc;
+    HIPCHK(ctx, tk::launch_glue_write(M, d_join.as<uint8_t>(), d_rank.as<uint64_t>(), b.o_ivl.as<uint64_t>(), b.o_mod.as<uint64_t>(), b.o_id.as<uint64_t>(), b.tables(), s));
+    // comments: a head without joiners keeps its entry; a glued head's is parsed, gets the written ids of its joiners under Cat
+    // (add_comment("Cat", md.get_id()), src/unsegment.cpp:99) and is dumped again; a joiner's own comment is dropped
+    const bool glued = n_heads < n;
+    if (!(p->flags & TKSMSEQ_MOL_NO_COMMENTS) && (glued || !in->h_comments.empty())) {
+        std::vector<uint8_t> join(n);
+        HostTables H;
+        if (n) HIPCHK(ctx, hipMemcpyAsync(join.data(), d_join.p, n, hipMemcpyDeviceToHost, s));
+        if (glued) { if ((rc = H.fetch(ctx, in, HostTables::IDS))) return rc; }
+        else HIPCHK(ctx, hipStreamSynchronize(s));
+        const bool have = !in->h_comments.empty();
+        b->h_comments.reserve(2 * n_heads);
+        CommentCopier cc;
+        for (uint64_t r = 0; r < n;) {
+            uint64_t e = r + 1;
+            while (e < n && join[e]) e++;
+            if (e == r + 1) {
+                if (have) rc = cc.put(ctx, b.get(), in, r, "glue");
+                else { b->h_comments.push_back((uint32_t)b->h_comment_pool.size()); b->h_comments.push_back(0u); rc = TKSMSEQ_OK; }
+            } else {
+                Meta meta = have ? parse_meta(in->h_comment_pool.data() + in->h_comments[2 * r], in->h_comments[2 * r + 1]) : Meta();
+                std::vector<std::string>& cat = meta["Cat"];
+                for (uint64_t q = r + 1; q < e; q++) {
+                    std::string id(H.idpool.data() + H.ids[2 * q], H.ids[2 * q + 1]);
+                    if (!in->h_dup.empty() && (in->h_dup[q] >> 31)) id += "_" + std::to_string(in->h_dup[q] & 0x7fffffffu);
+                    cat.push_back(std::move(id));
+                }
+                rc = append_comment(ctx, b.get(), dump_meta(meta), "glue");
+            }
+            if (rc) return rc;
+            r = e;
+        }
+    }
+    return b.finish(out);
+}
+
+int tksmseq_shuffle(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_shuffle_params* p, tksmseq_batch** out) {
+    if (!ctx || !in || !p || !out) return TKSMSEQ_EINVAL;
+    *out = nullptr;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint64_t n = in->n_reads;
+    if (n >= 0xffffffffull) { ctx->err = "shuffle: more than 2^32 molecules in one call"; return TKSMSEQ_ELIMIT; }
+    // whole mode is the windowed rule with a slot per molecule: no arrivals
+    const uint32_t B = (p->buffer_size == 0 || p->buffer_size >= n) ? (uint32_t)n : (uint32_t)p->buffer_size;
+    const uint64_t m = n - B;
+    int rc;
+    TmpBuf d_key(s), d_key_s(s), d_order(s), d_slot(s), d_slot_s(s), d_arr_s(s), d_src(s), n_ivl(s), n_mod(s), n_idl(s);
+    for (DevBuf* x : {(DevBuf*)&d_key, (DevBuf*)&d_key_s}) HIPCHK(ctx, x->ensure((size_t)B * 8 + 16));
+    for (DevBuf* x : {(DevBuf*)&d_slot, (DevBuf*)&d_slot_s, (DevBuf*)&d_arr_s}) HIPCHK(ctx, x->ensure((size_t)m * 4 + 16));
+    HIPCHK(ctx, d_order.ensure((size_t)B * 4 + 16));
+    HIPCHK(ctx, d_src.ensure(n * 4 + 16));
+    for (DevBuf* x : {(DevBuf*)&n_ivl, (DevBuf*)&n_mod, (DevBuf*)&n_idl}) HIPCHK(ctx, x->ensure(n * 8 + 16));
+    // the arrivals by slot (t order kept inside a slot), then the slots by key (slot order kept among equal keys)
+    int slot_bits = 1;
+    while (slot_bits < 32 && (1ull << slot_bits) < (uint64_t)B) slot_bits++;
+    HIPCHK(ctx, tk::launch_shf_slot(m, B, p->seed, d_slot.as<uint32_t>(), s));
+    if (m && (rc = sort_pairs<uint32_t>(ctx, tk::abund_sort_u32, d_slot.as<uint32_t>(), d_slot_s.as<uint32_t>(), d_arr_s.as<uint32_t>(), (uint32_t)m, slot_bits))) return rc;
+    HIPCHK(ctx, tk::launch_shf_evict(m, B, d_slot_s.as<uint32_t>(), d_arr_s.as<uint32_t>(), d_src.as<uint32_t>(), s));
+    HIPCHK(ctx, tk::launch_shf_key(B, p->seed, d_key.as<uint64_t>(), s));
+    if (B && (rc = sort_pairs<uint64_t>(ctx, tk::abund_sort_u64, d_key.as<uint64_t>(), d_key_s.as<uint64_t>(), d_order.as<uint32_t>(), B, 64))) return rc;
+    HIPCHK(ctx, tk::launch_shf_occupant(B, m, d_order.as<uint32_t>(), d_slot_s.as<uint32_t>(), d_arr_s.as<uint32_t>(), d_src.as<uint32_t>() + m, s));
+    // the gather in that order
+    const tk::MolView M = mol_view(in);
+    HIPCHK(ctx, tk::launch_gather_count(M, d_src.as<uint32_t>(), n, n_ivl.as<uint64_t>(), n_mod.as<uint64_t>(), n_idl.as<uint64_t>(), s));
+    OutBatch b(ctx);
+    if ((rc = b.scan(n_ivl, n_mod, n_idl, n)) || (rc = b.alloc(n, "shuffle: ")) || (rc = b.literals(in))) return rc;
+    HIPCHK(ctx, tk::launch_gather_write(M, d_src.as<uint32_t>(), n, b.o_ivl.as<uint64_t>(), b.o_mod.as<uint64_t>(), b.o_id.as<uint64_t>(), b.tables(), s));
+    // comments: the input's entries in the new order (the order comes to the host once)
+    if (!in->h_comments.empty() && !(p->flags & TKSMSEQ_MOL_NO_COMMENTS)) {
+        std::vector<uint32_t> src(n);
+        if (n) HIPCHK(ctx, hipMemcpyAsync(src.data(), d_src.p, n * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        b->h_comments.reserve(2 * n);
+        CommentCopier cc;
+        for (uint64_t j = 0; j < n; j++) if ((rc = cc.put(ctx, b.get(), in, src[j], "shuffle"))) return rc;
     }
     return b.finish(out);
 }

@@ -379,6 +379,24 @@ class Sequencer:
         self._chk(self._lib.tksmseq_flip(self._ctx, batch._h, C.byref(q), C.byref(h)))
         return Batch(self, h)
 
+    # ---- unsegment and shuffle: glue and reorder molecules (device to device)
+    def glue(self, batch, p, seed=42, first_molecule_index=0, comments=True):
+        """The loop of Unsegment_module::run (src/unsegment.cpp:88-105) on the device: every unrolled molecule but the first is glued behind
+        its predecessor with probability p; a chain becomes one molecule with the head's id and the joiners' ids under the comment key Cat.
+        Unlike the reference the last chain is written, and the copies of a depth > 1 record draw one by one (tksmseq_glue)."""
+        q = L.GlueParams(seed, first_molecule_index, float(p), 0 if comments else L.MOL_NO_COMMENTS, 0)
+        h = C.c_void_p()
+        self._chk(self._lib.tksmseq_glue(self._ctx, batch._h, C.byref(q), C.byref(h)))
+        return Batch(self, h)
+
+    def shuffle(self, batch, seed=42, buffer_size=0, comments=True):
+        """Shuffle_module::shuffle_stream (src/shuffle.cpp:23-44) on the device: the unrolled molecules in a uniformly random order
+        (buffer_size 0), or in the order the reference's buffer of buffer_size molecules would give -- which does not bound memory here."""
+        q = L.ShuffleParams(seed, buffer_size, 0 if comments else L.MOL_NO_COMMENTS, 0)
+        h = C.c_void_p()
+        self._chk(self._lib.tksmseq_shuffle(self._ctx, batch._h, C.byref(q), C.byref(h)))
+        return Batch(self, h)
+
     # ---- filter and merge: split and join batches (device to device)
     def filter(self, batch, conditions, negate=False, want_false=True, comments=True):
         """The loop of Filter_module::run (src/filter.cpp:196-212) on the device: conditions as `tksm filter -c` takes them ("info CB",
