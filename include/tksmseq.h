@@ -533,6 +533,52 @@ int tksmseq_shuffle(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_shu
 int tksmseq_unsegment_main(int argc, char** argv);
 int tksmseq_shuffle_main(int argc, char** argv);
 
+/* ---- mutate: SNVs, insertions and deletions of a variant table applied on the device -------------------------------------------------------
+ * The reference's own mutate (src/mutate.cpp) is unfinished -- an insertion loses its anchor, nothing knows about strands, a deletion that
+ * shares an end with a segment deletes it whole, segments on contigs without variants are dropped (DESIGN.md section 7 lists the defects) --
+ * so only its TABLE FORMAT is taken (-t/--tsv, :157-181, Mod::Mod :99-108) and the transform is defined here.  It is pinned by this: a perfect
+ * read of a mutated molecule equals the same slice of the mutated contig.
+ *
+ * tksmseq_variants_load reads a table from `path`, or (path NULL) from text[0, len); ctx may be NULL (the message of a failure is then
+ * tksmseq_last_error(NULL)'s); no device is touched.  One variant per line, three whitespace-separated fields CONTIG POS MOD, lines without
+ * a field skipped, POS 0-based on the plus strand.  MOD all digits: a deletion of [min(POS, MOD), max(POS, MOD)) (empty: counted, no effect);
+ * one byte that is no digit: an SNV, the base at POS becomes that byte (a plus-strand letter, like an MDF substitution); anything else an
+ * insertion `X SEQ`: X is '.' or the letter that replaces the anchor base at POS, SEQ goes in BEHIND the anchor as plus-strand text.
+ * TKSMSEQ_EINVAL, naming file and line: fewer than three fields, a POS or deletion end that is no integer in [0, 2^31 - 1], a lone '.';
+ * TKSMSEQ_ELIMIT: an insertion of more than 2^20 letters, a table of 2^31 rows or more; TKSMSEQ_EIO: an unreadable file.
+ * Normal form, per contig name: the union of the deletions as disjoint ascending ranges (ranges that touch are one); the point variants
+ * (SNVs, insertions) by (POS, line), those inside a deleted range dropped.  tksmseq_variants_info: rows = snvs + insertions + deletions as
+ * read, deleted_ranges and dropped_points of the normal form.  A table is immutable and may be used from several contexts and threads.
+ *
+ * tksmseq_mutate: every molecule of `in`, depth-unrolled (ids get _k, comments kept unless TKSMSEQ_MOL_NO_COMMENTS), segment by segment.  A
+ * contig segment matches a table contig by name, a literal segment by its text; a segment that matches none, or with end <= start, is copied.
+ * For a segment [s, e) on a table contig: its events are the deleted ranges [f, t) with t > s && f < e and the insertions with s <= POS < e; its
+ * table substitutions the SNVs and the insertions with a letter X, s <= POS < e, in table order.  Without events the segment is copied with
+ * all its own substitutions, the table's follow at POS - s.  With events, in ascending position from cur = s: a range emits the piece
+ * [cur, f) if f > cur, then cur = min(t, e); an insertion at p emits [cur, p + 1) unless it is empty (a second insertion at one anchor), then
+ * the literal {SEQ, 0, |SEQ|} on the segment's strand, then cur = p + 1; at the end [cur, e) if not empty.  A piece [a, b) carries the segment's
+ * own substitutions with a - s <= position < b - s, in their order, re-based by a - s (the others are dropped, as einterval::truncate drops
+ * them), then ALL table substitutions with a <= POS < b in table order at POS - a.  A minus-strand segment gives the same pieces and literals
+ * in reverse order, all on the minus strand, the literal's text as the table has it (the splice reverse-complements it).  A molecule all of
+ * whose segments are deleted stays, without segments.  The output's literal table is the input's followed by one entry per kept insertion.
+ * No random numbers: the result does not depend on batching or devices.  The device form of the table is kept by the context and rebuilt
+ * when another table is used or the context's reference has changed.  Known limit: a literal whose text equals a contig name becomes that
+ * contig once it is written as text and parsed again.  TKSMSEQ_ELIMIT ("mutate: ..."): a result beyond the table limits of a batch. */
+typedef struct tksmseq_variants tksmseq_variants;
+int tksmseq_variants_load(tksmseq_ctx* ctx, const char* path, const char* text, uint64_t len, tksmseq_variants** out);
+int tksmseq_variants_info(const tksmseq_variants* v, uint64_t* rows, uint64_t* snvs, uint64_t* insertions, uint64_t* deletions, uint64_t* deleted_ranges,
+                          uint64_t* dropped_points);
+void tksmseq_variants_free(tksmseq_variants* v);
+typedef struct {
+    int32_t flags;                   /* TKSMSEQ_MOL_NO_COMMENTS or 0 */
+    int32_t reserved;
+} tksmseq_mutate_params;
+int tksmseq_mutate(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_variants* v, const tksmseq_mutate_params* params, tksmseq_batch** out);
+/* `tksm mutate`: -i, -o, -t/--tsv; "input is required!" / "output is required!" / "tsv is required!" per missing one, the help, exit 1
+ * (src/mutate.cpp:217-233).  The table is read and checked before any context is made: a bad table is exit 1 with the line named.  Streamed
+ * in batches of --batch-bytes over --devices; the output depends on neither. */
+int tksmseq_mutate_main(int argc, char** argv);
+
 /* ---- tail-noise: random and hairpin noise appended on the device ----------------------------------------------------------------------
  * tksmseq_append_noise replaces NoiseAdder::operator() (src/append_noise.cpp:83-128; module AppendNoise_module :131-229) -- not to be
  * confused with the Badread tail-noise MODEL of tksmseq_load_tail_model.  Molecule i (depth-unrolled, like every segment edit; the

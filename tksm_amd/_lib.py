@@ -102,6 +102,10 @@ class ShuffleParams(C.Structure):            # tksmseq_shuffle_params
     _fields_ = [("seed", C.c_uint64), ("buffer_size", C.c_uint64), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MutateParams(C.Structure):             # tksmseq_mutate_params
+    _fields_ = [("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class WgsParams(C.Structure):                # tksmseq_wgs_params
     _fields_ = [("seed", C.c_uint64), ("dist", C.c_int32), ("reserved", C.c_int32), ("a", C.c_double), ("b", C.c_double),
                 ("base_count", C.c_int64), ("first_candidate", C.c_uint64), ("n_candidates", C.c_uint64),
@@ -174,6 +178,7 @@ SYMBOLS = [
     "tksmseq_abundance_free", "tksmseq_abundance_main",
     "tksmseq_filter", "tksmseq_concat", "tksmseq_filter_main",
     "tksmseq_glue", "tksmseq_glue_joins", "tksmseq_shuffle", "tksmseq_unsegment_main", "tksmseq_shuffle_main",
+    "tksmseq_variants_load", "tksmseq_variants_info", "tksmseq_variants_free", "tksmseq_mutate", "tksmseq_mutate_main",
 ]
 
 _lib = None
@@ -291,6 +296,11 @@ def load():
         "tksmseq_shuffle": (C.c_int, [vp, vp, P(ShuffleParams), P(vp)]),
         "tksmseq_unsegment_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
         "tksmseq_shuffle_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
+        "tksmseq_variants_load": (C.c_int, [vp, C.c_char_p, C.c_char_p, u64, P(vp)]),
+        "tksmseq_variants_info": (C.c_int, [vp, P(u64), P(u64), P(u64), P(u64), P(u64), P(u64)]),
+        "tksmseq_variants_free": (None, [vp]),
+        "tksmseq_mutate": (C.c_int, [vp, vp, vp, P(MutateParams), P(vp)]),
+        "tksmseq_mutate_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

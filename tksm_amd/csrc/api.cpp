@@ -15,6 +15,7 @@
 #include "loop_filter.h"
 
 static thread_local std::string g_create_error;
+void set_contextless_error(const std::string& e) { g_create_error = e; }
 
 
 template <class T>

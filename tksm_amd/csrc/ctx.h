@@ -252,6 +252,10 @@ struct tksmseq_ctx : ContigLookup {
     DevBuf d_tsb_first, d_tsb_exons, d_tsb_lits, d_tsb_litpool;
     uint64_t tsb_n_lits = 0, tsb_lit_bytes = 0;
     float tsb_plan_ms = 0.f, tsb_write_ms = 0.f;          // device time of the last plan / tksmseq_transcribe by HIP events (tksmseq_set_timing)
+    // mutate: the device form of the variant table used last (tk::MutView), the context's contigs resolved against the table's names;
+    // rebuilt when another table comes or the reference has changed
+    uint64_t mut_serial = 0, mut_ref_version = ~0ull;         // (serial 0: no device form yet)
+    DevBuf d_mut_refctg, d_mut_nameoff, d_mut_names, d_mut_delfirst, d_mut_ptfirst, d_mut_delfrom, d_mut_delto, d_mut_ptpos, d_mut_ptinfo, d_mut_insent, d_mut_inspool;
 
     // models
     ErrorModelHost em; QScoreModelHost qm; IdentityHost idm;
@@ -318,6 +322,9 @@ int sort_pairs(tksmseq_ctx* ctx, Sort sort, const K* keys, K* keys_sorted, uint3
 
 // a batch whose tables were written on the device (PCR, truncation): lengths, sorted order and sizing on the host
 int finalize_device_batch(tksmseq_ctx* ctx, tksmseq_batch* b);
+
+// the message tksmseq_last_error(NULL) gives on the calling thread (api.cpp): for calls that fail without a context
+void set_contextless_error(const std::string& e);
 
 // TKSMSEQ_VERBOSE: 0 when unset, otherwise at least 1
 inline int verbose_level() { const char* v = getenv("TKSMSEQ_VERBOSE"); return v ? std::max(1, atoi(v)) : 0; }

@@ -144,6 +144,27 @@ hipError_t launch_gather_count(const MolView& m, const uint32_t* src, uint64_t n
 hipError_t launch_gather_write(const MolView& m, const uint32_t* src, uint64_t n, const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off,
                                const MolOut& o, hipStream_t s);
 
+// mutate (a variant table applied to every segment; the transform is this build's own, DESIGN.md "mutate"): see mdf_kernels.hip
+constexpr uint32_t MUT_NONE = 0xffffffffu;
+constexpr uint64_t MUT_PT_LETTER = 1ull << 40, MUT_PT_INSERTION = 1ull << 41;     // pt_info (mut_host.h): ordinal | letter << 32 | flags
+struct MutView {                          // the device form of a variant table in its normal form, for one context
+    uint32_t n_contigs, n_ref, n_ins;     // contigs of the table; contigs of the context's reference; kept insertions
+    const uint32_t* ref_ctg;              // [n_ref] the table's contig of a context contig, MUT_NONE: not in the table
+    const uint32_t* name_off;             // [n_contigs + 1] the table's contig names in `names`, sorted by (length, bytes)
+    const uint8_t* names;
+    const uint32_t *del_first, *pt_first; // [n_contigs + 1]
+    const uint32_t *del_from, *del_to;    // disjoint deleted ranges, ascending per contig
+    const uint32_t* pt_pos;               // SNVs and insertions, ascending per contig, equal positions in table order
+    const uint64_t* pt_info;
+    const uint64_t* ins_ent;              // [n_ins][2] {offset in the table's insertion pool, letters}
+};
+// one lane per literal entry of the input: lit_ctg[l] = the table's contig whose name is the literal's text, MUT_NONE: none; and one lane per
+// kept insertion k: entry lit_base + k of the OUTPUT literal table = {pool_base + its offset, its letters}
+hipError_t launch_mut_resolve(const BatchView& b, const MutView& v, uint32_t* lit_ctg, uint64_t* out_lits, uint32_t lit_base, uint64_t pool_base, hipStream_t s);
+hipError_t launch_mut_count(const MolView& m, const MutView& v, const uint32_t* lit_ctg, uint64_t* n_ivls, uint64_t* n_mods, uint64_t* n_idlen, hipStream_t s);
+hipError_t launch_mut_write(const MolView& m, const MutView& v, const uint32_t* lit_ctg, uint32_t lit_base, const uint64_t* ivl_off, const uint64_t* mod_off,
+                            const uint64_t* id_off, const MolOut& o, hipStream_t s);
+
 // random-wgs (src/random_wgs.cpp:181-207): fragments of the whole genome, one lane per candidate; see mdf_kernels.hip
 constexpr int WGS_LDS_CONTIGS = 2048;       // running sums of that many contigs are searched in LDS (16 KB), more in global memory
 enum { WGS_NORMAL = 0, WGS_UNIFORM = 1, WGS_LOGNORMAL = 2, WGS_EXPONENTIAL = 3 };

@@ -16,6 +16,7 @@
 //   Splicer_module::run          src/transcribe.cpp:170-197 an abundance row becomes `depth` copies of its transcript's exons, no input batch
 //   Unsegment_module::run        src/unsegment.cpp:88-105  a molecule is glued behind its predecessor with a probability (concat, src/interval.h:893-896)
 //   Shuffle_module::shuffle_stream  src/shuffle.cpp:23-44  the molecules in a random order, whole or through a buffer of B slots
+//   Mutate_module (table format) src/mutate.cpp:99-108, :157-181 SNVs, insertions, deletions; the transform itself is defined in DESIGN.md ("mutate")
 // Integer / byte work, one LANE per molecule (tail-noise alone spreads its per-base work: one wave per molecule, or a flat grid): the tables of a molecule are a few dozen bytes, the work per molecule is a short
 // serial walk (tree of copies; list of segments).  The reference draws from a sequential Mersenne Twister; here every
 // decision has its own Philox counter (template molecule, path of copy cycles, purpose), so the result does not depend on
@@ -1149,6 +1150,155 @@ __global__ void k_gather_write(MolView M, const uint32_t* __restrict__ src, uint
 }
 
 // ------------------------------------------------------------------------------------------------
+// mutate: a variant table -- SNVs, insertions, deletions -- applied to every segment ("mutate"; the reference's src/mutate.cpp is
+// unfinished, so the transform is specified there and in include/tksmseq.h).  The table comes in its normal form (mut_host.h): per contig
+// the disjoint deleted ranges [del_from, del_to) ascending, and the point variants (SNVs and insertions outside every deleted range) by
+// (position, table line).  k_mut_resolve: one lane per literal entry of the input finds the table contig whose NAME is the literal's text (a
+// batch parsed without a reference knows its contigs as literals), by binary search over the names sorted by (length, bytes).
+// k_mut_count / k_mut_write: one lane per molecule walks its segments.  A segment [s, e) on a table contig finds its deleted ranges (the first
+// with del_to > s, up to the first with del_from >= e) and its points (lower bounds of s and e) by binary search -- a table of millions of
+// rows is a few tens of MB that stay in L2 -- and then, if there is a range or an insertion among them, merges the two lists by position:
+// a range ends the running piece in front of it and moves on behind it, an insertion ends the piece behind its anchor and puts the
+// insertion's literal (entry lit_base + ordinal of the output's literal table, shared by all molecules) after it.  A piece [a, b) carries the
+// segment's own substitutions that fall into it, re-based, then ALL of the table's letters with a <= POS < b in table order.  Without an
+// event the segment is copied whole, its own substitutions untouched, the table's letters behind them.  A minus-strand segment comes out
+// back to front: the write pass sizes the segment first (the same walk, counting), then fills intervals and substitutions from the end.
+// ------------------------------------------------------------------------------------------------
+DEV uint32_t mut_lower(const uint32_t* a, uint32_t lo, uint32_t hi, uint32_t key) {      // first index in [lo, hi) with a[index] >= key
+    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (a[mid] < key) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+
+__global__ void k_mut_resolve(BatchView B, MutView V, uint32_t* __restrict__ lit_ctg, uint64_t* __restrict__ out_lits, uint32_t lit_base, uint64_t pool_base) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < B.n_literals) {
+        const uint64_t len = B.literals[2 * i + 1];
+        const uint8_t* t = B.litpool + B.literals[2 * i];
+        uint32_t lo = 0, hi = V.n_contigs, found = MUT_NONE;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            const uint32_t no = V.name_off[mid], nl = V.name_off[mid + 1] - no;
+            int c = (uint64_t)nl < len ? -1 : ((uint64_t)nl > len ? 1 : 0);
+            for (uint32_t k = 0; c == 0 && k < nl; k++) c = (int)V.names[no + k] - (int)t[k];
+            if (c == 0) { found = mid; break; }
+            if (c < 0) lo = mid + 1; else hi = mid;
+        }
+        lit_ctg[i] = found;
+    }
+    if (i < V.n_ins) { out_lits[2ull * (lit_base + i)] = pool_base + V.ins_ent[2 * i]; out_lits[2ull * (lit_base + i) + 1] = V.ins_ent[2 * i + 1]; }
+}
+
+// One segment `iv` of the input.  WRITE false: io / mo are advanced by the intervals / substitutions the segment becomes.  WRITE true: they
+// are written from io / mo on as well.
+template <bool WRITE>
+DEV void mut_segment(const BatchView& B, const MutView& V, const uint32_t* __restrict__ lit_ctg, const uint32_t* iv, uint32_t lit_base, uint64_t& io, uint64_t& mo,
+                     const MolOut& O) {
+    const uint32_t s = iv[1], e = iv[2], mb = iv[3] & 0x7fffffffu, me = iv[7] & 0x7fffffffu, strand = iv[3] & 0x80000000u;
+    const uint32_t tc = (iv[0] >> 31) ? lit_ctg[iv[0] & 0x7fffffffu] : (iv[0] < V.n_ref ? V.ref_ctg[iv[0]] : MUT_NONE);
+    uint32_t d0 = 0, d1 = 0, p0 = 0, p1 = 0;
+    bool events = false;
+    if (tc != MUT_NONE && e > s) {
+        const uint32_t db = V.del_first[tc], de = V.del_first[tc + 1], pb = V.pt_first[tc], pe = V.pt_first[tc + 1];
+        d0 = mut_lower(V.del_to, db, de, s + 1u);                     // the first range with del_to > s
+        d1 = mut_lower(V.del_from, d0, de, e);                        // ... up to the first with del_from >= e
+        p0 = mut_lower(V.pt_pos, pb, pe, s);
+        p1 = mut_lower(V.pt_pos, p0, pe, e);
+        events = d0 < d1;
+        for (uint32_t q = p0; q < p1 && !events; q++) events = (V.pt_info[q] & MUT_PT_INSERTION) != 0ull;
+    }
+    if (!events) {
+        if (WRITE) {
+            uint32_t* ov = O.intervals + 4ull * io;
+            ov[0] = iv[0]; ov[1] = s; ov[2] = e; ov[3] = (uint32_t)mo | strand;
+            for (uint32_t m = mb; m < me; m++) { O.mods[2 * (mo + (m - mb))] = B.mods[2ull * m]; O.mods[2 * (mo + (m - mb)) + 1] = B.mods[2ull * m + 1]; }
+        }
+        io++; mo += me - mb;
+        for (uint32_t q = p0; q < p1; q++) {                           // SNVs only: appended, as add_error appends
+            const uint64_t info = V.pt_info[q];
+            if (!(info & MUT_PT_LETTER)) continue;
+            if (WRITE) { O.mods[2 * mo] = V.pt_pos[q] - s; O.mods[2 * mo + 1] = (uint32_t)(info >> 32) & 0xffu; }
+            mo++;
+        }
+        return;
+    }
+    const bool back = WRITE && strand != 0u;                          // minus strand: filled from the end
+    uint64_t hi_i = 0, hi_m = 0, seg_i = 0, seg_m = 0;
+    if (back) { mut_segment<false>(B, V, lit_ctg, iv, lit_base, seg_i, seg_m, O); hi_i = io + seg_i; hi_m = mo + seg_m; }
+    uint32_t cur = s, d = d0, q = p0, qs = p0;
+    auto piece = [&](uint32_t a, uint32_t b) {
+        const uint32_t fa = a - s, fb = b - s;
+        uint32_t nm = 0;
+        for (uint32_t m = mb; m < me; m++) { const uint32_t p = B.mods[2ull * m]; nm += (p >= fa && p < fb) ? 1u : 0u; }
+        while (qs < p1 && V.pt_pos[qs] < a) qs++;
+        uint32_t qe = qs;
+        for (; qe < p1 && V.pt_pos[qe] < b; qe++) nm += (V.pt_info[qe] & MUT_PT_LETTER) ? 1u : 0u;
+        if (WRITE) {
+            if (back) hi_m -= nm;
+            uint64_t at = back ? hi_m : mo;
+            uint32_t* ov = O.intervals + 4ull * (back ? --hi_i : io);
+            ov[0] = iv[0]; ov[1] = a; ov[2] = b; ov[3] = (uint32_t)at | strand;
+            for (uint32_t m = mb; m < me; m++) {
+                const uint32_t p = B.mods[2ull * m];
+                if (p >= fa && p < fb) { O.mods[2 * at] = p - fa; O.mods[2 * at + 1] = B.mods[2ull * m + 1]; at++; }
+            }
+            for (uint32_t x = qs; x < qe; x++) {
+                const uint64_t info = V.pt_info[x];
+                if (info & MUT_PT_LETTER) { O.mods[2 * at] = V.pt_pos[x] - a; O.mods[2 * at + 1] = (uint32_t)(info >> 32) & 0xffu; at++; }
+            }
+        }
+        if (!back) { io++; mo += nm; }
+        qs = qe;
+    };
+    for (;;) {
+        while (q < p1 && !(V.pt_info[q] & MUT_PT_INSERTION)) q++;     // the next insertion
+        const bool hd = d < d1, hq = q < p1;
+        if (!hd && !hq) break;
+        if (hd && (!hq || V.del_from[d] <= V.pt_pos[q])) {            // (a kept point lies in no range)
+            const uint32_t f = V.del_from[d], t = V.del_to[d];
+            if (f > cur) piece(cur, f);
+            cur = t < e ? t : e;
+            d++;
+        } else {
+            const uint32_t p = V.pt_pos[q];
+            if (p + 1u > cur) piece(cur, p + 1u);                     // (empty for a second insertion at the same anchor)
+            if (WRITE) {
+                const uint32_t li = (uint32_t)V.pt_info[q];
+                uint32_t* ov = O.intervals + 4ull * (back ? --hi_i : io);
+                ov[0] = 0x80000000u | (lit_base + li); ov[1] = 0u; ov[2] = (uint32_t)V.ins_ent[2ull * li + 1]; ov[3] = (uint32_t)(back ? hi_m : mo) | strand;
+            }
+            if (!back) io++;
+            cur = p + 1u;
+            q++;
+        }
+    }
+    if (cur < e) piece(cur, e);
+    if (back) { io += seg_i; mo += seg_m; }
+}
+
+__global__ void k_mut_count(MolView M, MutView V, const uint32_t* __restrict__ lit_ctg, uint64_t* __restrict__ n_ivls, uint64_t* __restrict__ n_mods,
+                            uint64_t* __restrict__ n_idlen) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= M.B.n_reads) return;
+    const BatchView& B = M.B;
+    const uint32_t ib = B.reads[2 * r], ic = B.reads[2 * r + 1];
+    uint64_t ni = 0, nm = 0;
+    for (uint32_t i = 0; i < ic; i++) mut_segment<false>(B, V, lit_ctg, B.intervals + 4ull * (ib + i), 0u, ni, nm, MolOut{});
+    n_ivls[r] = ni; n_mods[r] = nm; n_idlen[r] = unrolled_id_len(M, r);
+}
+
+__global__ void k_mut_write(MolView M, MutView V, const uint32_t* __restrict__ lit_ctg, uint32_t lit_base, const uint64_t* __restrict__ ivl_off,
+                            const uint64_t* __restrict__ mod_off, const uint64_t* __restrict__ id_off, MolOut O) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= M.B.n_reads) return;
+    const BatchView& B = M.B;
+    const uint32_t ib = B.reads[2 * r], ic = B.reads[2 * r + 1];
+    uint64_t io = ivl_off[r], mo = mod_off[r];
+    O.reads[2 * r] = (uint32_t)io; O.reads[2 * r + 1] = (uint32_t)(ivl_off[r + 1] - io);
+    copy_id(M, r, r, id_off[r], O);
+    for (uint32_t i = 0; i < ic; i++) mut_segment<true>(B, V, lit_ctg, B.intervals + 4ull * (ib + i), lit_base, io, mo, O);
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
 static inline unsigned nblk(uint64_t n) { return (unsigned)((n + 127) / 128); }
@@ -1274,6 +1424,24 @@ hipError_t launch_gather_write(const MolView& m, const uint32_t* src, uint64_t n
                                const MolOut& o, hipStream_t s) {
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(k_gather_write, dim3(nblk(n)), dim3(128), 0, s, m, src, n, ivl_off, mod_off, id_off, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_mut_resolve(const BatchView& b, const MutView& v, uint32_t* lit_ctg, uint64_t* out_lits, uint32_t lit_base, uint64_t pool_base, hipStream_t s) {
+    const uint64_t n = b.n_literals > v.n_ins ? b.n_literals : v.n_ins;
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_mut_resolve, dim3(nblk(n)), dim3(128), 0, s, b, v, lit_ctg, out_lits, lit_base, pool_base);
+    return hipGetLastError();
+}
+hipError_t launch_mut_count(const MolView& m, const MutView& v, const uint32_t* lit_ctg, uint64_t* n_ivls, uint64_t* n_mods, uint64_t* n_idlen, hipStream_t s) {
+    if (!m.B.n_reads) return hipSuccess;
+    hipLaunchKernelGGL(k_mut_count, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, v, lit_ctg, n_ivls, n_mods, n_idlen);
+    return hipGetLastError();
+}
+hipError_t launch_mut_write(const MolView& m, const MutView& v, const uint32_t* lit_ctg, uint32_t lit_base, const uint64_t* ivl_off, const uint64_t* mod_off,
+                            const uint64_t* id_off, const MolOut& o, hipStream_t s) {
+    if (!m.B.n_reads) return hipSuccess;
+    hipLaunchKernelGGL(k_mut_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, v, lit_ctg, lit_base, ivl_off, mod_off, id_off, o);
     return hipGetLastError();
 }
 

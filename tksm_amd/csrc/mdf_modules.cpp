@@ -16,6 +16,7 @@
 //   Filter_module           src/filter.cpp:119-231   -i, -t/--true-output, -f/--false-output, -c/--condition (comma-separated, repeatable), --negate
 //   Unsegment_module        src/unsegment.cpp:22-116 -i, -o, -p/--probability ("<name> is required!", the help, exit 1)
 //   Shuffle_module          src/shuffle.cpp:22-125   -i, -o, --buffer-size (long only); the whole input is one batch
+//   Mutate_module           src/mutate.cpp:182-233   -i, -o, -t/--tsv ("<name> is required!", the help, exit 1); the table is checked before any context
 //   Splicer_module          src/transcribe.cpp:19-218 -g/--gtf, -a/--abundance, --molecule-count, -w/--weights, ... (no fusion submodule): GTF + TSV in, MDF out
 //   model-truncation        py/truncate_kde.py:36-112, :323-352 (behind src/model_truncation.cpp) PAF in, KDE model JSON out: no MDF, one context
 //   abundance               py/transcript_abundance.py:32-139, :326-389 (behind src/abundance.cpp) PAF in, expression TSV out: no MDF, one context
@@ -900,6 +901,44 @@ extern "C" int tksmseq_unsegment_main(int argc, char** argv) {
         q.first_molecule_index = pc.first;
         return tksmseq_glue(ctx, in, &q, out);
     }, nullptr, [p](uint64_t g) { return tksmseq_glue_joins(p.seed, p.probability, g) != 0; });
+}
+
+// `tksm mutate` (Mutate_module, src/mutate.cpp:141-250: -i, -o, -t/--tsv; "<name> is required!" per missing one, the help, exit 1).  The table is
+// read and checked here, before any context exists: a bad table ends the run with its line named and without a device.
+extern "C" int tksmseq_mutate_main(int argc, char** argv) {
+    Common c;
+    std::string tsv;
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            if (o == "--slice-molecules") return NO_SUCH;            // (a common flag this module does not have; -s/--seed is taken and draws nothing)
+            if ((o != "-t" && o != "--tsv") || !v) return NOT_MINE;
+            tsv = v;
+            return TOOK_VALUE;
+        })) return 1;
+    static const char* help =
+        "Mutate module: apply the SNVs, insertions and deletions of a table to every molecule\nusage: mutate -i INPUT -o OUTPUT -t TSV\n"
+        "              [--devices D[,D...]] [--batch-bytes B] [--verbosity L] [--log-file F]\n"
+        "TSV: one variant per line, 'chr pos modification' (pos 0-based, plus strand): all digits = deletion of [pos, modification),\n"
+        "one letter = SNV, '.SEQ' or 'XSEQ' = SEQ inserted behind pos (X replaces the base at pos).\n";
+    if (c.help) { printf("%s", help); return 0; }
+    int missing = 0;
+    if (c.input.empty()) { fprintf(stderr, "input is required!\n"); missing++; }
+    if (c.output.empty()) { fprintf(stderr, "output is required!\n"); missing++; }
+    if (tsv.empty()) { fprintf(stderr, "tsv is required!\n"); missing++; }
+    if (missing) { fprintf(stderr, "%s\n", help); return 1; }
+    Logger log;
+    if (!open_log(c, "mutate", log)) return 1;
+    tksmseq_variants* table = nullptr;
+    if (tksmseq_variants_load(nullptr, tsv.c_str(), nullptr, 0, &table)) { fprintf(stderr, "Error: %s\n", tksmseq_last_error(nullptr)); return 1; }
+    uint64_t rows = 0, snvs = 0, ins = 0, dels = 0, ranges = 0, dropped = 0;
+    tksmseq_variants_info(table, &rows, &snvs, &ins, &dels, &ranges, &dropped);
+    log.log(Logger::INFO, "%s: %llu variants (%llu SNVs, %llu insertions, %llu deletions in %llu ranges; %llu SNVs / insertions inside a deletion dropped)", tsv.c_str(),
+            (unsigned long long)rows, (unsigned long long)snvs, (unsigned long long)ins, (unsigned long long)dels, (unsigned long long)ranges, (unsigned long long)dropped);
+    const tksmseq_mutate_params p{};
+    const int rc = stream_batches(c, log, "mutate", [&](tksmseq_ctx* ctx, const tksmseq_batch* in, Piece&, tksmseq_batch** out) -> int {
+        return tksmseq_mutate(ctx, in, table, &p, out);
+    });
+    tksmseq_variants_free(table);
+    return rc;
 }
 
 // `tksm shuffle` (Shuffle_module, src/shuffle.cpp:22-125): the whole input is one batch on the first entry of --devices, as the reference

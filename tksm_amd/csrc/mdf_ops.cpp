@@ -7,6 +7,7 @@
 //   tksmseq_wgs            src/random_wgs.cpp:181-207 (no input: the molecules are made on the device)
 //   tksmseq_append_noise   src/append_noise.cpp:83-128 (tail-noise: a random literal or a hairpin behind every molecule)
 //   tksmseq_transcribe     src/transcribe.cpp:170-197 (no input batch: abundance rows x the context's transcript table)
+//   tksmseq_mutate         a variant table applied to every segment (the table format of src/mutate.cpp:157-181; the transform is this build's own)
 //   tksmseq_batch_to_mdf_text   molecule_descriptor::operator<<, src/interval.h:898-905 (+ dump_comment :880-890)
 // The molecule tables stay on the device from one transform to the next and into tksmseq_run; only sizes, per-read lengths
 // (which the host needs to size and order a Seq batch) and, for the text writer, the tables themselves come back.
@@ -22,6 +23,7 @@
 #include <thread>
 #include "filter_host.h"
 #include "mdf_kernels.h"
+#include "mut_host.h"
 
 namespace {
 
@@ -1457,6 +1459,106 @@ int tksmseq_transcribe_text(const tksmseq_tsb_plan* plan, uint64_t first_record,
     memcpy(buf, o.data(), o.size()); buf[o.size()] = 0;
     *text = buf; *len = o.size();
     return TKSMSEQ_OK;
+}
+
+// ---- mutate ----------------------------------------------------------------------------------------------------------------------
+// A variant table in its normal form (mut_host.h), on the host; immutable once loaded, so any number of contexts may use it.
+struct tksmseq_variants { mut::Variants v; };
+
+// the table as k_mut_count / k_mut_write read it, the context's contigs resolved against the table's names
+static int mut_table(tksmseq_ctx* ctx, const mut::Variants& T, tk::MutView& V) {
+    hipStream_t s = ctx->stream;
+    if (ctx->mut_serial != T.serial || ctx->mut_ref_version != ctx->ref_version) {
+        std::vector<uint32_t> ref_ctg(ctx->contig_names.size()), name_off{0};
+        for (size_t i = 0; i < ref_ctg.size(); i++) { const int k = T.find(ctx->contig_names[i].data(), ctx->contig_names[i].size()); ref_ctg[i] = k >= 0 ? (uint32_t)k : tk::MUT_NONE; }
+        std::string names;
+        for (auto& n : T.names) {
+            if (names.size() + n.size() >= 0xffffffffull) { ctx->err = "mutate: more than 4 GB of contig names in the variant table"; return TKSMSEQ_ELIMIT; }
+            names += n; name_off.push_back((uint32_t)names.size());
+        }
+        HIPCHK(ctx, hipStreamSynchronize(s));                           // (nothing queued may still read the table that goes)
+        ctx->mut_serial = 0;
+        auto up = [&](DevBuf& d, const void* p, size_t bytes) {
+            hipError_t e = d.ensure(bytes + 16);
+            if (e == hipSuccess && bytes) e = hipMemcpyAsync(d.p, p, bytes, hipMemcpyHostToDevice, s);
+            return e;
+        };
+        HIPCHK(ctx, up(ctx->d_mut_refctg, ref_ctg.data(), ref_ctg.size() * 4));
+        HIPCHK(ctx, up(ctx->d_mut_nameoff, name_off.data(), name_off.size() * 4));
+        HIPCHK(ctx, up(ctx->d_mut_names, names.data(), names.size()));
+        HIPCHK(ctx, up(ctx->d_mut_delfirst, T.del_first.data(), T.del_first.size() * 4));
+        HIPCHK(ctx, up(ctx->d_mut_ptfirst, T.pt_first.data(), T.pt_first.size() * 4));
+        HIPCHK(ctx, up(ctx->d_mut_delfrom, T.del_from.data(), T.del_from.size() * 4));
+        HIPCHK(ctx, up(ctx->d_mut_delto, T.del_to.data(), T.del_to.size() * 4));
+        HIPCHK(ctx, up(ctx->d_mut_ptpos, T.pt_pos.data(), T.pt_pos.size() * 4));
+        HIPCHK(ctx, up(ctx->d_mut_ptinfo, T.pt_info.data(), T.pt_info.size() * 8));
+        HIPCHK(ctx, up(ctx->d_mut_insent, T.ins_ent.data(), T.ins_ent.size() * 8));
+        HIPCHK(ctx, up(ctx->d_mut_inspool, T.ins_pool.data(), T.ins_pool.size()));
+        HIPCHK(ctx, hipStreamSynchronize(s));                           // (the host vectors above go)
+        ctx->mut_serial = T.serial; ctx->mut_ref_version = ctx->ref_version;
+    }
+    V = tk::MutView{(uint32_t)T.names.size(), (uint32_t)ctx->contig_names.size(), (uint32_t)T.n_insertions_kept(), ctx->d_mut_refctg.as<uint32_t>(),
+                    ctx->d_mut_nameoff.as<uint32_t>(), ctx->d_mut_names.as<uint8_t>(), ctx->d_mut_delfirst.as<uint32_t>(), ctx->d_mut_ptfirst.as<uint32_t>(),
+                    ctx->d_mut_delfrom.as<uint32_t>(), ctx->d_mut_delto.as<uint32_t>(), ctx->d_mut_ptpos.as<uint32_t>(), ctx->d_mut_ptinfo.as<uint64_t>(),
+                    ctx->d_mut_insent.as<uint64_t>()};
+    return TKSMSEQ_OK;
+}
+
+int tksmseq_variants_load(tksmseq_ctx* ctx, const char* path, const char* text, uint64_t len, tksmseq_variants** out) {
+    if (!out || (!path && !text && len)) return TKSMSEQ_EINVAL;
+    *out = nullptr;
+    static std::atomic<uint64_t> serial{0};
+    std::unique_ptr<tksmseq_variants> v(new tksmseq_variants());
+    std::string err;
+    bool limit = false, io = false;
+    const bool ok = path ? mut::read_variants(path, v->v, err, limit, io) : mut::parse_variants(text, len, "<text>", v->v, err, limit);
+    if (!ok) {
+        if (ctx) ctx->err = err; else set_contextless_error(err);
+        return io ? TKSMSEQ_EIO : limit ? TKSMSEQ_ELIMIT : TKSMSEQ_EINVAL;
+    }
+    v->v.serial = ++serial;
+    *out = v.release();
+    return TKSMSEQ_OK;
+}
+
+int tksmseq_variants_info(const tksmseq_variants* v, uint64_t* rows, uint64_t* snvs, uint64_t* insertions, uint64_t* deletions, uint64_t* deleted_ranges,
+                          uint64_t* dropped_points) {
+    if (!v) return TKSMSEQ_EINVAL;
+    if (rows) *rows = v->v.rows;
+    if (snvs) *snvs = v->v.snvs;
+    if (insertions) *insertions = v->v.insertions;
+    if (deletions) *deletions = v->v.deletions;
+    if (deleted_ranges) *deleted_ranges = v->v.deleted_ranges;
+    if (dropped_points) *dropped_points = v->v.dropped_points;
+    return TKSMSEQ_OK;
+}
+
+void tksmseq_variants_free(tksmseq_variants* v) { delete v; }
+
+int tksmseq_mutate(tksmseq_ctx* ctx, const tksmseq_batch* in, const tksmseq_variants* v, const tksmseq_mutate_params* p, tksmseq_batch** out) {
+    if (!ctx || !in || !v || !p || !out) return TKSMSEQ_EINVAL;
+    *out = nullptr;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const mut::Variants& T = v->v;
+    tk::MutView V{};
+    int rc = mut_table(ctx, T, V);
+    if (rc) return rc;
+    const uint64_t n = in->n_reads;
+    // the output's literals: the input's, then one entry per kept insertion of the table, shared by all molecules
+    OutBatch b(ctx);
+    if ((rc = b.literals(in, T.n_insertions_kept(), T.ins_pool.size()))) return rc;
+    if (!T.ins_pool.empty()) HIPCHK(ctx, hipMemcpyAsync(b->litpool.as<uint8_t>() + b.pool_base, ctx->d_mut_inspool.p, T.ins_pool.size(), hipMemcpyDeviceToDevice, s));
+    TmpBuf lit_ctg(s), n_ivl(s), n_mod(s), n_idl(s);
+    HIPCHK(ctx, lit_ctg.ensure(in->n_literals * 4 + 16));
+    const tk::MolView M = mol_view(in);
+    HIPCHK(ctx, tk::launch_mut_resolve(M.B, V, lit_ctg.as<uint32_t>(), b->literals.as<uint64_t>(), b.lit_base, b.pool_base, s));
+    for (DevBuf* x : {&n_ivl, &n_mod, &n_idl}) HIPCHK(ctx, x->ensure(n * 8 + 16));
+    HIPCHK(ctx, tk::launch_mut_count(M, V, lit_ctg.as<uint32_t>(), n_ivl.as<uint64_t>(), n_mod.as<uint64_t>(), n_idl.as<uint64_t>(), s));
+    if ((rc = b.scan(n_ivl, n_mod, n_idl, n)) || (rc = b.alloc(n, "mutate: "))) return rc;
+    HIPCHK(ctx, tk::launch_mut_write(M, V, lit_ctg.as<uint32_t>(), b.lit_base, b.o_ivl.as<uint64_t>(), b.o_mod.as<uint64_t>(), b.o_id.as<uint64_t>(), b.tables(), s));
+    edit_comments(in, b, p->flags);
+    return b.finish(out);
 }
 
 int tksmseq_batch_to_mdf_text(tksmseq_ctx* ctx, const tksmseq_batch* b, char** text, uint64_t* len) {

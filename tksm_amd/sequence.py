@@ -134,6 +134,29 @@ class TranscribePlan:
             pass
 
 
+class Variants:
+    """A variant table in its normal form (tksmseq_variants_load): .rows lines read, of which .snvs, .insertions and .deletions; the
+    deletions' union is .deleted_ranges disjoint ranges, and .dropped_points SNVs / insertions lie inside one.  Host only; may be used
+    with any Sequencer."""
+
+    def __init__(self, lib, handle):
+        self._lib, self._h = lib, handle
+        v = [C.c_uint64() for _ in range(6)]
+        lib.tksmseq_variants_info(handle, *[C.byref(x) for x in v])
+        self.rows, self.snvs, self.insertions, self.deletions, self.deleted_ranges, self.dropped_points = [x.value for x in v]
+
+    def close(self):
+        if self._h:
+            self._lib.tksmseq_variants_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Sequencer:
     """One context = one GPU (the reference's module globals: reference_seqs, identities, models).
 
@@ -270,6 +293,14 @@ class Sequencer:
         self._chk(self._lib.tksmseq_batch_from_mdf_text(self._ctx, b, len(b), C.byref(h)))
         return Batch(self, h)
 
+    def molecules_from_mdf(self, text):
+        """The parser of the MDF -> MDF modules (tksmseq_molecules_from_mdf_text), which run without a FASTA: a contig name the context
+        does not know stays what it is (a literal, printed back by to_mdf_text), substitution positions are not checked."""
+        b = text.encode() if isinstance(text, str) else bytes(text)
+        h = C.c_void_p()
+        self._chk(self._lib.tksmseq_molecules_from_mdf_text(self._ctx, b, len(b), C.byref(h)))
+        return Batch(self, h)
+
     def batch_from_arrays(self, reads, intervals, mods=None, literals=None, literal_pool=b"", ids=None, id_pool=b""):
         """Binary layout of include/tksmseq.h (numpy arrays)."""
         reads = np.ascontiguousarray(reads, np.uint32).reshape(-1, 2)
@@ -395,6 +426,28 @@ class Sequencer:
         q = L.ShuffleParams(seed, buffer_size, 0 if comments else L.MOL_NO_COMMENTS, 0)
         h = C.c_void_p()
         self._chk(self._lib.tksmseq_shuffle(self._ctx, batch._h, C.byref(q), C.byref(h)))
+        return Batch(self, h)
+
+    # ---- mutate: a variant table applied to every segment (device to device)
+    def load_variants(self, path=None, text=None):
+        """A table of `CONTIG POS MOD` lines (tksmseq_variants_load) from a file or from text: MOD all digits is a deletion of
+        [POS, MOD), one letter an SNV, `.SEQ` / `XSEQ` an insertion of SEQ behind POS (X replaces the base at POS)."""
+        if (path is None) == (text is None):
+            raise ValueError("exactly one of path and text")
+        h = C.c_void_p()
+        if path is not None:
+            self._chk(self._lib.tksmseq_variants_load(self._ctx, str(path).encode(), None, 0, C.byref(h)))
+        else:
+            b = text.encode() if isinstance(text, str) else bytes(text)
+            self._chk(self._lib.tksmseq_variants_load(self._ctx, None, b, len(b), C.byref(h)))
+        return Variants(self._lib, h)
+
+    def mutate(self, batch, variants, comments=True):
+        """tksmseq_mutate: the SNVs, insertions and deletions of `variants` applied to every (unrolled) molecule of the batch; a perfect
+        read of the result is the same slice of the mutated contigs.  No random numbers."""
+        q = L.MutateParams(0 if comments else L.MOL_NO_COMMENTS, 0)
+        h = C.c_void_p()
+        self._chk(self._lib.tksmseq_mutate(self._ctx, batch._h, variants._h, C.byref(q), C.byref(h)))
         return Batch(self, h)
 
     # ---- filter and merge: split and join batches (device to device)
