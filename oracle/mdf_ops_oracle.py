@@ -157,7 +157,7 @@ class PcrUnresolved(ValueError):
 
 
 def pcr_table_error(cycles, efficiency, drop, tables=None):
-    """Bound on the relative error of the divisors 1 - q[t] and 1 - A[t] of the walk (pcr_setup in tksm_amd/csrc/mdf_ops.cpp has the same
+    """Bound on the relative error of the divisors 1 - q[t] and 1 - A[t] of the walk (pcr_tables in tksm_amd/csrc/mdf_ops.cpp has the same
     recursion): every floating-point operation is exact up to a factor 1 +- u, u = 2^-53; eq, eA bound |computed - exact| of q[t], A[t].
     Both divisors are differences of numbers near 1 -- 1 - q[cycles - 1] is the drop ratio itself -- so the bound is about
     (5 / efficiency + 2) u / drop; at a drop ratio near u the divisors round to 0, pm / (1 - A[t]) is 0 / 0 and nothing is written."""

@@ -1,12 +1,15 @@
-"""The output-batch builder that pcr, truncate, polyA, tag, scb, flip, tail-noise and random-wgs share (OutBatch, tksm_amd/csrc/mdf_ops.cpp)
-where a shared builder can go wrong: a batch without molecules, a batch of one molecule with one segment, a batch with an unrolled
+"""The output-batch builder that every molecule transform shares (OutBatch and MolPlacement, tksm_amd/csrc/mdf_batch.h; the transforms
+themselves are in mdf_ops.cpp, mdf_move.cpp and mdf_make.cpp) where a shared builder can go wrong: a batch without molecules, a batch of one molecule with one segment, a batch with an unrolled
 depth-3 molecule, an empty segment and a literal contig -- every transform against its specification, text for text -- and a context
 that goes on working after a transform has returned an error half way (what the error exit gave back to the allocation cache is
 really free).  GPU only (-m gpu)."""
 import pytest
 
 import core_modules_spec as cs
+import filter_spec as fs
+import glue_shuffle_spec as gss
 import mdf_ops_oracle as mo
+import mutate_spec as ms
 import noise_spec as ns
 import wgs_spec as ws
 
@@ -19,6 +22,25 @@ BATCHES = {
               "+gap\t1\tCB=.;\nchr1\t500\t500\t+\t\nchr2\t2000\t2350\t-\t3T\n"
               "+lit\t1\tz;CB=TTGACCATGA,ACGT;\nchr1\t10\t260\t+\t\nAAAAAAAAAAAAAAAAAAAAAAAAA\t0\t25\t-\t0C\n"),
 }
+# SNV, deletion, insertion with and without anchor letter, and a contig that the batch knows as a literal
+VARIANTS = "chr1\t1100\tG\nchr1\t1200\t1250\nchr2\t100\tATTT\nchr2\t2100\t.GG\nAAAAAAAAAAAAAAAAAAAAAAAAA\t3\tC\n"
+FILTER = ["size >=400", "info CB"]
+
+
+def _mutate(s, b):
+    v = s.load_variants(text=VARIANTS)
+    try:
+        return s.mutate(b, v)
+    finally:
+        v.close()
+
+
+def _filter_side(s, b, true_side):
+    t, f = s.filter(b, FILTER)
+    (f if true_side else t).free()
+    return t if true_side else f
+
+
 # name: (the transform on the device, its specification on the unrolled molecules)
 TRANSFORMS = {
     "pcr": (lambda s, b: s.pcr(b, 3, 40, error_rate=2e-3, efficiency=0.8, seed=5),
@@ -36,6 +58,13 @@ TRANSFORMS = {
                           lambda m: ns.noise_spec(m, 17, ns.NORMAL, 50.0, 10.0, first=99)),
     "tail-noise palindromic": (lambda s, b: s.append_noise(b, ns.NORMAL, 300.0, 200.0, palindromic=True, error_rate=0.5, seed=17, first=99),
                                lambda m: ns.noise_spec(m, 17, ns.NORMAL, 300.0, 200.0, True, 0.5, first=99)),
+    "glue": (lambda s, b: s.glue(b, 0.5, seed=7, first_molecule_index=31), lambda m: gss.glue_spec(m, 0.5, 7, first=31)),
+    "shuffle whole": (lambda s, b: s.shuffle(b, seed=11), lambda m: gss.shuffle_spec(m, 11)),
+    "shuffle buffer 2": (lambda s, b: s.shuffle(b, seed=11, buffer_size=2), lambda m: gss.shuffle_spec(m, 11, 2)),
+    "mutate": (_mutate, lambda m: ms.mutate_spec(m, ms.normal_form(ms.parse_variants(VARIANTS))[0])),
+    "filter true side": (lambda s, b: _filter_side(s, b, True), lambda m: fs.filter_spec(m, FILTER)[0]),
+    "filter false side": (lambda s, b: _filter_side(s, b, False), lambda m: fs.filter_spec(m, FILTER)[1]),
+    "merge": (lambda s, b: s.merge([b, b]), lambda m: fs.concat_spec([m, m])),
 }
 _WANT = {}
 

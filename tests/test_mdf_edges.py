@@ -69,7 +69,7 @@ def test_deterministic_kde_model_draws_constants():
 def test_pcr_refusal_threshold():
     """The q / A tables stop resolving the drop ratio long before they fail outright (1 - q[cycles - 1] IS the drop ratio, known to
     about 2^-53 / drop of itself): pcr_spec raises where the bound on the relative error of the divisors 1 - q[t], 1 - A[t] is above
-    2^-24 (mo.pcr_table_error has the derivation, tksm_amd/csrc/mdf_ops.cpp pcr_setup the same recursion).  The case that used to come
+    2^-24 (mo.pcr_table_error has the derivation, tksm_amd/csrc/mdf_ops.cpp pcr_tables the same recursion).  The case that used to come
     back empty is refused; BASELINE config 5 (20 cycles, Taq-setting1, 2e8 templates, target 2e8) is far inside."""
     mols = mo.stream_mdf(ec.pcr_templates_text(), unroll=True)
     with pytest.raises(mo.PcrUnresolved, match="56 cycles.*efficiency 1.0.*200 templates"):

@@ -1,5 +1,5 @@
 // ctx.h -- internal: the context and batch objects behind the opaque handles of include/tksmseq.h (shared by api.cpp, run.cpp
-// and mdf_ops.cpp).
+// and, through mdf_batch.h, the molecule transforms mdf_ops.cpp, mdf_move.cpp, mdf_make.cpp and mdf_text.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -91,10 +91,15 @@ struct DevBuf {
     // pooled: allocations come from / go back to DevCache, and no queued work may still use a block that goes back.  With pool_stream set
     // the buffer sees to that itself: release() drains that stream first (TmpBuf, the temporaries of a call).  The tables of a batch carry
     // no stream; whoever deletes a batch drains the stream of the context that ran it first: tksmseq_batch_free for a finished batch,
-    // OutBatch (mdf_ops.cpp) for one still under construction when a transform returns an error.
+    // OutBatch (mdf_batch.h) for one still under construction when a transform returns an error.
     bool pooled = false;
     hipStream_t pool_stream = nullptr;
     int dev = -1;
+    // one owner per block: a buffer moves (the source is left empty), it is never copied
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap), owned(o.owned), pooled(o.pooled), pool_stream(o.pool_stream), dev(o.dev) { o.p = nullptr; o.cap = 0; }
     void release() {
         if (p && owned) {
             if (pooled) { if (pool_stream) (void)hipStreamSynchronize(pool_stream); DevCache::get().give(dev, p, cap); }

@@ -1,5 +1,5 @@
 // filter_host.h -- the condition parser of `filter` (FilterCondition's constructor, src/filter.cpp:24-115), shared by tksmseq_filter
-// (mdf_ops.cpp) and `tksm filter` (mdf_modules.cpp), which checks its conditions before it opens a file or a device.
+// (mdf_move.cpp) and `tksm filter` (mdf_modules.cpp), which checks its conditions before it opens a file or a device.
 #pragma once
 #include <cerrno>
 #include <climits>

@@ -35,14 +35,17 @@ struct MolView {
 struct MolOut {
     uint32_t* reads; uint32_t* intervals; uint32_t* mods; uint32_t* ids; uint8_t* idpool;
 };
+// what a count pass writes and a write pass reads, one entry per output molecule
+struct MolCounts { uint64_t *ivl, *mod, *id; };           // intervals, substitutions, id bytes
+struct MolOffsets { const uint64_t *ivl, *mod, *id; };    // their exclusive scans, [n + 1]
 
 // PCR: pass 1 counts the emitted copies of every template; pass 2 lists them (template, path mask) with their sizes;
 // pass 3 writes the molecules
 hipError_t launch_pcr_count(const MolView& m, const PcrParams& p, uint64_t* n_out /* [n_kept] */, uint32_t* status, hipStream_t s);
 hipError_t launch_pcr_list(const MolView& m, const PcrParams& p, const uint64_t* out_off /* [n_kept + 1] */, uint32_t* node_mol,
-                           uint64_t* node_mask, uint64_t* node_ivls, uint64_t* node_mods, uint64_t* node_idlen, hipStream_t s);
+                           uint64_t* node_mask, const MolCounts& c, hipStream_t s);
 hipError_t launch_pcr_write(const MolView& m, const PcrParams& p, uint64_t n_nodes, const uint32_t* node_mol, const uint64_t* node_mask,
-                            const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off, const MolOut& o, hipStream_t s);
+                            const MolOffsets& f, const MolOut& o, hipStream_t s);
 
 // truncation
 struct TrcParams {
@@ -61,9 +64,8 @@ struct TrcParams {
 };
 // per molecule: the kept part [cut5, total - cut3) of its bases in segment order, plus what the TR comment shows
 hipError_t launch_trc_plan(const MolView& m, const TrcParams& p, uint64_t first_index, uint32_t* keep_from, uint32_t* keep_to,
-                           double* tr_len, double* tr_side, uint64_t* n_ivls, uint64_t* n_mods, uint64_t* n_idlen, hipStream_t s);
-hipError_t launch_trc_write(const MolView& m, const uint32_t* keep_from, const uint32_t* keep_to, const uint64_t* ivl_off,
-                            const uint64_t* mod_off, const uint64_t* id_off, const MolOut& o, hipStream_t s);
+                           double* tr_len, double* tr_side, const MolCounts& c, hipStream_t s);
+hipError_t launch_trc_write(const MolView& m, const uint32_t* keep_from, const uint32_t* keep_to, const MolOffsets& f, const MolOut& o, hipStream_t s);
 
 
 // polyA / tag / scb / flip (src/polyA.cpp:133-148, src/tag.cpp:70-113, src/scb.cpp:57-80, src/interval.h:908-920): a plan per molecule
@@ -91,10 +93,9 @@ hipError_t launch_tag_plan(uint64_t n, const TagParams& p, uint64_t first_index,
                            hipStream_t s);
 hipError_t launch_flip_plan(uint64_t n, uint64_t seed, double p, uint64_t first_index, uint8_t* flip, hipStream_t s);
 // pre / post / flip: [n_reads], any may be null (nothing of that kind); lits: the OUTPUT literal table (new literals' lengths)
-hipError_t launch_edit_count(const MolView& m, const uint32_t* pre, const uint32_t* post, uint64_t* n_ivls, uint64_t* n_mods, uint64_t* n_idlen,
-                             hipStream_t s);
-hipError_t launch_edit_write(const MolView& m, const uint32_t* pre, const uint32_t* post, const uint8_t* flip, const uint64_t* lits,
-                             const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off, const MolOut& o, hipStream_t s);
+hipError_t launch_edit_count(const MolView& m, const uint32_t* pre, const uint32_t* post, const MolCounts& c, hipStream_t s);
+hipError_t launch_edit_write(const MolView& m, const uint32_t* pre, const uint32_t* post, const uint8_t* flip, const uint64_t* lits, const MolOffsets& f,
+                             const MolOut& o, hipStream_t s);
 
 // filter (src/filter.cpp:21-117, :196-212): a two-way partition of a batch by a conjunction of conditions; see mdf_kernels.hip
 enum { FLT_SIZE = 1, FLT_LOCUS = 2 };     // (`info` conditions are read off the comments by the host: a byte per molecule)
@@ -108,28 +109,24 @@ struct FltCond {
     int ranged;                           // 0: any segment on the contig; 1: one whose overlap with [start, end) is positive
     long long start, end;
 };
-struct FltCounts { uint64_t *n_ivls, *n_mods, *n_idlen; };                    // per input molecule: its counts on this side, 0 on the other
-struct FltOffsets { const uint64_t *ivl, *mod, *id; };                        // their exclusive scans
-// side[r]: 1 when the conjunction (inverted by negate) holds; flag[r] the same as a scan input; f.n_ivls null: no false side is sized
+// side[r]: 1 when the conjunction (inverted by negate) holds; flag[r] the same as a scan input; t / f: per INPUT molecule its counts on
+// that side, 0 on the other; f.ivl null: no false side is sized
 hipError_t launch_flt_pred(const MolView& m, const FltCond* conds, uint32_t n_conds, const uint8_t* info, int negate, uint8_t* side, uint64_t* flag,
-                           const FltCounts& t, const FltCounts& f, hipStream_t s);
+                           const MolCounts& t, const MolCounts& f, hipStream_t s);
 // rank: exclusive scan of flag; f.ivl null: molecules of the false side are not written (of is not touched)
-hipError_t launch_flt_write(const MolView& m, const uint8_t* side, const uint64_t* rank, const FltOffsets& t, const FltOffsets& f, const MolOut& ot,
+hipError_t launch_flt_write(const MolView& m, const uint8_t* side, const uint64_t* rank, const MolOffsets& t, const MolOffsets& f, const MolOut& ot,
                             const MolOut& of, hipStream_t s);
 // concat: where one input's molecules, intervals, substitutions, id bytes, literal entries and literal pool bytes start in the output
 struct CatBase { uint64_t mol, ivl, mod, id; uint32_t lit; uint64_t pool; };
-// ivl_off / mod_off / id_off: scans of the input's own counts (launch_edit_count without literals); lits: the output's literal table
-hipError_t launch_cat_write(const MolView& m, const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off, const CatBase& base, uint64_t* lits,
-                            const MolOut& o, hipStream_t s);
+// f: scans of the input's own counts (launch_edit_count without literals); lits: the output's literal table
+hipError_t launch_cat_write(const MolView& m, const MolOffsets& f, const CatBase& base, uint64_t* lits, const MolOut& o, hipStream_t s);
 
 // unsegment (src/unsegment.cpp:88-105): glue a molecule behind its predecessor with probability p; see mdf_kernels.hip
 // join[r]: 1 when molecule r (index first_index + r of the whole input) joins its predecessor, never for r = 0; head[r] = 1 - join[r] as a scan
 // input; the three counts of molecule r on its own, the id length 0 for a joiner
-hipError_t launch_glue_plan(const MolView& m, uint64_t seed, double p, uint64_t first_index, uint8_t* join, uint64_t* head, uint64_t* n_ivls, uint64_t* n_mods,
-                            uint64_t* n_idlen, hipStream_t s);
+hipError_t launch_glue_plan(const MolView& m, uint64_t seed, double p, uint64_t first_index, uint8_t* join, uint64_t* head, const MolCounts& c, hipStream_t s);
 // rank: exclusive scan of head ([n_reads + 1]); the offsets: scans of the counts.  Output molecule rank[r] is the chain that head r opens
-hipError_t launch_glue_write(const MolView& m, const uint8_t* join, const uint64_t* rank, const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off,
-                             const MolOut& o, hipStream_t s);
+hipError_t launch_glue_write(const MolView& m, const uint8_t* join, const uint64_t* rank, const MolOffsets& f, const MolOut& o, hipStream_t s);
 
 // shuffle (src/shuffle.cpp:23-44): the buffer of n_slots molecules as a sort; see mdf_kernels.hip.  n_arrivals = n - n_slots
 hipError_t launch_shf_key(uint64_t n_slots, uint64_t seed, uint64_t* key, hipStream_t s);                       // key[s] of slot s
@@ -140,9 +137,8 @@ hipError_t launch_shf_evict(uint64_t n_arrivals, uint32_t n_slots, const uint32_
 hipError_t launch_shf_occupant(uint32_t n_slots, uint64_t n_arrivals, const uint32_t* order, const uint32_t* slot_sorted, const uint32_t* arrival_sorted,
                                uint32_t* src_tail, hipStream_t s);
 // a gather: output molecule j is input molecule src[j] (unrolled: ids with their suffix); counts, then -- with their scans -- the copy
-hipError_t launch_gather_count(const MolView& m, const uint32_t* src, uint64_t n, uint64_t* n_ivls, uint64_t* n_mods, uint64_t* n_idlen, hipStream_t s);
-hipError_t launch_gather_write(const MolView& m, const uint32_t* src, uint64_t n, const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off,
-                               const MolOut& o, hipStream_t s);
+hipError_t launch_gather_count(const MolView& m, const uint32_t* src, uint64_t n, const MolCounts& c, hipStream_t s);
+hipError_t launch_gather_write(const MolView& m, const uint32_t* src, uint64_t n, const MolOffsets& f, const MolOut& o, hipStream_t s);
 
 // mutate (a variant table applied to every segment; the transform is this build's own, DESIGN.md "mutate"): see mdf_kernels.hip
 constexpr uint32_t MUT_NONE = 0xffffffffu;
@@ -161,9 +157,8 @@ struct MutView {                          // the device form of a variant table 
 // one lane per literal entry of the input: lit_ctg[l] = the table's contig whose name is the literal's text, MUT_NONE: none; and one lane per
 // kept insertion k: entry lit_base + k of the OUTPUT literal table = {pool_base + its offset, its letters}
 hipError_t launch_mut_resolve(const BatchView& b, const MutView& v, uint32_t* lit_ctg, uint64_t* out_lits, uint32_t lit_base, uint64_t pool_base, hipStream_t s);
-hipError_t launch_mut_count(const MolView& m, const MutView& v, const uint32_t* lit_ctg, uint64_t* n_ivls, uint64_t* n_mods, uint64_t* n_idlen, hipStream_t s);
-hipError_t launch_mut_write(const MolView& m, const MutView& v, const uint32_t* lit_ctg, uint32_t lit_base, const uint64_t* ivl_off, const uint64_t* mod_off,
-                            const uint64_t* id_off, const MolOut& o, hipStream_t s);
+hipError_t launch_mut_count(const MolView& m, const MutView& v, const uint32_t* lit_ctg, const MolCounts& c, hipStream_t s);
+hipError_t launch_mut_write(const MolView& m, const MutView& v, const uint32_t* lit_ctg, uint32_t lit_base, const MolOffsets& f, const MolOut& o, hipStream_t s);
 
 // random-wgs (src/random_wgs.cpp:181-207): fragments of the whole genome, one lane per candidate; see mdf_kernels.hip
 constexpr int WGS_LDS_CONTIGS = 2048;       // running sums of that many contigs are searched in LDS (16 KB), more in global memory
@@ -231,10 +226,8 @@ hipError_t launch_noise_plan(const MolView& m, const NoiseParams& p, uint64_t fi
 hipError_t launch_noise_fill(uint64_t n, uint64_t n_blocks, const NoiseParams& p, uint64_t first_index, const uint32_t* len, const uint64_t* blk_off,
                              uint32_t lit_base, uint64_t pool_base, uint64_t* lits, uint8_t* pool, uint32_t* post, hipStream_t s);
 // palindromic mode, after launch_edit_count / launch_edit_write without literals or flip: the count ADDS the hairpin's segments and
-// substitutions to n_ivls / n_mods, the write puts them behind the molecule's own (ivl_off / mod_off: scans of the sums)
-hipError_t launch_pal_count(const MolView& m, const NoiseParams& p, uint64_t first_index, const uint4* plan, uint64_t* n_ivls, uint64_t* n_mods,
-                            hipStream_t s);
-hipError_t launch_pal_write(const MolView& m, const NoiseParams& p, uint64_t first_index, const uint4* plan, const uint64_t* ivl_off,
-                            const uint64_t* mod_off, const MolOut& o, hipStream_t s);
+// substitutions to c.ivl / c.mod, the write puts them behind the molecule's own (f.ivl / f.mod: scans of the sums); the id members are not read
+hipError_t launch_pal_count(const MolView& m, const NoiseParams& p, uint64_t first_index, const uint4* plan, const MolCounts& c, hipStream_t s);
+hipError_t launch_pal_write(const MolView& m, const NoiseParams& p, uint64_t first_index, const uint4* plan, const MolOffsets& f, const MolOut& o, hipStream_t s);
 
 }  // namespace tk

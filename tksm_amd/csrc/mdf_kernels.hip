@@ -153,8 +153,8 @@ DEV uint32_t pcr_id_len(const MolView& M, uint32_t u, unsigned long long mask) {
 }
 
 __global__ void k_pcr_list(MolView M, PcrParams P, const uint64_t* __restrict__ out_off, uint32_t* __restrict__ node_mol,
-                           uint64_t* __restrict__ node_mask, uint64_t* __restrict__ node_ivls, uint64_t* __restrict__ node_mods,
-                           uint64_t* __restrict__ node_idlen) {
+                           uint64_t* __restrict__ node_mask, MolCounts C) {
+    uint64_t* __restrict__ node_ivls = C.ivl; uint64_t* __restrict__ node_mods = C.mod; uint64_t* __restrict__ node_idlen = C.id;
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M.n_kept) return;
     const uint32_t u = pcr_template(M, i);
@@ -177,8 +177,8 @@ __global__ void k_pcr_list(MolView M, PcrParams P, const uint64_t* __restrict__ 
 }
 
 __global__ void k_pcr_write(MolView M, PcrParams P, uint64_t n_nodes, const uint32_t* __restrict__ node_mol,
-                            const uint64_t* __restrict__ node_mask, const uint64_t* __restrict__ ivl_off,
-                            const uint64_t* __restrict__ mod_off, const uint64_t* __restrict__ id_off, MolOut O) {
+                            const uint64_t* __restrict__ node_mask, MolOffsets F, MolOut O) {
+    const uint64_t* __restrict__ ivl_off = F.ivl; const uint64_t* __restrict__ mod_off = F.mod; const uint64_t* __restrict__ id_off = F.id;
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n_nodes) return;
     const uint32_t u = node_mol[j];
@@ -258,8 +258,8 @@ DEV double trc_row_draw(const TrcParams& T, int row, double u, uint32_t w) {
 }
 
 __global__ void k_trc_plan(MolView M, TrcParams T, uint64_t first_index, uint32_t* __restrict__ keep_from, uint32_t* __restrict__ keep_to,
-                           double* __restrict__ tr_len, double* __restrict__ tr_side, uint64_t* __restrict__ n_ivls,
-                           uint64_t* __restrict__ n_mods, uint64_t* __restrict__ n_idlen) {
+                           double* __restrict__ tr_len, double* __restrict__ tr_side, MolCounts C) {
+    uint64_t* __restrict__ n_ivls = C.ivl; uint64_t* __restrict__ n_mods = C.mod; uint64_t* __restrict__ n_idlen = C.id;
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= M.B.n_reads) return;
     const BatchView& B = M.B;
@@ -332,9 +332,8 @@ __global__ void k_trc_plan(MolView M, TrcParams T, uint64_t first_index, uint32_
     n_idlen[r] = B.ids[2 * r + 1] + ((M.dup && (M.dup[r] >> 31)) ? 1u + (uint32_t)ndig(M.dup[r] & 0x7fffffffu) : 0u);
 }
 
-__global__ void k_trc_write(MolView M, const uint32_t* __restrict__ keep_from, const uint32_t* __restrict__ keep_to,
-                            const uint64_t* __restrict__ ivl_off, const uint64_t* __restrict__ mod_off,
-                            const uint64_t* __restrict__ id_off, MolOut O) {
+__global__ void k_trc_write(MolView M, const uint32_t* __restrict__ keep_from, const uint32_t* __restrict__ keep_to, MolOffsets F, MolOut O) {
+    const uint64_t* __restrict__ ivl_off = F.ivl; const uint64_t* __restrict__ mod_off = F.mod; const uint64_t* __restrict__ id_off = F.id;
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= M.B.n_reads) return;
     const BatchView& B = M.B;
@@ -523,8 +522,8 @@ DEV uint32_t unrolled_id_len(const MolView& M, uint64_t r) {
     return M.B.ids[2 * r + 1] + ((M.dup && (M.dup[r] >> 31)) ? 1u + (uint32_t)ndig(M.dup[r] & 0x7fffffffu) : 0u);
 }
 
-__global__ void k_edit_count(MolView M, const uint32_t* __restrict__ pre, const uint32_t* __restrict__ post, uint64_t* __restrict__ n_ivls,
-                             uint64_t* __restrict__ n_mods, uint64_t* __restrict__ n_idlen) {
+__global__ void k_edit_count(MolView M, const uint32_t* __restrict__ pre, const uint32_t* __restrict__ post, MolCounts C) {
+    uint64_t* __restrict__ n_ivls = C.ivl; uint64_t* __restrict__ n_mods = C.mod; uint64_t* __restrict__ n_idlen = C.id;
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= M.B.n_reads) return;
     n_ivls[r] = M.B.reads[2 * r + 1] + ((pre && pre[r] != EDIT_NONE) ? 1u : 0u) + ((post && post[r] != EDIT_NONE) ? 1u : 0u);
@@ -533,8 +532,8 @@ __global__ void k_edit_count(MolView M, const uint32_t* __restrict__ pre, const 
 }
 
 __global__ void k_edit_write(MolView M, const uint32_t* __restrict__ pre, const uint32_t* __restrict__ post, const uint8_t* __restrict__ flip,
-                             const uint64_t* __restrict__ lits, const uint64_t* __restrict__ ivl_off, const uint64_t* __restrict__ mod_off,
-                             const uint64_t* __restrict__ id_off, MolOut O) {
+                             const uint64_t* __restrict__ lits, MolOffsets F, MolOut O) {
+    const uint64_t* __restrict__ ivl_off = F.ivl; const uint64_t* __restrict__ mod_off = F.mod; const uint64_t* __restrict__ id_off = F.id;
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= M.B.n_reads) return;
     const BatchView& B = M.B;
@@ -762,8 +761,8 @@ DEV bool noise_hit(const NoiseParams& P, uint64_t g, uint32_t t, uint32_t& pick)
     return u01((t & 1u) ? w.z : w.x) < P.error_rate;
 }
 
-__global__ void __launch_bounds__(256) k_pal_count(MolView M, NoiseParams P, uint64_t first_index, const uint4* __restrict__ plan,
-                                                   uint64_t* __restrict__ n_ivls, uint64_t* __restrict__ n_mods) {
+__global__ void __launch_bounds__(256) k_pal_count(MolView M, NoiseParams P, uint64_t first_index, const uint4* __restrict__ plan, MolCounts C) {
+    uint64_t* __restrict__ n_ivls = C.ivl; uint64_t* __restrict__ n_mods = C.mod;
     const uint64_t r = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
     if (r >= M.B.n_reads) return;
     const uint32_t lane = threadIdx.x & 63u;
@@ -791,8 +790,9 @@ __global__ void __launch_bounds__(256) k_pal_count(MolView M, NoiseParams P, uin
     if (lane == 0u) { n_ivls[r] += nseg; n_mods[r] += nm; }
 }
 
-__global__ void __launch_bounds__(256) k_pal_write(MolView M, NoiseParams P, uint64_t first_index, const uint4* __restrict__ plan,
-                                                   const uint64_t* __restrict__ ivl_off, const uint64_t* __restrict__ mod_off, MolOut O) {
+__global__ void __launch_bounds__(256) k_pal_write(MolView M, NoiseParams P, uint64_t first_index, const uint4* __restrict__ plan, MolOffsets F,
+                                                   MolOut O) {
+    const uint64_t* __restrict__ ivl_off = F.ivl; const uint64_t* __restrict__ mod_off = F.mod;
     const uint64_t r = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
     if (r >= M.B.n_reads) return;
     const uint32_t lane = threadIdx.x & 63u;
@@ -988,7 +988,7 @@ DEV bool flt_holds(const BatchView& B, uint32_t r, const FltCond& C) {
 }
 
 __global__ void k_flt_pred(MolView M, const FltCond* __restrict__ conds, uint32_t n_conds, const uint8_t* __restrict__ info, int negate,
-                           uint8_t* __restrict__ side, uint64_t* __restrict__ flag, FltCounts T, FltCounts F) {
+                           uint8_t* __restrict__ side, uint64_t* __restrict__ flag, MolCounts T, MolCounts F) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= M.B.n_reads) return;
     bool ok = info ? info[r] != 0 : true;
@@ -997,8 +997,8 @@ __global__ void k_flt_pred(MolView M, const FltCond* __restrict__ conds, uint32_
     side[r] = ok ? 1 : 0;
     flag[r] = ok ? 1ull : 0ull;
     const uint64_t ni = M.B.reads[2 * r + 1], nm = mol_mods(M.B, (uint32_t)r), nd = unrolled_id_len(M, r);
-    T.n_ivls[r] = ok ? ni : 0ull; T.n_mods[r] = ok ? nm : 0ull; T.n_idlen[r] = ok ? nd : 0ull;
-    if (F.n_ivls) { F.n_ivls[r] = ok ? 0ull : ni; F.n_mods[r] = ok ? 0ull : nm; F.n_idlen[r] = ok ? 0ull : nd; }
+    T.ivl[r] = ok ? ni : 0ull; T.mod[r] = ok ? nm : 0ull; T.id[r] = ok ? nd : 0ull;
+    if (F.ivl) { F.ivl[r] = ok ? 0ull : ni; F.mod[r] = ok ? 0ull : nm; F.id[r] = ok ? 0ull : nd; }
 }
 
 // the id of molecule r of M (with the unroll suffix) becomes the id of molecule j of O, its bytes at id_at
@@ -1032,7 +1032,7 @@ DEV void copy_molecule(const MolView& M, uint64_t r, uint64_t j, uint64_t io, ui
 }
 
 // rank: exclusive scan of flag (molecules of the true side before r); T / F: the scans of the counts; OF is not touched without F
-__global__ void k_flt_write(MolView M, const uint8_t* __restrict__ side, const uint64_t* __restrict__ rank, FltOffsets T, FltOffsets F, MolOut OT, MolOut OF) {
+__global__ void k_flt_write(MolView M, const uint8_t* __restrict__ side, const uint64_t* __restrict__ rank, MolOffsets T, MolOffsets F, MolOut OT, MolOut OF) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= M.B.n_reads) return;
     if (side[r]) copy_molecule(M, r, rank[r], T.ivl[r], T.mod[r], T.id[r], 0u, OT);
@@ -1040,8 +1040,8 @@ __global__ void k_flt_write(MolView M, const uint8_t* __restrict__ side, const u
 }
 
 // one input of a concatenation: its molecules (lanes below n_reads) and its literal entries (lanes below n_literals)
-__global__ void k_cat_write(MolView M, const uint64_t* __restrict__ ivl_off, const uint64_t* __restrict__ mod_off, const uint64_t* __restrict__ id_off,
-                            CatBase base, uint64_t* __restrict__ lits, MolOut O) {
+__global__ void k_cat_write(MolView M, MolOffsets F, CatBase base, uint64_t* __restrict__ lits, MolOut O) {
+    const uint64_t* __restrict__ ivl_off = F.ivl; const uint64_t* __restrict__ mod_off = F.mod; const uint64_t* __restrict__ id_off = F.id;
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r < M.B.n_reads) copy_molecule(M, r, base.mol + r, base.ivl + ivl_off[r], base.mod + mod_off[r], base.id + id_off[r], base.lit, O);
     if (r < M.B.n_literals) { lits[2ull * (base.lit + r)] = M.B.literals[2 * r] + base.pool; lits[2ull * (base.lit + r) + 1] = M.B.literals[2 * r + 1]; }
@@ -1061,7 +1061,8 @@ __global__ void k_cat_write(MolView M, const uint64_t* __restrict__ ivl_off, con
 // chimeras and a joiner's depth is lost).
 // ------------------------------------------------------------------------------------------------
 __global__ void k_glue_plan(MolView M, uint64_t seed, double p, uint64_t first_index, uint8_t* __restrict__ join, uint64_t* __restrict__ head,
-                            uint64_t* __restrict__ n_ivls, uint64_t* __restrict__ n_mods, uint64_t* __restrict__ n_idlen) {
+                            MolCounts C) {
+    uint64_t* __restrict__ n_ivls = C.ivl; uint64_t* __restrict__ n_mods = C.mod; uint64_t* __restrict__ n_idlen = C.id;
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= M.B.n_reads) return;
     const bool j = r > 0 && u01(philox_mol(seed, first_index + r, ST_GLUE, 0).x) < p;      // (NaN compares false: nothing joins)
@@ -1073,8 +1074,8 @@ __global__ void k_glue_plan(MolView M, uint64_t seed, double p, uint64_t first_i
 }
 
 // rank: exclusive scan of head ([n + 1]); ivl_off / mod_off / id_off: the scans of the counts
-__global__ void k_glue_write(MolView M, const uint8_t* __restrict__ join, const uint64_t* __restrict__ rank, const uint64_t* __restrict__ ivl_off,
-                             const uint64_t* __restrict__ mod_off, const uint64_t* __restrict__ id_off, MolOut O) {
+__global__ void k_glue_write(MolView M, const uint8_t* __restrict__ join, const uint64_t* __restrict__ rank, MolOffsets F, MolOut O) {
+    const uint64_t* __restrict__ ivl_off = F.ivl; const uint64_t* __restrict__ mod_off = F.mod; const uint64_t* __restrict__ id_off = F.id;
     const uint64_t n = M.B.n_reads;
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
@@ -1134,16 +1135,16 @@ __global__ void k_shf_occupant(uint64_t n_slots, uint64_t n_arrivals, uint32_t B
     src_tail[q] = (lo > 0 && slot_s[lo - 1] == s) ? B + arr_s[lo - 1] : s;
 }
 
-__global__ void k_gather_count(MolView M, const uint32_t* __restrict__ src, uint64_t n, uint64_t* __restrict__ n_ivls, uint64_t* __restrict__ n_mods,
-                               uint64_t* __restrict__ n_idlen) {
+__global__ void k_gather_count(MolView M, const uint32_t* __restrict__ src, uint64_t n, MolCounts C) {
+    uint64_t* __restrict__ n_ivls = C.ivl; uint64_t* __restrict__ n_mods = C.mod; uint64_t* __restrict__ n_idlen = C.id;
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
     const uint32_t r = src[j];
     n_ivls[j] = M.B.reads[2 * r + 1]; n_mods[j] = mol_mods(M.B, r); n_idlen[j] = unrolled_id_len(M, r);
 }
 
-__global__ void k_gather_write(MolView M, const uint32_t* __restrict__ src, uint64_t n, const uint64_t* __restrict__ ivl_off,
-                               const uint64_t* __restrict__ mod_off, const uint64_t* __restrict__ id_off, MolOut O) {
+__global__ void k_gather_write(MolView M, const uint32_t* __restrict__ src, uint64_t n, MolOffsets F, MolOut O) {
+    const uint64_t* __restrict__ ivl_off = F.ivl; const uint64_t* __restrict__ mod_off = F.mod; const uint64_t* __restrict__ id_off = F.id;
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
     copy_molecule(M, src[j], j, ivl_off[j], mod_off[j], id_off[j], 0u, O);
@@ -1275,8 +1276,8 @@ DEV void mut_segment(const BatchView& B, const MutView& V, const uint32_t* __res
     if (back) { io += seg_i; mo += seg_m; }
 }
 
-__global__ void k_mut_count(MolView M, MutView V, const uint32_t* __restrict__ lit_ctg, uint64_t* __restrict__ n_ivls, uint64_t* __restrict__ n_mods,
-                            uint64_t* __restrict__ n_idlen) {
+__global__ void k_mut_count(MolView M, MutView V, const uint32_t* __restrict__ lit_ctg, MolCounts C) {
+    uint64_t* __restrict__ n_ivls = C.ivl; uint64_t* __restrict__ n_mods = C.mod; uint64_t* __restrict__ n_idlen = C.id;
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= M.B.n_reads) return;
     const BatchView& B = M.B;
@@ -1286,8 +1287,8 @@ __global__ void k_mut_count(MolView M, MutView V, const uint32_t* __restrict__ l
     n_ivls[r] = ni; n_mods[r] = nm; n_idlen[r] = unrolled_id_len(M, r);
 }
 
-__global__ void k_mut_write(MolView M, MutView V, const uint32_t* __restrict__ lit_ctg, uint32_t lit_base, const uint64_t* __restrict__ ivl_off,
-                            const uint64_t* __restrict__ mod_off, const uint64_t* __restrict__ id_off, MolOut O) {
+__global__ void k_mut_write(MolView M, MutView V, const uint32_t* __restrict__ lit_ctg, uint32_t lit_base, MolOffsets F, MolOut O) {
+    const uint64_t* __restrict__ ivl_off = F.ivl; const uint64_t* __restrict__ mod_off = F.mod; const uint64_t* __restrict__ id_off = F.id;
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= M.B.n_reads) return;
     const BatchView& B = M.B;
@@ -1308,28 +1309,27 @@ hipError_t launch_pcr_count(const MolView& m, const PcrParams& p, uint64_t* n_ou
     hipLaunchKernelGGL(k_pcr_count, dim3(nblk(m.n_kept)), dim3(128), 0, s, m, p, n_out, status);
     return hipGetLastError();
 }
-hipError_t launch_pcr_list(const MolView& m, const PcrParams& p, const uint64_t* out_off, uint32_t* node_mol, uint64_t* node_mask,
-                           uint64_t* node_ivls, uint64_t* node_mods, uint64_t* node_idlen, hipStream_t s) {
+hipError_t launch_pcr_list(const MolView& m, const PcrParams& p, const uint64_t* out_off, uint32_t* node_mol, uint64_t* node_mask, const MolCounts& c,
+                           hipStream_t s) {
     if (!m.n_kept) return hipSuccess;
-    hipLaunchKernelGGL(k_pcr_list, dim3(nblk(m.n_kept)), dim3(128), 0, s, m, p, out_off, node_mol, node_mask, node_ivls, node_mods, node_idlen);
+    hipLaunchKernelGGL(k_pcr_list, dim3(nblk(m.n_kept)), dim3(128), 0, s, m, p, out_off, node_mol, node_mask, c);
     return hipGetLastError();
 }
 hipError_t launch_pcr_write(const MolView& m, const PcrParams& p, uint64_t n_nodes, const uint32_t* node_mol, const uint64_t* node_mask,
-                            const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off, const MolOut& o, hipStream_t s) {
+                            const MolOffsets& f, const MolOut& o, hipStream_t s) {
     if (!n_nodes) return hipSuccess;
-    hipLaunchKernelGGL(k_pcr_write, dim3(nblk(n_nodes)), dim3(128), 0, s, m, p, n_nodes, node_mol, node_mask, ivl_off, mod_off, id_off, o);
+    hipLaunchKernelGGL(k_pcr_write, dim3(nblk(n_nodes)), dim3(128), 0, s, m, p, n_nodes, node_mol, node_mask, f, o);
     return hipGetLastError();
 }
 hipError_t launch_trc_plan(const MolView& m, const TrcParams& p, uint64_t first_index, uint32_t* keep_from, uint32_t* keep_to, double* tr_len,
-                           double* tr_side, uint64_t* n_ivls, uint64_t* n_mods, uint64_t* n_idlen, hipStream_t s) {
+                           double* tr_side, const MolCounts& c, hipStream_t s) {
     if (!m.B.n_reads) return hipSuccess;
-    hipLaunchKernelGGL(k_trc_plan, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, p, first_index, keep_from, keep_to, tr_len, tr_side, n_ivls, n_mods, n_idlen);
+    hipLaunchKernelGGL(k_trc_plan, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, p, first_index, keep_from, keep_to, tr_len, tr_side, c);
     return hipGetLastError();
 }
-hipError_t launch_trc_write(const MolView& m, const uint32_t* keep_from, const uint32_t* keep_to, const uint64_t* ivl_off,
-                            const uint64_t* mod_off, const uint64_t* id_off, const MolOut& o, hipStream_t s) {
+hipError_t launch_trc_write(const MolView& m, const uint32_t* keep_from, const uint32_t* keep_to, const MolOffsets& f, const MolOut& o, hipStream_t s) {
     if (!m.B.n_reads) return hipSuccess;
-    hipLaunchKernelGGL(k_trc_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, keep_from, keep_to, ivl_off, mod_off, id_off, o);
+    hipLaunchKernelGGL(k_trc_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, keep_from, keep_to, f, o);
     return hipGetLastError();
 }
 
@@ -1349,49 +1349,46 @@ hipError_t launch_flip_plan(uint64_t n, uint64_t seed, double p, uint64_t first_
     hipLaunchKernelGGL(k_flip_plan, dim3(nblk(n)), dim3(128), 0, s, n, seed, p, first_index, flip);
     return hipGetLastError();
 }
-hipError_t launch_edit_count(const MolView& m, const uint32_t* pre, const uint32_t* post, uint64_t* n_ivls, uint64_t* n_mods, uint64_t* n_idlen,
-                             hipStream_t s) {
+hipError_t launch_edit_count(const MolView& m, const uint32_t* pre, const uint32_t* post, const MolCounts& c, hipStream_t s) {
     if (!m.B.n_reads) return hipSuccess;
-    hipLaunchKernelGGL(k_edit_count, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, pre, post, n_ivls, n_mods, n_idlen);
+    hipLaunchKernelGGL(k_edit_count, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, pre, post, c);
     return hipGetLastError();
 }
 hipError_t launch_edit_write(const MolView& m, const uint32_t* pre, const uint32_t* post, const uint8_t* flip, const uint64_t* lits,
-                             const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off, const MolOut& o, hipStream_t s) {
+                             const MolOffsets& f, const MolOut& o, hipStream_t s) {
     if (!m.B.n_reads) return hipSuccess;
-    hipLaunchKernelGGL(k_edit_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, pre, post, flip, lits, ivl_off, mod_off, id_off, o);
+    hipLaunchKernelGGL(k_edit_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, pre, post, flip, lits, f, o);
     return hipGetLastError();
 }
 
 hipError_t launch_flt_pred(const MolView& m, const FltCond* conds, uint32_t n_conds, const uint8_t* info, int negate, uint8_t* side, uint64_t* flag,
-                           const FltCounts& t, const FltCounts& f, hipStream_t s) {
+                           const MolCounts& t, const MolCounts& f, hipStream_t s) {
     if (!m.B.n_reads) return hipSuccess;
     hipLaunchKernelGGL(k_flt_pred, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, conds, n_conds, info, negate, side, flag, t, f);
     return hipGetLastError();
 }
-hipError_t launch_flt_write(const MolView& m, const uint8_t* side, const uint64_t* rank, const FltOffsets& t, const FltOffsets& f, const MolOut& ot,
+hipError_t launch_flt_write(const MolView& m, const uint8_t* side, const uint64_t* rank, const MolOffsets& t, const MolOffsets& f, const MolOut& ot,
                             const MolOut& of, hipStream_t s) {
     if (!m.B.n_reads) return hipSuccess;
     hipLaunchKernelGGL(k_flt_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, side, rank, t, f, ot, of);
     return hipGetLastError();
 }
-hipError_t launch_cat_write(const MolView& m, const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off, const CatBase& base, uint64_t* lits,
-                            const MolOut& o, hipStream_t s) {
+hipError_t launch_cat_write(const MolView& m, const MolOffsets& f, const CatBase& base, uint64_t* lits, const MolOut& o, hipStream_t s) {
     const uint64_t n = m.B.n_reads > m.B.n_literals ? m.B.n_reads : (uint64_t)m.B.n_literals;
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(k_cat_write, dim3(nblk(n)), dim3(128), 0, s, m, ivl_off, mod_off, id_off, base, lits, o);
+    hipLaunchKernelGGL(k_cat_write, dim3(nblk(n)), dim3(128), 0, s, m, f, base, lits, o);
     return hipGetLastError();
 }
 
-hipError_t launch_glue_plan(const MolView& m, uint64_t seed, double p, uint64_t first_index, uint8_t* join, uint64_t* head, uint64_t* n_ivls, uint64_t* n_mods,
-                            uint64_t* n_idlen, hipStream_t s) {
+hipError_t launch_glue_plan(const MolView& m, uint64_t seed, double p, uint64_t first_index, uint8_t* join, uint64_t* head, const MolCounts& c,
+                            hipStream_t s) {
     if (!m.B.n_reads) return hipSuccess;
-    hipLaunchKernelGGL(k_glue_plan, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, seed, p, first_index, join, head, n_ivls, n_mods, n_idlen);
+    hipLaunchKernelGGL(k_glue_plan, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, seed, p, first_index, join, head, c);
     return hipGetLastError();
 }
-hipError_t launch_glue_write(const MolView& m, const uint8_t* join, const uint64_t* rank, const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off,
-                             const MolOut& o, hipStream_t s) {
+hipError_t launch_glue_write(const MolView& m, const uint8_t* join, const uint64_t* rank, const MolOffsets& f, const MolOut& o, hipStream_t s) {
     if (!m.B.n_reads) return hipSuccess;
-    hipLaunchKernelGGL(k_glue_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, join, rank, ivl_off, mod_off, id_off, o);
+    hipLaunchKernelGGL(k_glue_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, join, rank, f, o);
     return hipGetLastError();
 }
 hipError_t launch_shf_key(uint64_t n_slots, uint64_t seed, uint64_t* key, hipStream_t s) {
@@ -1415,15 +1412,14 @@ hipError_t launch_shf_occupant(uint32_t n_slots, uint64_t n_arrivals, const uint
     hipLaunchKernelGGL(k_shf_occupant, dim3(nblk(n_slots)), dim3(128), 0, s, (uint64_t)n_slots, n_arrivals, n_slots, order, slot_sorted, arrival_sorted, src_tail);
     return hipGetLastError();
 }
-hipError_t launch_gather_count(const MolView& m, const uint32_t* src, uint64_t n, uint64_t* n_ivls, uint64_t* n_mods, uint64_t* n_idlen, hipStream_t s) {
+hipError_t launch_gather_count(const MolView& m, const uint32_t* src, uint64_t n, const MolCounts& c, hipStream_t s) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(k_gather_count, dim3(nblk(n)), dim3(128), 0, s, m, src, n, n_ivls, n_mods, n_idlen);
+    hipLaunchKernelGGL(k_gather_count, dim3(nblk(n)), dim3(128), 0, s, m, src, n, c);
     return hipGetLastError();
 }
-hipError_t launch_gather_write(const MolView& m, const uint32_t* src, uint64_t n, const uint64_t* ivl_off, const uint64_t* mod_off, const uint64_t* id_off,
-                               const MolOut& o, hipStream_t s) {
+hipError_t launch_gather_write(const MolView& m, const uint32_t* src, uint64_t n, const MolOffsets& f, const MolOut& o, hipStream_t s) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(k_gather_write, dim3(nblk(n)), dim3(128), 0, s, m, src, n, ivl_off, mod_off, id_off, o);
+    hipLaunchKernelGGL(k_gather_write, dim3(nblk(n)), dim3(128), 0, s, m, src, n, f, o);
     return hipGetLastError();
 }
 
@@ -1433,15 +1429,15 @@ hipError_t launch_mut_resolve(const BatchView& b, const MutView& v, uint32_t* li
     hipLaunchKernelGGL(k_mut_resolve, dim3(nblk(n)), dim3(128), 0, s, b, v, lit_ctg, out_lits, lit_base, pool_base);
     return hipGetLastError();
 }
-hipError_t launch_mut_count(const MolView& m, const MutView& v, const uint32_t* lit_ctg, uint64_t* n_ivls, uint64_t* n_mods, uint64_t* n_idlen, hipStream_t s) {
+hipError_t launch_mut_count(const MolView& m, const MutView& v, const uint32_t* lit_ctg, const MolCounts& c, hipStream_t s) {
     if (!m.B.n_reads) return hipSuccess;
-    hipLaunchKernelGGL(k_mut_count, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, v, lit_ctg, n_ivls, n_mods, n_idlen);
+    hipLaunchKernelGGL(k_mut_count, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, v, lit_ctg, c);
     return hipGetLastError();
 }
-hipError_t launch_mut_write(const MolView& m, const MutView& v, const uint32_t* lit_ctg, uint32_t lit_base, const uint64_t* ivl_off, const uint64_t* mod_off,
-                            const uint64_t* id_off, const MolOut& o, hipStream_t s) {
+hipError_t launch_mut_write(const MolView& m, const MutView& v, const uint32_t* lit_ctg, uint32_t lit_base, const MolOffsets& f, const MolOut& o,
+                            hipStream_t s) {
     if (!m.B.n_reads) return hipSuccess;
-    hipLaunchKernelGGL(k_mut_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, v, lit_ctg, lit_base, ivl_off, mod_off, id_off, o);
+    hipLaunchKernelGGL(k_mut_write, dim3(nblk(m.B.n_reads)), dim3(128), 0, s, m, v, lit_ctg, lit_base, f, o);
     return hipGetLastError();
 }
 
@@ -1496,16 +1492,15 @@ hipError_t launch_noise_fill(uint64_t n, uint64_t n_blocks, const NoiseParams& p
     return hipGetLastError();
 }
 // one wave per molecule: 4 molecules per block of 256
-hipError_t launch_pal_count(const MolView& m, const NoiseParams& p, uint64_t first_index, const uint4* plan, uint64_t* n_ivls, uint64_t* n_mods,
-                            hipStream_t s) {
+hipError_t launch_pal_count(const MolView& m, const NoiseParams& p, uint64_t first_index, const uint4* plan, const MolCounts& c, hipStream_t s) {
     if (!m.B.n_reads) return hipSuccess;
-    hipLaunchKernelGGL(k_pal_count, dim3((unsigned)((m.B.n_reads + 3) / 4)), dim3(256), 0, s, m, p, first_index, plan, n_ivls, n_mods);
+    hipLaunchKernelGGL(k_pal_count, dim3((unsigned)((m.B.n_reads + 3) / 4)), dim3(256), 0, s, m, p, first_index, plan, c);
     return hipGetLastError();
 }
-hipError_t launch_pal_write(const MolView& m, const NoiseParams& p, uint64_t first_index, const uint4* plan, const uint64_t* ivl_off,
-                            const uint64_t* mod_off, const MolOut& o, hipStream_t s) {
+hipError_t launch_pal_write(const MolView& m, const NoiseParams& p, uint64_t first_index, const uint4* plan, const MolOffsets& f, const MolOut& o,
+                            hipStream_t s) {
     if (!m.B.n_reads) return hipSuccess;
-    hipLaunchKernelGGL(k_pal_write, dim3((unsigned)((m.B.n_reads + 3) / 4)), dim3(256), 0, s, m, p, first_index, plan, ivl_off, mod_off, o);
+    hipLaunchKernelGGL(k_pal_write, dim3((unsigned)((m.B.n_reads + 3) / 4)), dim3(256), 0, s, m, p, first_index, plan, f, o);
     return hipGetLastError();
 }
 

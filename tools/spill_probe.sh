@@ -19,7 +19,7 @@ if [ "$1" = build ]; then
   for v in w5 w5noasm v96 r64w4; do
     X=""; [ $v = w5noasm ] && X="-DTKSM_NO_INLINE_ASM"; [ $v = v96 ] && X="-DTKSM_ALNF_NUM_VGPR=96"
     /opt/rocm/bin/hipcc $F $X -c $C/_spill/kernels_$v.hip -o $C/_spill/kernels_$v.o 2>&1 | grep -v "warning\|^ \|^$" || true
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $R/tksm_amd/libtksmseq_spill_$v.so $C/_spill/kernels_$v.o $C/_build/mdf_kernels.o $C/_build/api.o $C/_build/mdf_ops.o \
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $R/tksm_amd/libtksmseq_spill_$v.so $C/_spill/kernels_$v.o $C/_build/mdf_kernels.o $C/_build/api.o $C/_build/mdf_ops.o $C/_build/mdf_move.o $C/_build/mdf_make.o $C/_build/mdf_text.o \
         $C/_build/models.o $C/_build/hostio.o $C/_build/sequencer_module.o $C/_build/mdf_modules.o -lz -ldl
   done
   python3 - <<PY
