@@ -835,6 +835,84 @@ void tksmseq_abundance_free(tksmseq_abundance_result* r);
  * ("abundance: error: ..."), 1 for everything that fails later.  Stdout: the reference's progress lines and "Parsed alignments for N reads". */
 int tksmseq_abundance_main(int argc, char** argv);
 
+/* ---- model-sequence: Badread error and q-score models built on the device --------------------------------------------------------------------
+ * Replaces `badread error_model` + `badread qscore_model` (the model_sequence rule, Snakefile:507-546): the two files that
+ * tksmseq_load_error_model / tksmseq_load_qscore_model read.  Badread's source is not part of the reference tree: the FILE FORMATS are the
+ * reference's (the loaders py/tksm_badread.py:91-117 and :546-582, the window use :584-655, the shipped files), the COUNTING RULES below
+ * are this build's own ("model-sequence").
+ *
+ * Inputs.  The context's reference (upper-cased).  reads_paths: a comma list of FASTQ files, plain or .gz; four lines per record, the name is
+ * the header up to the first white space, bases upper-cased, quality = char - 33 in [0, 93].  paf_path: a PAF with cg:Z: tags; columns
+ * 1, 2, 3, 4, 5, 6, 8, 9 (1-based) and the tags tp:A: and cg:Z: are read.
+ *
+ * Lines, in file order.  SKIPPED (one counter each): no cg:Z: tag; tp:A:S; a read name that is in no FASTQ file; a target that is not in
+ * the reference; a CIGAR with an op outside M = X I D.  TKSMSEQ_EINVAL ("PAF line N: ..."): fewer than 12 columns; a used column that is
+ * no integer in [0, 2^31); start > end or end > length (the target's length is the reference contig's); column 2 differs from the FASTQ
+ * read's length; a CIGAR that does not consume exactly qend - qstart read bases and tend - tstart reference bases.  max_alignments N > 0
+ * stops after N USED lines.  Strand '-': the read is reverse-complemented and its qualities reversed; the aligned part is then
+ * [qlen - qend, qlen - qstart) of that.
+ *
+ * Columns.  The CIGAR expands to alignment columns: an M, = or X column is '=' if both bytes are equal and in ACGT, else 'X'; 'I' a read
+ * base without a reference base, 'D' a reference base without a read base.
+ *
+ * Error model (error_k K in [3, 8], max_alt in [0, 31]).  Every reference offset t, tstart <= t, t + K <= tend, with c0 / c1 the columns of
+ * reference bases t / t + K - 1, COUNTS when all K reference bases are in ACGT, columns c0 and c1 are '=' and every read base in columns
+ * c0..c1 is in ACGT.  Its alternative is the read's bases in c0..c1.  total[kmer] += 1; an alternative of at most K + 4 bases also does
+ * count[kmer][alt] += 1 (longer ones stay in the total: the residual).  The file: one line per k-mer, all 4^K in ACGT order,
+ * "KMER,p;ALT,p;...;\n": the k-mer itself first (also with count 0), then the up to max_alt other alternatives by count descending, length
+ * ascending, bytes ascending; p = count / total as a double, "%.6f"; a k-mer with total 0: "KMER,1.000000;".
+ *
+ * Q-score model (qscore_k Kq odd in [1, 29]).  Every read position i of the aligned part (n = qend - qstart) and every half-width
+ * h = 0 .. (Kq - 1) / 2 with i - h >= 0 and i + h <= n - 1: the key is the column letters from the column of read position i - h to that of
+ * i + h.  A key with a run of more than max_del 'D's is not counted (windows_max_del); otherwise one longer than 29 letters is not counted
+ * (keys_too_long); otherwise count[key][q_i] += 1.  overall[q_i] += 1 once per read position.  The file: "overall;N;q:p,...,\n", then
+ * the keys with N >= min_occur by N descending, length ascending, bytes ascending, at most max_output of them; '=', 'X' and 'I' are always
+ * among the written keys (each takes the place of the last key of the cut that is not one of the three, or is added when max_output is
+ * below 3); any of the three with count 0: TKSMSEQ_EINVAL naming it.  A line: "KEY;N;q:p,q:p,...,\n", every q with count > 0
+ * ascending, p = count / N as "%.6f" with the trailing zeros removed ("0.0185", "0.").
+ *
+ * On the device: the columns of every alignment (one wave each), one event per reference offset and (Kq + 1) / 2 + 1 per read position,
+ * radix sort + run lengths, per chunk of at most chunk_events events (0: sized from free device memory); the chunks' tables are merged by
+ * concatenate, sort and reduce, so the files are the same bytes for every chunk size and on every run.  All counts are integers; there is
+ * no floating point on the device.  error_out / qscore_out: either may be NULL; gzipped (host zlib) when the name ends in .gz; written
+ * under <path>.tmp and renamed.
+ *
+ * TKSMSEQ_EINVAL also: both outputs NULL, a parameter out of range, a malformed FASTQ record, no used alignment.  TKSMSEQ_EIO: a file
+ * that cannot be read or written.  TKSMSEQ_ELIMIT: 2^31 alignments, 2^31 events or more in one chunk (one alignment), 2^31 distinct keys, an alternative counted 2^32 times. */
+typedef struct tksmseq_model_sequence_params {
+    int32_t error_k;                 /* --error-k (7) */
+    int32_t qscore_k;                /* --qscore-k (9) */
+    int64_t max_alignments;          /* --max_alignments (0: all) */
+    int32_t max_alt;                 /* --max_alt (25) */
+    int32_t max_del;                 /* --max_del (6) */
+    int64_t min_occur;               /* --min_occur (100) */
+    int64_t max_output;              /* --max_output (10000) */
+    uint64_t chunk_events;           /* events per chunk; 0: from free device memory */
+} tksmseq_model_sequence_params;
+typedef struct tksmseq_model_sequence_info {
+    uint64_t lines;                  /* PAF lines read (up to the stop of max_alignments) */
+    uint64_t used;                   /* alignments used */
+    uint64_t skipped_no_cigar, skipped_supplementary, skipped_unknown_read, skipped_unknown_target, skipped_cigar_op;
+    uint64_t counting_positions;     /* error model: the sum of the totals */
+    uint64_t alternatives_too_long;  /* ... of them with an alternative above K + 4 */
+    uint64_t windows_max_del;        /* q-score windows not counted for a 'D' run above max_del */
+    uint64_t keys_too_long;          /* ... for more than 29 letters */
+    uint64_t read_positions;         /* the N of the overall line */
+    uint64_t error_keys, qscore_keys;   /* distinct (k-mer, alternative) / q-score keys counted */
+    uint64_t chunks, events;
+    float device_ms;                 /* by HIP events, all chunks: */
+    float stage_ms[4];               /* columns, events, sort + reduce + merge, select */
+    float reserved;
+    double read_ms, upload_ms, write_ms;   /* host wall time: reading and parsing, uploads, formatting and writing */
+} tksmseq_model_sequence_info;
+int tksmseq_model_sequence(tksmseq_ctx* ctx, const tksmseq_model_sequence_params* params, const char* reads_paths /* comma list */, const char* paf_path,
+                           const char* error_out /* or NULL */, const char* qscore_out /* or NULL */, tksmseq_model_sequence_info* info /* or NULL */);
+/* `tksm model-sequence`: --reference R[,R] --reads F[,F] --alignment PAF [--error-model OUT] [--qscore-model OUT] [--error-k 7] [--qscore-k 9]
+ * [--max_alignments 0] [--max_alt 25] [--max_del 6] [--min_occur 100] [--max_output 10000] [--devices D] [--verbosity V] [--log-file L]; at least
+ * one output.  Exit codes as the other model modules: 2 for a missing required option, an unknown option or a value out of range
+ * ("model-sequence: error: ..."), 1 for everything that fails later. */
+int tksmseq_model_sequence_main(int argc, char** argv);
+
 /* The batch as MDF text, the way molecule_descriptor::operator<< writes it (src/interval.h:898-905): "+id<TAB>depth<TAB>comment",
  * then "chr<TAB>start<TAB>end<TAB>strand<TAB>pos<base>,..." per segment; depth 1 per molecule; comments re-serialised key-sorted
  * like dump_comment (:880-890).  *text is malloc'ed: release with tksmseq_text_free. */

@@ -147,6 +147,19 @@ class AbundanceParams(C.Structure):        # tksmseq_abundance_params
                 ("cb_mu", C.c_double), ("cb_sigma", C.c_double), ("cb_pattern", C.c_char_p), ("cb_txt_path", C.c_char_p), ("lr_br_path", C.c_char_p)]
 
 
+class ModelSequenceParams(C.Structure):    # tksmseq_model_sequence_params
+    _fields_ = [("error_k", C.c_int32), ("qscore_k", C.c_int32), ("max_alignments", C.c_int64), ("max_alt", C.c_int32), ("max_del", C.c_int32),
+                ("min_occur", C.c_int64), ("max_output", C.c_int64), ("chunk_events", C.c_uint64)]
+
+
+class ModelSequenceInfo(C.Structure):      # tksmseq_model_sequence_info
+    _fields_ = [(n, C.c_uint64) for n in ("lines", "used", "skipped_no_cigar", "skipped_supplementary", "skipped_unknown_read", "skipped_unknown_target",
+                                          "skipped_cigar_op", "counting_positions", "alternatives_too_long", "windows_max_del", "keys_too_long",
+                                          "read_positions", "error_keys", "qscore_keys", "chunks", "events")] + \
+               [("device_ms", C.c_float), ("stage_ms", C.c_float * 4), ("reserved", C.c_float), ("read_ms", C.c_double), ("upload_ms", C.c_double),
+                ("write_ms", C.c_double)]
+
+
 ABUND_CHUNK = 1024                           # hits per chunk partial of the abundance sums (abund_kernels.h)
 KDE_CHUNK = 4096                             # samples per partial grid of tksmseq_kde_grid (kde_kernels.h; doubled for large inputs)
 KDE_BANDWIDTHS = tuple(range(50, 1000, 100))
@@ -176,6 +189,7 @@ SYMBOLS = [
     "tksmseq_abundance", "tksmseq_abundance_info", "tksmseq_abundance_row", "tksmseq_abundance_vector", "tksmseq_abundance_transcript",
     "tksmseq_abundance_cell", "tksmseq_abundance_read", "tksmseq_abundance_hits", "tksmseq_abundance_device_ms", "tksmseq_abundance_write",
     "tksmseq_abundance_free", "tksmseq_abundance_main",
+    "tksmseq_model_sequence", "tksmseq_model_sequence_main",
     "tksmseq_filter", "tksmseq_concat", "tksmseq_filter_main",
     "tksmseq_glue", "tksmseq_glue_joins", "tksmseq_shuffle", "tksmseq_unsegment_main", "tksmseq_shuffle_main",
     "tksmseq_variants_load", "tksmseq_variants_info", "tksmseq_variants_free", "tksmseq_mutate", "tksmseq_mutate_main",
@@ -288,6 +302,8 @@ def load():
         "tksmseq_abundance_write": (C.c_int, [vp, C.c_char_p]),
         "tksmseq_abundance_free": (None, [vp]),
         "tksmseq_abundance_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
+        "tksmseq_model_sequence": (C.c_int, [vp, P(ModelSequenceParams), C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, P(ModelSequenceInfo)]),
+        "tksmseq_model_sequence_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
         "tksmseq_filter": (C.c_int, [vp, vp, P(FilterParams), P(vp), P(vp)]),
         "tksmseq_concat": (C.c_int, [vp, P(vp), u64, i32, P(vp)]),
         "tksmseq_filter_main": (C.c_int, [C.c_int, P(C.c_char_p)]),

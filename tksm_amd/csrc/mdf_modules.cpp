@@ -20,6 +20,7 @@
 //   Splicer_module          src/transcribe.cpp:19-218 -g/--gtf, -a/--abundance, --molecule-count, -w/--weights, ... (no fusion submodule): GTF + TSV in, MDF out
 //   model-truncation        py/truncate_kde.py:36-112, :323-352 (behind src/model_truncation.cpp) PAF in, KDE model JSON out: no MDF, one context
 //   abundance               py/transcript_abundance.py:32-139, :326-389 (behind src/abundance.cpp) PAF in, expression TSV out: no MDF, one context
+//   model-sequence          the model_sequence rule (Snakefile:507-546: badread error_model + qscore_model) reference, FASTQ and PAF in, two model files out: no MDF, one context
 //   utility flags           src/module.h:75-104      -s/--seed (default 42), --verbosity, --log-file, -h
 // All stream: `truncate` and the four segment edits read the input in batches of whole molecules (--batch-bytes), `pcr` amplifies its templates in slices
 // of about --slice-molecules output molecules (tksmseq_pcr_params::template_begin / _end); the pieces go round the entries of
@@ -1142,6 +1143,87 @@ extern "C" int tksmseq_abundance_main(int argc, char** argv) {
         tksmseq_abundance_free(res);
     }
     fflush(stdout);
+    tksmseq_destroy(ctx);
+    return rc ? 1 : 0;
+}
+
+// `tksm model-sequence`: the model_sequence rule of the reference's workflow (Snakefile:507-546) runs `badread error_model` and `badread
+// qscore_model`; this module builds both files in one pass (include/tksmseq.h).  Exit codes as the other two model modules: 2 for a missing
+// required option, an unknown option or a value out of range, 1 for everything that fails later.  One context on the first entry of --devices.
+extern "C" int tksmseq_model_sequence_main(int argc, char** argv) {
+    Common c;
+    tksmseq_model_sequence_params p{};
+    p.error_k = 7; p.qscore_k = 9; p.max_alt = 25; p.max_del = 6; p.min_occur = 100; p.max_output = 10000;
+    std::string reference, reads, paf, error_out, qscore_out;
+    std::string range_error;
+    auto integer = [](const char* v, long long& out) { char* e = nullptr; out = strtoll(v, &e, 10); return e != v && !*e; };
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            // (the common flags know -i, -o, -s, --batch-bytes and --slice-molecules, which this module does not have)
+            if (o == "-i" || o == "--input" || o == "-o" || o == "--output" || o == "-s" || o == "--seed" || o == "--batch-bytes" || o == "--slice-molecules") return NO_SUCH;
+            long long iv = 0;
+            auto ranged = [&](long long lo, long long hi, const char* what) {
+                if (!integer(v, iv)) return false;
+                if ((iv < lo || iv > hi) && range_error.empty()) range_error = o + " " + what;
+                return true;
+            };
+            if ((o == "-r" || o == "--reference") && v) reference = v;
+            else if (o == "--reads" && v) reads = v;
+            else if (o == "--alignment" && v) paf = v;
+            else if (o == "--error-model" && v) error_out = v;
+            else if (o == "--qscore-model" && v) qscore_out = v;
+            else if (o == "--error-k" && v) { if (!ranged(3, 8, "must be between 3 and 8")) return MALFORMED; p.error_k = (int32_t)std::max(-1ll, std::min(iv, 99ll)); }
+            else if (o == "--qscore-k" && v) {
+                if (!ranged(1, 29, "must be odd and between 1 and 29")) return MALFORMED;
+                if (iv % 2 == 0 && range_error.empty()) range_error = o + " must be odd and between 1 and 29";
+                p.qscore_k = (int32_t)std::max(-1ll, std::min(iv, 99ll));
+            }
+            else if (o == "--max_alignments" && v) { if (!ranged(0, 0x7FFFFFFFFFFFFFFFll, "must not be negative")) return MALFORMED; p.max_alignments = iv; }
+            else if (o == "--max_alt" && v) { if (!ranged(0, 31, "must be between 0 and 31")) return MALFORMED; p.max_alt = (int32_t)std::max(-1ll, std::min(iv, 99ll)); }
+            else if (o == "--max_del" && v) { if (!ranged(0, 1 << 20, "must be between 0 and 1048576")) return MALFORMED; p.max_del = (int32_t)std::max(-1ll, std::min(iv, 1ll << 20)); }
+            else if (o == "--min_occur" && v) { if (!ranged(0, 0x7FFFFFFFFFFFFFFFll, "must not be negative")) return MALFORMED; p.min_occur = iv; }
+            else if (o == "--max_output" && v) { if (!ranged(0, 0x7FFFFFFEll, "must be between 0 and 2147483646")) return MALFORMED; p.max_output = iv; }
+            else return NOT_MINE;
+            return TOOK_VALUE;
+        })) return 2;
+    if (c.help) { printf("Builds the Badread error model and q-score model of `tksm sequence` from reads aligned to a reference.\n"
+                         "usage: model-sequence --reference R[,R] --reads F[,F] --alignment PAF [--error-model OUT] [--qscore-model OUT] [--error-k 7] [--qscore-k 9]\n"
+                         "                      [--max_alignments 0] [--max_alt 25] [--max_del 6] [--min_occur 100] [--max_output 10000] [--devices D] [--verbosity V]\n"
+                         "                      [--log-file L]\n"
+                         "PAF: minimap2 -c output (cg:Z: tags); FASTQ and model files may be .gz; at least one of --error-model, --qscore-model\n"); return 0; }
+    std::string missing;
+    for (const auto& need : {std::make_pair(&reference, "--reference"), std::make_pair(&reads, "--reads"), std::make_pair(&paf, "--alignment")})
+        if (need.first->empty()) missing += (missing.empty() ? "" : ", ") + std::string(need.second);
+    if (!missing.empty()) { fprintf(stderr, "model-sequence: error: the following arguments are required: %s\n", missing.c_str()); return 2; }
+    if (error_out.empty() && qscore_out.empty()) { fprintf(stderr, "model-sequence: error: at least one of --error-model and --qscore-model is required\n"); return 2; }
+    if (!range_error.empty()) { fprintf(stderr, "model-sequence: error: %s\n", range_error.c_str()); return 2; }
+    Logger log;
+    if (!open_log(c, "model-sequence", log)) return 1;
+    tksmseq_ctx* ctx = nullptr;
+    if (tksmseq_create(c.devices[0], &ctx)) { fprintf(stderr, "Error: %s\n", tksmseq_last_error(nullptr)); return 1; }
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = 0;
+    for (size_t a = 0; a <= reference.size() && !rc;) {
+        size_t b = reference.find(',', a);
+        if (b == std::string::npos) b = reference.size();
+        if (b > a) {
+            log.log(Logger::INFO, "Reading %s", reference.substr(a, b - a).c_str());
+            rc = tksmseq_reference_add_fasta(ctx, reference.substr(a, b - a).c_str());
+        }
+        a = b + 1;
+    }
+    tksmseq_model_sequence_info info{};
+    if (!rc) rc = tksmseq_model_sequence(ctx, &p, reads.c_str(), paf.c_str(), error_out.empty() ? nullptr : error_out.c_str(), qscore_out.empty() ? nullptr : qscore_out.c_str(), &info);
+    if (rc) fprintf(stderr, "Error: %s\n", tksmseq_last_error(ctx));
+    else {
+        log.log(Logger::INFO, "model-sequence: %llu PAF lines, %llu used (skipped: %llu without cg:Z:, %llu tp:A:S, %llu unknown reads, %llu unknown targets, %llu other CIGAR ops)",
+                (unsigned long long)info.lines, (unsigned long long)info.used, (unsigned long long)info.skipped_no_cigar, (unsigned long long)info.skipped_supplementary,
+                (unsigned long long)info.skipped_unknown_read, (unsigned long long)info.skipped_unknown_target, (unsigned long long)info.skipped_cigar_op);
+        log.log(Logger::INFO, "model-sequence: %llu counting positions (%llu alternatives too long), %llu read positions (%llu windows over --max_del, %llu keys too long), "
+                "%llu + %llu distinct keys", (unsigned long long)info.counting_positions, (unsigned long long)info.alternatives_too_long, (unsigned long long)info.read_positions,
+                (unsigned long long)info.windows_max_del, (unsigned long long)info.keys_too_long, (unsigned long long)info.error_keys, (unsigned long long)info.qscore_keys);
+        log.log(Logger::INFO, "model-sequence: %llu events in %llu chunks, written in %.2f s (device %.2f ms)", (unsigned long long)info.events,
+                (unsigned long long)info.chunks, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), info.device_ms);
+    }
     tksmseq_destroy(ctx);
     return rc ? 1 : 0;
 }

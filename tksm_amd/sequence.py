@@ -571,6 +571,23 @@ class Sequencer:
         finally:
             self._lib.tksmseq_abundance_free(h)
 
+    # ---- model-sequence: Badread error and q-score models built on the device
+    def model_sequence(self, reads, alignment, error_out=None, qscore_out=None, error_k=7, qscore_k=9, max_alignments=0, max_alt=25, max_del=6,
+                       min_occur=100, max_output=10000, chunk_events=0):
+        """`badread error_model` + `badread qscore_model` on the device (tksmseq_model_sequence, the rules in include/tksmseq.h): `reads` (one
+        FASTQ path or a list of them, .gz or plain) aligned to the context's reference in `alignment` (a PAF with cg:Z: tags) -> the files
+        load_error_model / load_qscore_model read; either output may be None.  Returns the counters of tksmseq_model_sequence_info as a dict."""
+        if not isinstance(reads, (list, tuple)):
+            reads = [reads]
+        p = L.ModelSequenceParams(int(error_k), int(qscore_k), int(max_alignments), int(max_alt), int(max_del), int(min_occur), int(max_output), int(chunk_events))
+        info = L.ModelSequenceInfo()
+        self._chk(self._lib.tksmseq_model_sequence(self._ctx, C.byref(p), ",".join(str(r) for r in reads).encode(), str(alignment).encode(),
+                                                   str(error_out).encode() if error_out else None, str(qscore_out).encode() if qscore_out else None,
+                                                   C.byref(info)))
+        out = {n: getattr(info, n) for n, _ in L.ModelSequenceInfo._fields_ if n not in ("stage_ms", "reserved")}
+        out["stage_ms"] = list(info.stage_ms)
+        return out
+
     # ---- random-wgs: whole-genome fragments made on the device
     def wgs(self, dist, a, b=0, base_count=None, depth=None, seed=42, first_candidate=0, n_candidates=1 << 20, state=None):
         """The loop of RWGS_module::run (src/random_wgs.cpp:181-207) for candidates [first_candidate, first_candidate + n_candidates)
