@@ -42,6 +42,11 @@
  *                          no cap).  Which rounds align at full width does not change, so a round with more jobs than rows leaves waves without
  *                          rows: their jobs are counted as fall-backs (reason bit 0x02) and their reads finish in the exact kernel
  *   TKSMSEQ_FULL_POOL_MB=M memory for the unbanded alignment fallback of the wave-wide kernel (default 1024)
+ *   TKSMSEQ_POISON=W       diagnostic: W a 32-bit word in hex (1 - 8 digits).  Every device block and page-locked buffer the library's allocator
+ *                          hands out, fresh or recycled, is filled with W first (a grown buffer: behind the bytes it keeps), each fill
+ *                          waited for, and every context prints `poison W: <blocks> blocks, <bytes> bytes` on stderr as it is destroyed: what
+ *                          the process has filled since the line before.  The same bytes must come out whatever W is
+ *                          (tests/test_history_gpu.py).  Read once per process, at the first allocation
  *   TKSMSEQ_STATS_FILE=P   (CLI) `tksm sequence` writes one JSON object with the run's stage clocks to P: reads, batches, MDF bytes in, record
  *                          bytes out, seconds of set-up (devices, references, models), of streaming (first chunk read -> last record byte
  *                          written) and, summed over the threads of a stage, of parsing, running, device-side staging copies, waiting for

@@ -5,6 +5,8 @@
 #include <chrono>
 
 #include <algorithm>
+#include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <map>
 #include <memory>
@@ -84,6 +86,63 @@ struct DevCache {
     }
 };
 
+// ---- TKSMSEQ_POISON=<32-bit word, hex> (diagnostic; read once per process): every block that DevBuf::ensure or PinnedBuf::ensure hands out
+// is filled with that word first, so that a result which depends on what a recycled block held changes with the word
+// (tests/test_history_gpu.py runs the same calls unset, with 00000000 and with 00000001 and compares the bytes).  The counters are per
+// process; every context prints what was filled since the line before as it goes (report(), from ~tksmseq_ctx).  Hidden: the library
+// exports what it exported before.
+struct __attribute__((visibility("hidden"))) Poison {
+    bool on = false;
+    uint32_t word = 0;
+    std::mutex m;
+    uint64_t blocks = 0, bytes = 0, shown_blocks = 0, shown_bytes = 0;
+    // 1 to 8 hex digits (a leading 0x is allowed), nothing else
+    static bool parse(const char* s, uint32_t* word) {
+        if (!s) return false;
+        if (s[0] == '0' && (s[1] == 'x' || s[1] == 'X')) s += 2;
+        uint32_t v = 0;
+        int n = 0;
+        for (; *s; s++, n++) {
+            const int d = *s >= '0' && *s <= '9' ? *s - '0' : *s >= 'a' && *s <= 'f' ? *s - 'a' + 10 : *s >= 'A' && *s <= 'F' ? *s - 'A' + 10 : -1;
+            if (d < 0 || n == 8) return false;
+            v = v << 4 | (uint32_t)d;
+        }
+        if (!n) return false;
+        *word = v;
+        return true;
+    }
+    // the bytes [lo, hi) of a new block of ncap bytes to fill: all of it, or with `keep` what lies behind the min(old cap, ncap) bytes
+    // copied from the old block; whole words (every capacity here is a multiple of 256)
+    static void range(size_t old_cap, size_t ncap, bool kept, size_t* lo, size_t* hi) {
+        *hi = ncap & ~(size_t)3;
+        *lo = std::min(kept ? (std::min(old_cap, ncap) + 3) & ~(size_t)3 : 0, *hi);
+    }
+    Poison() {
+        const char* e = getenv("TKSMSEQ_POISON");
+        on = parse(e, &word);
+        if (e && !on) fprintf(stderr, "TKSMSEQ_POISON=%s is not a 32-bit hex word: ignored\n", e);
+    }
+    static Poison& get() { static Poison p; return p; }
+    void filled(size_t n) { std::lock_guard<std::mutex> l(m); blocks++; bytes += n; }
+    // on the null stream, and waited for: the contexts' streams are non-blocking, so nothing else orders the fill against them; a
+    // block that ensure() hands out has no other user (DevCache receives drained blocks only)
+    hipError_t fill_device(void* p, size_t lo, size_t hi) {
+        if (hi > lo) {
+            hipError_t e = hipMemsetD32Async((hipDeviceptr_t)((char*)p + lo), (int)word, (hi - lo) / 4, nullptr);
+            if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+            if (e != hipSuccess) return e;
+        }
+        filled(hi - lo);
+        return hipSuccess;
+    }
+    void fill_host(void* p, size_t bytes) { std::fill_n((uint32_t*)p, bytes / 4, word); filled(bytes & ~(size_t)3); }
+    void report() {
+        std::lock_guard<std::mutex> l(m);
+        fprintf(stderr, "poison %08x: %llu blocks, %llu bytes\n", word, (unsigned long long)(blocks - shown_blocks), (unsigned long long)(bytes - shown_bytes));
+        shown_blocks = blocks; shown_bytes = bytes;
+    }
+};
+
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
@@ -130,11 +189,18 @@ struct DevBuf {
             alloc_calls()++;
             if (e != hipSuccess) return e;
         }
-        if (keep && p && cap) {
-            hipError_t e = hipMemcpyAsync(np, p, std::min(cap, ncap), hipMemcpyDeviceToDevice, s);
+        hipError_t e = hipSuccess;
+        const bool kept = keep && p && cap;
+        if (kept) {
+            e = hipMemcpyAsync(np, p, std::min(cap, ncap), hipMemcpyDeviceToDevice, s);
             if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) { if (pooled) DevCache::get().give(ndev, np, ncap); else (void)hipFree(np); return e; }
         }
+        if (e == hipSuccess && Poison::get().on) {           // (TKSMSEQ_POISON: what the caller has not been given to keep)
+            size_t lo, hi;
+            Poison::range(cap, ncap, kept, &lo, &hi);
+            e = Poison::get().fill_device(np, lo, hi);
+        }
+        if (e != hipSuccess) { if (pooled) DevCache::get().give(ndev, np, ncap); else (void)hipFree(np); return e; }
         const bool was_owned = owned;
         if (was_owned) release(); else { p = nullptr; cap = 0; }
         p = np; cap = ncap; owned = true; dev = ndev;
@@ -158,6 +224,7 @@ struct PinnedBuf {
         const hipError_t e = hipHostMalloc(&p, bytes * 2, hipHostMallocDefault);
         if (e != hipSuccess) { p = nullptr; return e; }
         cap = bytes * 2;
+        if (Poison::get().on) Poison::get().fill_host(p, cap);
         return hipSuccess;
     }
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
@@ -308,6 +375,7 @@ struct tksmseq_ctx : ContigLookup {
         auto it = contig_index.find(name);
         return it == contig_index.end() ? -1 : it->second;
     }
+    ~tksmseq_ctx() { if (Poison::get().on) Poison::get().report(); }
 };
 
 // the permutation that orders n keys (stable; sort: abund_sort_u32 / abund_sort_u64 over bits [0, end_bit)), and the sorted keys; queued on
