@@ -918,6 +918,83 @@ int tksmseq_model_sequence(tksmseq_ctx* ctx, const tksmseq_model_sequence_params
  * ("model-sequence: error: ..."), 1 for everything that fails later. */
 int tksmseq_model_sequence_main(int argc, char** argv);
 
+/* ---- barcode-match: long reads to cell barcodes on the device ---------------------------------------------------------------------------------
+ * Replaces the three scTagger rules of the reference's single-cell route (scTagger_lr_seg, scTagger_extract_bc, scTagger_match: Snakefile,
+ * "Preprocessing rules"): FASTQ reads and a barcode whitelist in, the lr_matches.tsv file that `abundance --lr-br` reads out.  scTagger's
+ * source is not part of the reference tree: the FILE FORMAT is the consumer's (parse_lr_bc_matches, py/transcript_abundance.py:166-180: five
+ * columns, columns 1, 3 and 5 used, a read kept only when column 3 is "1"), the RULES below are this build's own, and so are the defaults
+ * (choices, not measurements of anything).  These are not scTagger's rules ("barcode-match").
+ *
+ * Inputs.  reads_paths: a comma list of FASTQ files, plain or .gz, read like model-sequence's (the name is the header up to the first white
+ * space, bases upper-cased; a name may occur once over all files).  whitelist_path: one barcode per line, plain or .gz, empty lines skipped;
+ * every barcode has the same length L in [4, 32] and letters in ACGT only; two lines with the same spelling: TKSMSEQ_EINVAL naming both.
+ * adapter: 4 to 32 letters of ACGT.  window >= the adapter's length, pad in [0, 16], max_adapter_errors < the adapter's length,
+ * max_errors < L, min_exact >= 0.  A byte of a read outside ACGT matches nothing and its complement is itself.  With revcomp_barcodes the
+ * spelling that is MATCHED is the reverse complement of the file's; the spelling that is PRINTED is always the file's.
+ *
+ * Infix distance.  d(P, T) = the minimum Levenshtein distance of P to any substring of T, the empty one included; its end e(P, T) = the
+ * smallest number of consumed letters of T at which that minimum is reached: the (|P| + 1) x (|T| + 1) table with row 0 all zeros and
+ * column 0 = i, d = the minimum of the last row, e = its first column.
+ *
+ * Adapter.  For orientation o = 0 (the read) and 1 (its reverse complement), T_o the oriented read: (da_o, ja_o) = (d, e) of the adapter in
+ * the first min(window, length) letters of T_o.  The smaller da wins, o = 0 wins a tie.  Winning da > max_adapter_errors: the read counts as
+ * no_adapter and appears in no output.
+ *
+ * Segment.  seg = T_o[max(0, ja - pad) : min(length, ja + L + pad)], bounds in the whole oriented read: at most L + 2 pad <= 64 letters.
+ *
+ * Selection.  Every window of L letters of every segment that is all ACGT and spells a whitelist barcode (matched spelling) adds 1 to
+ * exact[b]; every window counts, also twice in one segment.  The candidates: the barcodes with exact[b] >= min_exact, in whitelist order
+ * (min_exact 0: the whole whitelist).
+ *
+ * Match.  For every segment and every candidate b: d(matched spelling of b, seg); dmin = the minimum over the candidates.  No candidate, or
+ * dmin > max_errors: the read counts as no_barcode and gets no line.  Otherwise one line of matches_out, the reads in input order:
+ *     RID <TAB> dmin <TAB> COUNT <TAB> da <TAB> BC[,BC...] <NL>
+ * COUNT = the number of candidates at dmin; the list holds the first min(COUNT, 8) of them in whitelist order.
+ * segments_out (or NULL): RID <TAB> da <TAB> +|- <TAB> start <TAB> SEGMENT for every read with an adapter (start: the segment's first letter
+ * in the oriented read).  selected_out (or NULL): BARCODE <TAB> exact, one line per candidate.  Files are written under <path>.tmp and renamed,
+ * gzipped (host zlib) when the name ends in .gz.
+ *
+ * On the device: at most window + L + pad letters of each end of a read are uploaded, 2 bits a letter and a validity bit; the adapter is
+ * aligned by the bit-parallel column step of Myers (1999) in one 32-bit word, one lane per read and orientation; the whitelist's 64-bit keys
+ * are sorted once and every segment window is looked up by binary search, counted with integer atomics; every segment is aligned to every
+ * candidate, the barcode as the pattern in one 32-bit word.  Reads go in chunks of chunk_reads (0: sized from free device memory); selection
+ * sees all chunks before any match starts; the outputs are the same bytes for every chunk size and on every run.  No floating point.
+ *
+ * TKSMSEQ_EINVAL: a parameter out of range, a malformed FASTQ or whitelist, no reads.  TKSMSEQ_EIO: a file that cannot be read or written.
+ * TKSMSEQ_ELIMIT: 2^31 reads or 2^27 whitelist lines, or more. */
+typedef struct tksmseq_barcode_match_params {
+    const char* adapter;             /* --adapter (NULL: CTACACGACGCTCTTCCGATCT) */
+    int32_t window;                  /* --window (200) */
+    int32_t max_adapter_errors;      /* --max-adapter-errors (5) */
+    int32_t pad;                     /* --pad (4) */
+    int32_t max_errors;              /* --max-errors (2) */
+    int64_t min_exact;               /* --min-exact (2) */
+    int32_t revcomp_barcodes;        /* --revcomp-barcodes */
+    int32_t reserved;
+    uint64_t chunk_reads;            /* reads per chunk; 0: from free device memory */
+    const char* segments_out;        /* --segments-out, or NULL */
+    const char* selected_out;        /* --selected-out, or NULL */
+} tksmseq_barcode_match_params;
+typedef struct tksmseq_barcode_match_info {
+    uint64_t reads;
+    uint64_t no_adapter, forward, reverse;     /* reads = no_adapter + forward + reverse (the winning orientation) */
+    uint64_t whitelist, candidates;
+    uint64_t no_barcode, unique, ambiguous;    /* forward + reverse = no_barcode + unique (COUNT = 1) + ambiguous */
+    uint64_t pairs;                  /* (segment, candidate) pairs compared */
+    uint64_t chunks;
+    float device_ms;                 /* by HIP events, all chunks: */
+    float stage_ms[4];               /* adapter, selection, match, gather */
+    float reserved;
+    double read_ms, upload_ms, write_ms;   /* host wall time: reading and parsing, packing and uploads, formatting and writing */
+} tksmseq_barcode_match_info;
+int tksmseq_barcode_match(tksmseq_ctx* ctx, const tksmseq_barcode_match_params* params, const char* reads_paths /* comma list */, const char* whitelist_path,
+                          const char* matches_out, tksmseq_barcode_match_info* info /* or NULL */);
+/* `tksm barcode-match`: --reads F[,F] --whitelist W -o LR_MATCHES.tsv[.gz] [--adapter A] [--window 200] [--max-adapter-errors 5] [--pad 4] [--max-errors 2]
+ * [--min-exact 2] [--revcomp-barcodes] [--segments-out F] [--selected-out F] [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L].  Exit codes
+ * as the other model modules: 2 for a missing required option, an unknown option or a value out of range ("barcode-match: error: ..."), checked
+ * before any device is opened; 1 for everything that fails later. */
+int tksmseq_barcode_match_main(int argc, char** argv);
+
 /* The batch as MDF text, the way molecule_descriptor::operator<< writes it (src/interval.h:898-905): "+id<TAB>depth<TAB>comment",
  * then "chr<TAB>start<TAB>end<TAB>strand<TAB>pos<base>,..." per segment; depth 1 per molecule; comments re-serialised key-sorted
  * like dump_comment (:880-890).  *text is malloc'ed: release with tksmseq_text_free. */

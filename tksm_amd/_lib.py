@@ -160,7 +160,23 @@ class ModelSequenceInfo(C.Structure):      # tksmseq_model_sequence_info
                 ("write_ms", C.c_double)]
 
 
-ABUND_CHUNK = 1024                           # hits per chunk partial of the abundance sums (abund_kernels.h)
+class BarcodeMatchParams(C.Structure):     # tksmseq_barcode_match_params
+    _fields_ = [("adapter", C.c_char_p), ("window", C.c_int32), ("max_adapter_errors", C.c_int32), ("pad", C.c_int32), ("max_errors", C.c_int32),
+                ("min_exact", C.c_int64), ("revcomp_barcodes", C.c_int32), ("reserved", C.c_int32), ("chunk_reads", C.c_uint64),
+                ("segments_out", C.c_char_p), ("selected_out", C.c_char_p)]
+
+
+class BarcodeMatchInfo(C.Structure):       # tksmseq_barcode_match_info
+    _fields_ = [(n, C.c_uint64) for n in ("reads", "no_adapter", "forward", "reverse", "whitelist", "candidates", "no_barcode", "unique", "ambiguous",
+                                          "pairs", "chunks")] + \
+               [("device_ms", C.c_float), ("stage_ms", C.c_float * 4), ("reserved", C.c_float), ("read_ms", C.c_double), ("upload_ms", C.c_double),
+                ("write_ms", C.c_double)]
+
+
+BM_CAND_TILE = 256                           # candidates per workgroup row of the barcode match: a multiple of this (bm_kernels.h)
+BM_TARGET_WAVES = 2048                       # ... split until about this many waves (bm_kernels.h)
+BM_LIST = 8                                  # barcodes listed per read
+ABUND_CHUNK = 1024                     # hits per chunk partial of the abundance sums (abund_kernels.h)
 KDE_CHUNK = 4096                             # samples per partial grid of tksmseq_kde_grid (kde_kernels.h; doubled for large inputs)
 KDE_BANDWIDTHS = tuple(range(50, 1000, 100))
 
@@ -190,6 +206,7 @@ SYMBOLS = [
     "tksmseq_abundance_cell", "tksmseq_abundance_read", "tksmseq_abundance_hits", "tksmseq_abundance_device_ms", "tksmseq_abundance_write",
     "tksmseq_abundance_free", "tksmseq_abundance_main",
     "tksmseq_model_sequence", "tksmseq_model_sequence_main",
+    "tksmseq_barcode_match", "tksmseq_barcode_match_main",
     "tksmseq_filter", "tksmseq_concat", "tksmseq_filter_main",
     "tksmseq_glue", "tksmseq_glue_joins", "tksmseq_shuffle", "tksmseq_unsegment_main", "tksmseq_shuffle_main",
     "tksmseq_variants_load", "tksmseq_variants_info", "tksmseq_variants_free", "tksmseq_mutate", "tksmseq_mutate_main",
@@ -304,6 +321,8 @@ def load():
         "tksmseq_abundance_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
         "tksmseq_model_sequence": (C.c_int, [vp, P(ModelSequenceParams), C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, P(ModelSequenceInfo)]),
         "tksmseq_model_sequence_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
+        "tksmseq_barcode_match": (C.c_int, [vp, P(BarcodeMatchParams), C.c_char_p, C.c_char_p, C.c_char_p, P(BarcodeMatchInfo)]),
+        "tksmseq_barcode_match_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
         "tksmseq_filter": (C.c_int, [vp, vp, P(FilterParams), P(vp), P(vp)]),
         "tksmseq_concat": (C.c_int, [vp, P(vp), u64, i32, P(vp)]),
         "tksmseq_filter_main": (C.c_int, [C.c_int, P(C.c_char_p)]),

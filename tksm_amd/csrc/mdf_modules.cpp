@@ -21,6 +21,7 @@
 //   model-truncation        py/truncate_kde.py:36-112, :323-352 (behind src/model_truncation.cpp) PAF in, KDE model JSON out: no MDF, one context
 //   abundance               py/transcript_abundance.py:32-139, :326-389 (behind src/abundance.cpp) PAF in, expression TSV out: no MDF, one context
 //   model-sequence          the model_sequence rule (Snakefile:507-546: badread error_model + qscore_model) reference, FASTQ and PAF in, two model files out: no MDF, one context
+//   barcode-match           the three scTagger rules (Snakefile, "Preprocessing rules") FASTQ and whitelist in, lr_matches.tsv out: no MDF, one context
 //   utility flags           src/module.h:75-104      -s/--seed (default 42), --verbosity, --log-file, -h
 // All stream: `truncate` and the four segment edits read the input in batches of whole molecules (--batch-bytes), `pcr` amplifies its templates in slices
 // of about --slice-molecules output molecules (tksmseq_pcr_params::template_begin / _end); the pieces go round the entries of
@@ -1223,6 +1224,82 @@ extern "C" int tksmseq_model_sequence_main(int argc, char** argv) {
                 (unsigned long long)info.windows_max_del, (unsigned long long)info.keys_too_long, (unsigned long long)info.error_keys, (unsigned long long)info.qscore_keys);
         log.log(Logger::INFO, "model-sequence: %llu events in %llu chunks, written in %.2f s (device %.2f ms)", (unsigned long long)info.events,
                 (unsigned long long)info.chunks, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), info.device_ms);
+    }
+    tksmseq_destroy(ctx);
+    return rc ? 1 : 0;
+}
+
+// `tksm barcode-match`: the three scTagger rules of the reference's single-cell route (Snakefile, "Preprocessing rules") in one call: FASTQ
+// reads and a barcode whitelist in, the lr_matches.tsv of `tksm abundance --lr-br` out (include/tksmseq.h).  Exit codes as the model modules:
+// 2 for a missing required option, an unknown option or a value out of range, all before any device is opened; 1 for everything later.
+extern "C" int tksmseq_barcode_match_main(int argc, char** argv) {
+    Common c;
+    tksmseq_barcode_match_params p{};
+    p.window = 200; p.max_adapter_errors = 5; p.pad = 4; p.max_errors = 2; p.min_exact = 2;
+    std::string reads, whitelist, adapter = "CTACACGACGCTCTTCCGATCT", segments_out, selected_out;
+    std::string range_error;
+    auto integer = [](const char* v, long long& out) { char* e = nullptr; out = strtoll(v, &e, 10); return e != v && !*e; };
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            // (the common flags know -i, -s, --batch-bytes and --slice-molecules, which this module does not have)
+            if (o == "-i" || o == "--input" || o == "-s" || o == "--seed" || o == "--batch-bytes" || o == "--slice-molecules") return NO_SUCH;
+            long long iv = 0;
+            auto ranged = [&](long long lo, long long hi, const char* what) {
+                if (!integer(v, iv)) return false;
+                if ((iv < lo || iv > hi) && range_error.empty()) range_error = o + " " + what;
+                iv = std::max(-1ll, std::min(iv, 0x7FFFFFFFll));
+                return true;
+            };
+            if (o == "--revcomp-barcodes") { p.revcomp_barcodes = 1; return TOOK_FLAG; }
+            if (o == "--reads" && v) reads = v;
+            else if (o == "--whitelist" && v) whitelist = v;
+            else if (o == "--adapter" && v) adapter = v;
+            else if (o == "--segments-out" && v) segments_out = v;
+            else if (o == "--selected-out" && v) selected_out = v;
+            else if (o == "--window" && v) { if (!ranged(4, 0x7FFFFFFF, "must be between the adapter's length and 2147483647")) return MALFORMED; p.window = (int32_t)iv; }
+            else if (o == "--max-adapter-errors" && v) { if (!ranged(0, 31, "must be between 0 and the adapter's length - 1")) return MALFORMED; p.max_adapter_errors = (int32_t)iv; }
+            else if (o == "--pad" && v) { if (!ranged(0, 16, "must be between 0 and 16")) return MALFORMED; p.pad = (int32_t)iv; }
+            else if (o == "--max-errors" && v) { if (!ranged(0, 31, "must be between 0 and the barcodes' length - 1")) return MALFORMED; p.max_errors = (int32_t)iv; }
+            else if (o == "--min-exact" && v) { if (!ranged(0, 0x7FFFFFFF, "must be between 0 and 2147483647")) return MALFORMED; p.min_exact = iv; }
+            else if (o == "--chunk-reads" && v) { if (!ranged(0, 0x7FFFFFFF, "must be between 0 and 2147483647")) return MALFORMED; p.chunk_reads = (uint64_t)std::max(0ll, iv); }
+            else return NOT_MINE;
+            return TOOK_VALUE;
+        })) return 2;
+    if (c.help) { printf("Assigns long reads to cell barcodes: finds the adapter at either end of a read and matches the bases behind it to a whitelist.\n"
+                         "usage: barcode-match --reads F[,F...] --whitelist W -o LR_MATCHES.tsv[.gz] [--adapter CTACACGACGCTCTTCCGATCT] [--window 200]\n"
+                         "                     [--max-adapter-errors 5] [--pad 4] [--max-errors 2] [--min-exact 2] [--revcomp-barcodes] [--segments-out F]\n"
+                         "                     [--selected-out F] [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L]\n"
+                         "FASTQ, whitelist and outputs may be .gz; the output is the file `tksm abundance --lr-br` reads\n"); return 0; }
+    std::string missing;
+    for (const auto& need : {std::make_pair(&reads, "--reads"), std::make_pair(&whitelist, "--whitelist"), std::make_pair(&c.output, "-o/--output")})
+        if (need.first->empty()) missing += (missing.empty() ? "" : ", ") + std::string(need.second);
+    if (!missing.empty()) { fprintf(stderr, "barcode-match: error: the following arguments are required: %s\n", missing.c_str()); return 2; }
+    if (range_error.empty()) {
+        bool acgt = adapter.size() >= 4 && adapter.size() <= 32;
+        for (char ch : adapter) acgt = acgt && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
+        if (!acgt) range_error = "--adapter must have 4 to 32 letters of ACGT";
+        else if (p.window < (int32_t)adapter.size()) range_error = "--window must be between the adapter's length and 2147483647";
+        else if (p.max_adapter_errors >= (int32_t)adapter.size()) range_error = "--max-adapter-errors must be between 0 and the adapter's length - 1";
+    }
+    if (!range_error.empty()) { fprintf(stderr, "barcode-match: error: %s\n", range_error.c_str()); return 2; }
+    Logger log;
+    if (!open_log(c, "barcode-match", log)) return 1;
+    tksmseq_ctx* ctx = nullptr;
+    if (tksmseq_create(c.devices[0], &ctx)) { fprintf(stderr, "Error: %s\n", tksmseq_last_error(nullptr)); return 1; }
+    const auto t0 = std::chrono::steady_clock::now();
+    p.adapter = adapter.c_str();
+    p.segments_out = segments_out.empty() ? nullptr : segments_out.c_str();
+    p.selected_out = selected_out.empty() ? nullptr : selected_out.c_str();
+    tksmseq_barcode_match_info info{};
+    const int rc = tksmseq_barcode_match(ctx, &p, reads.c_str(), whitelist.c_str(), c.output.c_str(), &info);
+    if (rc) fprintf(stderr, "Error: %s\n", tksmseq_last_error(ctx));
+    else {
+        log.log(Logger::INFO, "barcode-match: %llu reads: %llu without adapter, %llu forward, %llu reverse", (unsigned long long)info.reads, (unsigned long long)info.no_adapter,
+                (unsigned long long)info.forward, (unsigned long long)info.reverse);
+        log.log(Logger::INFO, "barcode-match: %llu of %llu barcodes are candidates; %llu reads with one barcode, %llu with several, %llu with none",
+                (unsigned long long)info.candidates, (unsigned long long)info.whitelist, (unsigned long long)info.unique, (unsigned long long)info.ambiguous,
+                (unsigned long long)info.no_barcode);
+        log.log(Logger::INFO, "barcode-match: %llu pairs in %llu chunks, written to %s in %.2f s (device %.2f ms)", (unsigned long long)info.pairs,
+                (unsigned long long)info.chunks, c.output.c_str(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), info.device_ms);
     }
     tksmseq_destroy(ctx);
     return rc ? 1 : 0;

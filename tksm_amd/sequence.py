@@ -588,6 +588,23 @@ class Sequencer:
         out["stage_ms"] = list(info.stage_ms)
         return out
 
+    def barcode_match(self, reads, whitelist, matches_out, adapter=None, window=200, max_adapter_errors=5, pad=4, max_errors=2, min_exact=2,
+                      revcomp_barcodes=False, segments_out=None, selected_out=None, chunk_reads=0):
+        """Long reads to cell barcodes on the device (tksmseq_barcode_match, the rules in include/tksmseq.h): `reads` (one FASTQ path or a list
+        of them, .gz or plain) and `whitelist` (one barcode per line) -> `matches_out`, the file `abundance(lr_br=...)` reads; optionally the
+        segments and the selected barcodes.  Returns the counters of tksmseq_barcode_match_info as a dict."""
+        if not isinstance(reads, (list, tuple)):
+            reads = [reads]
+        p = L.BarcodeMatchParams(adapter.encode() if adapter else None, int(window), int(max_adapter_errors), int(pad), int(max_errors), int(min_exact),
+                                 1 if revcomp_barcodes else 0, 0, int(chunk_reads), str(segments_out).encode() if segments_out else None,
+                                 str(selected_out).encode() if selected_out else None)
+        info = L.BarcodeMatchInfo()
+        self._chk(self._lib.tksmseq_barcode_match(self._ctx, C.byref(p), ",".join(str(r) for r in reads).encode(), str(whitelist).encode(),
+                                                  str(matches_out).encode(), C.byref(info)))
+        out = {n: getattr(info, n) for n, _ in L.BarcodeMatchInfo._fields_ if n not in ("stage_ms", "reserved")}
+        out["stage_ms"] = list(info.stage_ms)
+        return out
+
     # ---- random-wgs: whole-genome fragments made on the device
     def wgs(self, dist, a, b=0, base_count=None, depth=None, seed=42, first_candidate=0, n_candidates=1 << 20, state=None):
         """The loop of RWGS_module::run (src/random_wgs.cpp:181-207) for candidates [first_candidate, first_candidate + n_candidates)
