@@ -995,6 +995,89 @@ int tksmseq_barcode_match(tksmseq_ctx* ctx, const tksmseq_barcode_match_params* 
  * before any device is opened; 1 for everything that fails later. */
 int tksmseq_barcode_match_main(int argc, char** argv);
 
+/* ---- map: long reads to transcripts by minimizer chains on the device --------------------------------------------------------------------------
+ * Replaces the two minimap2 rules of the reference's workflow (minimap_cdna, minimap_cdna_for_badread_models: Snakefile): FASTQ reads and the
+ * context's reference (a cDNA FASTA) in, the PAF that `abundance -p` (columns 1, 2, 6, 8, 10, 11) and `model-truncation -i` (columns 7, 8, 9)
+ * read out.  Seeding and chaining only, the PAF minimap2 writes without -c: no base-level alignment and no cg:Z: tag, which model-sequence
+ * needs.  minimap2's source is not part of the reference tree: the FILE FORMAT is the consumers', the RULES below are this build's own, and so
+ * are the defaults (choices, not measurements of anything).  These are not minimap2's rules ("map").  Everything is integer: the
+ * output is the same bytes on every run and for every chunk size.
+ *
+ * Inputs.  The targets are the contigs of the context's reference, in contig order.  reads_paths: a comma list of FASTQ files, plain or .gz,
+ * read like model-sequence's (the name is the header up to the first white space, bases upper-cased, a name at most once).  A byte outside
+ * ACGT is invalid and belongs to no k-mer.
+ *
+ * k-mer.  k in [4, 28] (15), w in [1, 64] (10).  Position p covers [p, p + k).  fwd holds 2 bits per letter (A C G T = 0..3), the first
+ * letter highest; rev is the code of the reverse complement.  The k-mer is valid when all k letters are ACGT and fwd != rev; its strand is
+ * s = rev < fwd; its hash h is the splitmix64 finaliser of min(fwd, rev), all 64 bits kept:
+ *     x ^= x >> 30; x *= 0xbf58476d1ce4e5b9; x ^= x >> 27; x *= 0x94d049bb133111eb; x ^= x >> 31.
+ *
+ * Minimizers.  A sequence with n = len - k + 1 <= 0 positions has none.  Otherwise its windows are [j, min(j + w, n)) for
+ * j = 0 .. max(0, n - w).  Each window selects its valid position with the smallest (h, p); a window without a valid position selects
+ * nothing.  The minimizers are the distinct selected positions.
+ *
+ * Index.  Every target minimizer (h, target, p, s), ordered by (h, target, p).  A hash that occurs more than max_occ times (500) seeds nothing.
+ *
+ * Anchors.  For a read minimizer (h, q, sr) and an index entry (h, t, p, st): rel = sr ^ st; qa = q when rel = 0, else qlen - k - q (the
+ * k-mer's start in the reverse-complemented read); the anchor is (t, rel, p, qa).  The anchors of one (read, t, rel) form a group, ordered by
+ * (p, qa).
+ *
+ * Chain.  For anchor i of a group, f[i] = k with no predecessor to begin with.  Every j in [max(0, i - 64), i) with dt = p_i - p_j and
+ * dq = qa_i - qa_j is a candidate predecessor when dt > 0 and dq > 0, dt <= max_gap and dq <= max_gap (5000), and g = |dt - dq| <= bandwidth
+ * (500).  Its score is f[j] + min(k, dt, dq) - cost(g), cost(0) = 0 and cost(g) = g k / 100 + floor(log2 g) / 2 in integer division.  The
+ * largest candidate wins, among equal candidates the largest j; it becomes the predecessor, and f[i] its score, only when it exceeds k.
+ * The group's chain ends at the i with the largest f (the smallest such i on a tie) and is followed back through the predecessors: a group
+ * gives one chain, with cnt = its anchors, score = f[i], nmatch = k + the sum of min(k, dt, dq) over its links, tstart = p_first,
+ * tend = p_last + k, qs = qa_first, qe = qa_last + k, blen = max(tend - tstart, qe - qs).  It is kept when cnt >= min_count (3) and
+ * score >= min_score (40).
+ *
+ * Per read.  The kept chains ordered by (score descending, target ascending, rel ascending).  The first is the primary (tp:A:P), its
+ * mapq = min(60, 60 (s1 - s2) / s1) with s2 the second chain's score, or 0 when there is none.  The others are written as tp:A:S with mapq 0
+ * while score 1000 >= P s1, at most max_secondary of them (5); P = 1000 secondary_ratio rounded half up, computed on the host (0.8; the
+ * reference's workflow passes -p 0.0).  Reads appear in input order; a read without a kept chain gets no line and counts as unmapped.
+ *
+ * Line.  QNAME qlen qstart qend +|- TNAME tlen tstart tend nmatch blen mapq tp:A:P|S cm:i:cnt s1:i:score, tab-separated.  For rel = 1 the
+ * query interval is given in the original read: qstart = qlen - qe, qend = qlen - qs.  The file is written under <path>.tmp and renamed,
+ * gzipped (host zlib) when the name ends in .gz.
+ *
+ * On the device: the k-mer codes are cut from whole words of the packed sequences (the reads are packed like the reference), the window
+ * minimum is taken over an LDS tile; the index is radix-sorted by hash once per call and kept over the chunks; every read minimizer finds its
+ * hash by binary search; the anchors are sorted by (read, target, rel, p, qa) in two stable passes; groups below min_count anchors are dropped
+ * before chaining; a wave chains one group, lane l holding one of the 64 predecessors in registers.  Reads go in chunks of chunk_reads
+ * (0: sized from free device memory); a chunk with more anchors than the budget is split, never truncated.  No floating point.
+ *
+ * TKSMSEQ_EINVAL: a parameter out of range (also max_occ < 1, min_count < 1, a negative max_gap, bandwidth or min_score, secondary_ratio
+ * outside [0, 1], max_secondary outside [0, 1000]), a malformed FASTQ, no reads, or no reference.  TKSMSEQ_EIO: a file that cannot be read or
+ * written.  TKSMSEQ_ELIMIT: 2^31 reads, or a read or target of 2^31 bases, or more; one read with more anchors than a chunk may hold (2^24). */
+typedef struct tksmseq_map_params {
+    int32_t k;                       /* -k (15) */
+    int32_t w;                       /* -w (10) */
+    int32_t max_occ;                 /* --max-occ (500) */
+    int32_t max_gap;                 /* --max-gap (5000) */
+    int32_t bandwidth;               /* --bandwidth (500) */
+    int32_t min_count;               /* --min-count (3) */
+    int32_t min_score;               /* --min-score (40) */
+    int32_t reserved;
+    double secondary_ratio;          /* -p (0.8) */
+    int32_t max_secondary;           /* -N (5) */
+    int32_t reserved2;
+    uint64_t chunk_reads;            /* reads per chunk; 0: from free device memory */
+} tksmseq_map_params;
+typedef struct tksmseq_map_info {
+    uint64_t reads, mapped, unmapped, lines, secondary;        /* reads = mapped + unmapped; lines = mapped + secondary */
+    uint64_t target_minimizers, distinct_hashes, dropped_hashes;
+    uint64_t read_minimizers, anchors, groups, chained_groups, chunks;   /* chained_groups: the groups of at least min_count anchors */
+    float device_ms, stage_ms[5];    /* by HIP events, all chunks: sketch, index, seed, chain, select */
+    double read_ms, upload_ms, write_ms;   /* host wall time: reading and parsing, packing and uploads, formatting and writing */
+} tksmseq_map_info;
+/* params NULL: the defaults above */
+int tksmseq_map(tksmseq_ctx* ctx, const tksmseq_map_params* params, const char* reads_paths /* comma list */, const char* paf_out, tksmseq_map_info* info /* or NULL */);
+/* `tksm map`: -r REF.fa[.gz][,REF2.fa] --reads F.fq[.gz][,MORE] -o OUT.paf[.gz] [-k 15] [-w 10] [--max-occ 500] [--max-gap 5000] [--bandwidth 500]
+ * [--min-count 3] [--min-score 40] [-p 0.8] [-N 5] [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L].  Exit codes as the other model
+ * modules: 2 for a missing required option, an unknown option or a value out of range ("map: error: ..."), checked before any device is opened;
+ * 1 for everything that fails later. */
+int tksmseq_map_main(int argc, char** argv);
+
 /* The batch as MDF text, the way molecule_descriptor::operator<< writes it (src/interval.h:898-905): "+id<TAB>depth<TAB>comment",
  * then "chr<TAB>start<TAB>end<TAB>strand<TAB>pos<base>,..." per segment; depth 1 per molecule; comments re-serialised key-sorted
  * like dump_comment (:880-890).  *text is malloc'ed: release with tksmseq_text_free. */

@@ -173,6 +173,18 @@ class BarcodeMatchInfo(C.Structure):       # tksmseq_barcode_match_info
                 ("write_ms", C.c_double)]
 
 
+class MapParams(C.Structure):              # tksmseq_map_params
+    _fields_ = [("k", C.c_int32), ("w", C.c_int32), ("max_occ", C.c_int32), ("max_gap", C.c_int32), ("bandwidth", C.c_int32), ("min_count", C.c_int32),
+                ("min_score", C.c_int32), ("reserved", C.c_int32), ("secondary_ratio", C.c_double), ("max_secondary", C.c_int32), ("reserved2", C.c_int32),
+                ("chunk_reads", C.c_uint64)]
+
+
+class MapInfo(C.Structure):                # tksmseq_map_info
+    _fields_ = [(n, C.c_uint64) for n in ("reads", "mapped", "unmapped", "lines", "secondary", "target_minimizers", "distinct_hashes", "dropped_hashes",
+                                          "read_minimizers", "anchors", "groups", "chained_groups", "chunks")] + \
+               [("device_ms", C.c_float), ("stage_ms", C.c_float * 5), ("read_ms", C.c_double), ("upload_ms", C.c_double), ("write_ms", C.c_double)]
+
+
 BM_CAND_TILE = 256                           # candidates per workgroup row of the barcode match: a multiple of this (bm_kernels.h)
 BM_TARGET_WAVES = 2048                       # ... split until about this many waves (bm_kernels.h)
 BM_LIST = 8                                  # barcodes listed per read
@@ -207,6 +219,7 @@ SYMBOLS = [
     "tksmseq_abundance_free", "tksmseq_abundance_main",
     "tksmseq_model_sequence", "tksmseq_model_sequence_main",
     "tksmseq_barcode_match", "tksmseq_barcode_match_main",
+    "tksmseq_map", "tksmseq_map_main",
     "tksmseq_filter", "tksmseq_concat", "tksmseq_filter_main",
     "tksmseq_glue", "tksmseq_glue_joins", "tksmseq_shuffle", "tksmseq_unsegment_main", "tksmseq_shuffle_main",
     "tksmseq_variants_load", "tksmseq_variants_info", "tksmseq_variants_free", "tksmseq_mutate", "tksmseq_mutate_main",
@@ -323,6 +336,8 @@ def load():
         "tksmseq_model_sequence_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
         "tksmseq_barcode_match": (C.c_int, [vp, P(BarcodeMatchParams), C.c_char_p, C.c_char_p, C.c_char_p, P(BarcodeMatchInfo)]),
         "tksmseq_barcode_match_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
+        "tksmseq_map": (C.c_int, [vp, P(MapParams), C.c_char_p, C.c_char_p, P(MapInfo)]),
+        "tksmseq_map_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
         "tksmseq_filter": (C.c_int, [vp, vp, P(FilterParams), P(vp), P(vp)]),
         "tksmseq_concat": (C.c_int, [vp, P(vp), u64, i32, P(vp)]),
         "tksmseq_filter_main": (C.c_int, [C.c_int, P(C.c_char_p)]),

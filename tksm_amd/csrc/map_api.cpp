@@ -1,0 +1,395 @@
+// map_api.cpp -- C-ABI of map: tksmseq_map (include/tksmseq.h).  The host reads and checks (ms_host.cpp's FASTQ reader, map_host.cpp), packs
+// the reads of a chunk and formats the PAF; the sketch of targets and reads, the index, the seeds, the chains and the choice of the lines run
+// on the device (map_kernels.hip, with the radix sort of abundance and the run kernels of model-sequence).
+#include <chrono>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "abund_host.h"
+#include "ctx.h"
+#include "map_host.h"
+#include "map_kernels.h"
+#include "ms_kernels.h"
+
+namespace {
+
+constexpr uint64_t MAP_LIMIT = 1ull << 31;
+constexpr uint64_t MAP_ANCHORS_MIN = 1ull << 20, MAP_ANCHORS_MAX = 1ull << 24;      // the anchor budget of a chunk lies between these
+constexpr uint64_t MAP_ANCHOR_BYTES = 128;                                           // device bytes an anchor takes through sort and chain
+enum { ST_SKETCH, ST_INDEX, ST_SEED, ST_CHAIN, ST_SELECT };
+constexpr int RC_SPLIT = -1000;                                                      // (internal) the chunk has more anchors than the budget
+
+double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
+template <class T>
+hipError_t upload(TmpBuf& d, const T* v, size_t n, hipStream_t s) {
+    hipError_t e = d.ensure(std::max<size_t>(n, 1) * sizeof(T));
+    if (e != hipSuccess || !n) return e;
+    return hipMemcpyAsync(d.p, v, n * sizeof(T), hipMemcpyHostToDevice, s);
+}
+
+int bits_for(uint64_t n) { int b = 1; while (b < 64 && (n >> b)) b++; return b; }      // bits that hold every value below n (at least 1)
+
+// the state of one call
+struct MapRun {
+    tksmseq_ctx* ctx;
+    hipStream_t s;
+    tksmseq_map_params p;
+    uint32_t permille;
+    tksmseq_map_info info{};
+    hipEvent_t ev[2] = {};
+    // the index: distinct hashes with their runs in the sorted entries
+    TmpBuf d_tvalid, d_dkey, d_dcount, d_dstart, d_iseq, d_ips;
+    uint32_t n_distinct = 0;
+    uint64_t anchor_budget = MAP_ANCHORS_MAX;
+    const tkh::MsReads* reads = nullptr;
+    std::vector<std::string> names;
+    std::string paf;
+
+    MapRun(tksmseq_ctx* c, const tksmseq_map_params& q)
+        : ctx(c), s(c->stream), p(q), permille(tkh::map_permille(q.secondary_ratio)), d_tvalid(s), d_dkey(s), d_dcount(s), d_dstart(s), d_iseq(s), d_ips(s) {}
+    ~MapRun() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+
+    int begin() { HIPCHK(ctx, hipEventRecord(ev[0], s)); return TKSMSEQ_OK; }
+    int end(int stage) {
+        HIPCHK(ctx, hipEventRecord(ev[1], s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        float ms = 0.f;
+        HIPCHK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
+        info.stage_ms[stage] += ms;
+        return TKSMSEQ_OK;
+    }
+    // out[0 .. n] = the exclusive scan of in[0 .. n)
+    int scan(const uint64_t* in, uint64_t* out, uint64_t n) {
+        HIPCHK(ctx, ctx->w_scan.ensure(tk::scan_temp_bytes(n) + 64));
+        HIPCHK(ctx, tk::launch_scan(in, out, n, ctx->w_scan.p, ctx->w_scan.cap, s));
+        return TKSMSEQ_OK;
+    }
+    int fetch(const uint64_t* d, uint64_t& v) {
+        HIPCHK(ctx, hipMemcpyAsync(&v, d, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        return TKSMSEQ_OK;
+    }
+    // the minimizers of the tiled sequences: count, scan, write.  n_out minimizers in d_hash / d_seq / d_ps
+    int sketch(const uint32_t* codes, const uint32_t* valid, const tk::MapSeq* seqs, const std::vector<tkh::MapTile>& tiles, TmpBuf& d_tiles, TmpBuf& d_hash, TmpBuf& d_seq,
+               TmpBuf& d_ps, uint64_t& n_out) {
+        n_out = 0;
+        HIPCHK(ctx, d_hash.ensure(8)); HIPCHK(ctx, d_seq.ensure(4)); HIPCHK(ctx, d_ps.ensure(4));
+        if (tiles.empty()) return TKSMSEQ_OK;
+        const uint32_t n_tiles = (uint32_t)tiles.size();
+        TmpBuf d_cnt(s), d_off(s);
+        HIPCHK(ctx, upload(d_tiles, tiles.data(), tiles.size(), s));
+        HIPCHK(ctx, d_cnt.ensure(((size_t)n_tiles + 1) * 8));
+        HIPCHK(ctx, d_off.ensure(((size_t)n_tiles + 1) * 8));
+        const tk::MapSketch S{codes, valid, seqs, d_tiles.as<tk::MapTile>(), n_tiles, (uint32_t)p.k, (uint32_t)p.w};
+        HIPCHK(ctx, tk::launch_map_sketch_count(S, d_cnt.as<uint64_t>(), s));
+        if (int rc = scan(d_cnt.as<uint64_t>(), d_off.as<uint64_t>(), n_tiles)) return rc;
+        if (int rc = fetch(d_off.as<uint64_t>() + n_tiles, n_out)) return rc;
+        if (n_out >= (1ull << 32)) { ctx->err = "map: 2^32 minimizers or more in one pass"; return TKSMSEQ_ELIMIT; }
+        HIPCHK(ctx, d_hash.ensure(std::max<size_t>(n_out, 1) * 8));
+        HIPCHK(ctx, d_seq.ensure(std::max<size_t>(n_out, 1) * 4));
+        HIPCHK(ctx, d_ps.ensure(std::max<size_t>(n_out, 1) * 4));
+        HIPCHK(ctx, tk::launch_map_sketch_write(S, d_off.as<uint64_t>(), d_hash.as<uint64_t>(), d_seq.as<uint32_t>(), d_ps.as<uint32_t>(), s));
+        HIPCHK(ctx, hipStreamSynchronize(s));                   // (d_cnt and d_off go with this scope)
+        return TKSMSEQ_OK;
+    }
+    // keys[0 .. n) sorted: start[run] of the runs of equal keys, start[n_runs] = n
+    int runs(const uint64_t* sorted, uint32_t n, TmpBuf& d_start, uint64_t& n_runs) {
+        TmpBuf d_flag(s), d_scanned(s), d_info(s);
+        HIPCHK(ctx, d_flag.ensure(((size_t)n + 1) * 8));
+        HIPCHK(ctx, d_scanned.ensure(((size_t)n + 1) * 8));
+        HIPCHK(ctx, d_info.ensure(16));
+        HIPCHK(ctx, d_start.ensure(((size_t)n + 2) * 4));
+        HIPCHK(ctx, tk::launch_ms_run_flags(sorted, nullptr, n, d_flag.as<uint64_t>(), s));
+        if (int rc = scan(d_flag.as<uint64_t>(), d_scanned.as<uint64_t>(), n)) return rc;
+        HIPCHK(ctx, tk::launch_ms_run_starts(sorted, n, d_flag.as<uint64_t>(), d_scanned.as<uint64_t>(), d_start.as<uint32_t>(), d_info.as<uint64_t>(), s));
+        return fetch(d_info.as<uint64_t>(), n_runs);
+    }
+
+    int build_index();
+    int chunk(uint32_t r0, uint32_t r1);
+};
+
+int MapRun::build_index() {
+    const size_t n_t = ctx->contigs.size() / 2;
+    std::vector<tkh::MapSeq> tseq(n_t);
+    std::vector<tkh::MapTile> tiles;
+    for (size_t t = 0; t < n_t; t++) {
+        tseq[t] = {ctx->contigs[2 * t] / 32, (uint32_t)ctx->contigs[2 * t + 1], 0u};
+        tkh::map_add_tiles((uint32_t)t, ctx->contigs[2 * t + 1], (uint32_t)p.k, (uint32_t)p.w, tiles);
+    }
+    const tk::RefView R{ctx->d_packed.as<uint32_t>(), ctx->d_blocktab.as<uint32_t>(), ctx->d_pool.as<uint8_t>(), ctx->d_contigs.as<uint64_t>(), (uint32_t)n_t};
+    const uint64_t n_vwords = ctx->total_alloc / 32;
+    TmpBuf d_tseq(s), d_tiles(s), d_hash(s), d_seq(s), d_ps(s);
+    auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(ctx, upload(d_tseq, tseq.data(), tseq.size(), s));
+    HIPCHK(ctx, d_tvalid.ensure(std::max<size_t>(n_vwords, 1) * 4));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    info.upload_ms += ms_since(t0);
+
+    if (int rc = begin()) return rc;
+    HIPCHK(ctx, tk::launch_map_ref_valid(R, n_vwords, d_tvalid.as<uint32_t>(), s));
+    uint64_t n_tm = 0;
+    if (int rc = sketch(R.packed, d_tvalid.as<uint32_t>(), d_tseq.as<tk::MapSeq>(), tiles, d_tiles, d_hash, d_seq, d_ps, n_tm)) return rc;
+    if (int rc = end(ST_SKETCH)) return rc;
+    info.target_minimizers = n_tm;
+
+    HIPCHK(ctx, d_dkey.ensure(8)); HIPCHK(ctx, d_dcount.ensure(8)); HIPCHK(ctx, d_dstart.ensure(8)); HIPCHK(ctx, d_iseq.ensure(4)); HIPCHK(ctx, d_ips.ensure(4));
+    if (!n_tm) return TKSMSEQ_OK;
+    const uint32_t n = (uint32_t)n_tm;
+    if (int rc = begin()) return rc;
+    TmpBuf d_sorted(s), d_perm(s), d_dropped(s);
+    HIPCHK(ctx, d_sorted.ensure((size_t)n * 8));
+    HIPCHK(ctx, d_perm.ensure((size_t)n * 4));
+    HIPCHK(ctx, d_iseq.ensure((size_t)n * 4));
+    HIPCHK(ctx, d_ips.ensure((size_t)n * 4));
+    HIPCHK(ctx, d_dropped.ensure(8));
+    // stable: entries of one hash stay in (target, p) order
+    if (int rc = sort_pairs<uint64_t>(ctx, tk::abund_sort_u64, d_hash.as<uint64_t>(), d_sorted.as<uint64_t>(), d_perm.as<uint32_t>(), n, 64)) return rc;
+    HIPCHK(ctx, tk::launch_ms_gather_u32(d_seq.as<uint32_t>(), d_perm.as<uint32_t>(), n, d_iseq.as<uint32_t>(), s));
+    HIPCHK(ctx, tk::launch_ms_gather_u32(d_ps.as<uint32_t>(), d_perm.as<uint32_t>(), n, d_ips.as<uint32_t>(), s));
+    uint64_t n_runs = 0;
+    if (int rc = runs(d_sorted.as<uint64_t>(), n, d_dstart, n_runs)) return rc;
+    if (n_runs > n) { ctx->err = "map: more distinct hashes than minimizers"; return TKSMSEQ_EDEVICE; }
+    n_distinct = (uint32_t)n_runs;
+    HIPCHK(ctx, d_dkey.ensure((size_t)n_distinct * 8));
+    HIPCHK(ctx, d_dcount.ensure((size_t)n_distinct * 8));
+    HIPCHK(ctx, tk::launch_ms_run_write(d_sorted.as<uint64_t>(), nullptr, d_dstart.as<uint32_t>(), n_distinct, nullptr, nullptr, d_dkey.as<uint64_t>(), nullptr,
+                                        d_dcount.as<uint64_t>(), s));
+    HIPCHK(ctx, tk::launch_map_dropped(d_dcount.as<uint64_t>(), n_distinct, (uint64_t)p.max_occ, (unsigned long long*)d_dropped.p, s));
+    uint64_t dropped = 0;
+    if (int rc = fetch(d_dropped.as<uint64_t>(), dropped)) return rc;
+    if (int rc = end(ST_INDEX)) return rc;
+    info.distinct_hashes = n_distinct;
+    info.dropped_hashes = dropped;
+    return TKSMSEQ_OK;
+}
+
+// reads [r0, r1): their lines appended to paf, or RC_SPLIT (nothing appended, no counter touched) when they have more anchors than the budget
+int MapRun::chunk(uint32_t r0, uint32_t r1) {
+    const uint32_t n = r1 - r0, slots = (uint32_t)p.max_secondary + 1u;
+    std::vector<uint32_t> h_codes, h_valid;
+    std::vector<tkh::MapSeq> h_seqs;
+    std::vector<tkh::MapTile> tiles;
+    TmpBuf d_codes(s), d_valid(s), d_seqs(s), d_tiles(s), d_rh(s), d_rread(s), d_rps(s);
+    auto t0 = std::chrono::steady_clock::now();
+    tkh::map_pack_reads(*reads, r0, r1, h_codes, h_valid, h_seqs);
+    for (uint32_t r = 0; r < n; r++) tkh::map_add_tiles(r, h_seqs[r].len, (uint32_t)p.k, (uint32_t)p.w, tiles);
+    HIPCHK(ctx, upload(d_codes, h_codes.data(), h_codes.size(), s));
+    HIPCHK(ctx, upload(d_valid, h_valid.data(), h_valid.size(), s));
+    HIPCHK(ctx, upload(d_seqs, h_seqs.data(), h_seqs.size(), s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    const double upload_ms = ms_since(t0);
+
+    // ---- sketch
+    uint64_t n_rm64 = 0;
+    if (int rc = begin()) return rc;
+    if (int rc = sketch(d_codes.as<uint32_t>(), d_valid.as<uint32_t>(), d_seqs.as<tk::MapSeq>(), tiles, d_tiles, d_rh, d_rread, d_rps, n_rm64)) return rc;
+    if (int rc = end(ST_SKETCH)) return rc;
+    const uint32_t n_rm = (uint32_t)n_rm64;
+
+    // ---- seed: count, scan, write, and the two stable sorts that order the anchors by (read, target, rel, p, qa)
+    TmpBuf d_run(s), d_cnt(s), d_off(s), d_k1(s), d_k2(s), d_k1f(s), d_k2s(s), d_gstart(s), d_list(s);
+    uint64_t n_anchors = 0, n_groups = 0, n_chained = 0;
+    if (int rc = begin()) return rc;
+    HIPCHK(ctx, d_run.ensure(std::max<size_t>(n_rm, 1) * 4));
+    HIPCHK(ctx, d_cnt.ensure(((size_t)n_rm + 1) * 8));
+    HIPCHK(ctx, d_off.ensure(((size_t)n_rm + 1) * 8));
+    if (n_rm) {
+        HIPCHK(ctx, tk::launch_map_seed_count(d_rh.as<uint64_t>(), n_rm, d_dkey.as<uint64_t>(), d_dcount.as<uint64_t>(), n_distinct, (uint64_t)p.max_occ, d_run.as<uint32_t>(),
+                                              d_cnt.as<uint64_t>(), s));
+        if (int rc = scan(d_cnt.as<uint64_t>(), d_off.as<uint64_t>(), n_rm)) return rc;
+        if (int rc = fetch(d_off.as<uint64_t>() + n_rm, n_anchors)) return rc;
+    }
+    if (n_anchors > anchor_budget) {
+        if (int rc = end(ST_SEED)) return rc;
+        if (n > 1) return RC_SPLIT;                              // (the device time of the attempt stays in stage_ms: it was spent)
+        ctx->err = "map: read " + names[r0] + " has " + std::to_string(n_anchors) + " anchors, more than a chunk may hold";
+        return TKSMSEQ_ELIMIT;
+    }
+    const uint32_t na = (uint32_t)n_anchors;
+    HIPCHK(ctx, d_gstart.ensure(((size_t)na + 2) * 4));
+    HIPCHK(ctx, d_list.ensure(std::max<size_t>(na, 1) * 4));
+    HIPCHK(ctx, d_k1f.ensure(std::max<size_t>(na, 1) * 8));
+    HIPCHK(ctx, d_k2s.ensure(std::max<size_t>(na, 1) * 8));
+    if (na) {
+        TmpBuf d_k1s(s), d_perm1(s), d_k2g(s), d_perm2(s), d_flag(s), d_scanned(s);
+        HIPCHK(ctx, d_k1.ensure((size_t)na * 8));
+        HIPCHK(ctx, d_k2.ensure((size_t)na * 8));
+        HIPCHK(ctx, d_k1s.ensure((size_t)na * 8));
+        HIPCHK(ctx, d_k2g.ensure((size_t)na * 8));
+        HIPCHK(ctx, d_perm1.ensure((size_t)na * 4));
+        HIPCHK(ctx, d_perm2.ensure((size_t)na * 4));
+        HIPCHK(ctx, tk::launch_map_seed_write(d_rread.as<uint32_t>(), d_rps.as<uint32_t>(), d_run.as<uint32_t>(), d_cnt.as<uint64_t>(), d_off.as<uint64_t>(), n_rm,
+                                              d_dstart.as<uint32_t>(), d_iseq.as<uint32_t>(), d_ips.as<uint32_t>(), d_seqs.as<tk::MapSeq>(), (uint32_t)p.k, d_k1.as<uint64_t>(),
+                                              d_k2.as<uint64_t>(), s));
+        if (int rc = sort_pairs<uint64_t>(ctx, tk::abund_sort_u64, d_k1.as<uint64_t>(), d_k1s.as<uint64_t>(), d_perm1.as<uint32_t>(), na, 62)) return rc;
+        HIPCHK(ctx, tk::launch_ms_gather_u64(d_k2.as<uint64_t>(), d_perm1.as<uint32_t>(), na, d_k2g.as<uint64_t>(), s));
+        if (int rc = sort_pairs<uint64_t>(ctx, tk::abund_sort_u64, d_k2g.as<uint64_t>(), d_k2s.as<uint64_t>(), d_perm2.as<uint32_t>(), na, 32 + bits_for(n))) return rc;
+        HIPCHK(ctx, tk::launch_ms_gather_u64(d_k1s.as<uint64_t>(), d_perm2.as<uint32_t>(), na, d_k1f.as<uint64_t>(), s));
+        if (int rc = runs(d_k2s.as<uint64_t>(), na, d_gstart, n_groups)) return rc;
+        if (n_groups > na) { ctx->err = "map: more groups than anchors"; return TKSMSEQ_EDEVICE; }
+        // groups that cannot reach min_count anchors leave before any chaining
+        HIPCHK(ctx, d_flag.ensure(((size_t)n_groups + 1) * 8));
+        HIPCHK(ctx, d_scanned.ensure(((size_t)n_groups + 1) * 8));
+        HIPCHK(ctx, tk::launch_map_group_flags(d_gstart.as<uint32_t>(), (uint32_t)n_groups, (uint32_t)p.min_count, d_flag.as<uint64_t>(), s));
+        if (int rc = scan(d_flag.as<uint64_t>(), d_scanned.as<uint64_t>(), n_groups)) return rc;
+        if (int rc = fetch(d_scanned.as<uint64_t>() + n_groups, n_chained)) return rc;
+        if (n_chained > n_groups) { ctx->err = "map: more surviving groups than groups"; return TKSMSEQ_EDEVICE; }
+        HIPCHK(ctx, tk::launch_map_group_list(d_flag.as<uint64_t>(), d_scanned.as<uint64_t>(), (uint32_t)n_groups, d_list.as<uint32_t>(), s));
+        HIPCHK(ctx, hipStreamSynchronize(s));                   // (the temporaries of this scope go)
+    }
+    if (int rc = end(ST_SEED)) return rc;
+
+    // ---- chain: one wave per surviving group
+    const uint32_t nc = (uint32_t)n_chained;
+    TmpBuf d_pred(s), d_chain(s);
+    std::vector<tkh::MapChain> chains(nc);
+    if (int rc = begin()) return rc;
+    HIPCHK(ctx, d_pred.ensure(std::max<size_t>(na, 1) * 4));
+    HIPCHK(ctx, d_chain.ensure(std::max<size_t>(nc, 1) * sizeof(tk::MapChain)));
+    const tk::MapChainParams CP{(uint32_t)p.k, (uint32_t)p.max_gap, (uint32_t)p.bandwidth, (uint32_t)p.min_count, (uint32_t)p.min_score};
+    HIPCHK(ctx, tk::launch_map_chain(d_k1f.as<uint64_t>(), d_k2s.as<uint64_t>(), d_gstart.as<uint32_t>(), d_list.as<uint32_t>(), nc, CP, d_pred.as<uint32_t>(),
+                                     d_chain.as<tk::MapChain>(), s));
+    if (int rc = end(ST_CHAIN)) return rc;
+
+    // ---- select: the kept chains by (read, score descending), target and rel ascending by the sort's stability
+    TmpBuf d_key(s), d_keys(s), d_perm(s), d_nl(s), d_mq(s), d_lines(s);
+    std::vector<uint32_t> n_lines(n), mapq(n), lines((size_t)n * slots);
+    if (int rc = begin()) return rc;
+    HIPCHK(ctx, d_key.ensure(std::max<size_t>(nc, 1) * 8));
+    HIPCHK(ctx, d_keys.ensure(std::max<size_t>(nc, 1) * 8));
+    HIPCHK(ctx, d_perm.ensure(std::max<size_t>(nc, 1) * 4));
+    HIPCHK(ctx, d_nl.ensure((size_t)n * 4));
+    HIPCHK(ctx, d_mq.ensure((size_t)n * 4));
+    HIPCHK(ctx, d_lines.ensure((size_t)n * slots * 4));
+    if (nc) {
+        HIPCHK(ctx, tk::launch_map_chain_keys(d_chain.as<tk::MapChain>(), nc, d_key.as<uint64_t>(), s));
+        if (int rc = sort_pairs<uint64_t>(ctx, tk::abund_sort_u64, d_key.as<uint64_t>(), d_keys.as<uint64_t>(), d_perm.as<uint32_t>(), nc, 64)) return rc;
+    }
+    HIPCHK(ctx, tk::launch_map_select(d_keys.as<uint64_t>(), d_perm.as<uint32_t>(), nc, n, permille, (uint32_t)p.max_secondary, d_nl.as<uint32_t>(), d_mq.as<uint32_t>(),
+                                      d_lines.as<uint32_t>(), s));
+    HIPCHK(ctx, hipMemcpyAsync(n_lines.data(), d_nl.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(mapq.data(), d_mq.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(lines.data(), d_lines.p, (size_t)n * slots * 4, hipMemcpyDeviceToHost, s));
+    if (nc) HIPCHK(ctx, hipMemcpyAsync(chains.data(), d_chain.p, (size_t)nc * sizeof(tk::MapChain), hipMemcpyDeviceToHost, s));
+    if (int rc = end(ST_SELECT)) return rc;
+
+    // ---- the lines of the chunk
+    t0 = std::chrono::steady_clock::now();
+    for (uint32_t r = 0; r < n; r++) {
+        if (n_lines[r] > slots) { ctx->err = "map: more lines for a read than it may have"; return TKSMSEQ_EDEVICE; }
+        if (!n_lines[r]) { info.unmapped++; continue; }
+        info.mapped++;
+        for (uint32_t i = 0; i < n_lines[r]; i++) {
+            const uint32_t c = lines[(size_t)r * slots + i];
+            if (c >= nc || chains[c].read != r || (chains[c].tr >> 1) >= ctx->contig_names.size()) { ctx->err = "map: a line of a chain that does not exist"; return TKSMSEQ_EDEVICE; }
+            const uint32_t t = chains[c].tr >> 1;
+            tkh::map_paf_line(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], chains[c], i ? 0u : mapq[r], i == 0, paf);
+            info.lines++;
+            if (i) info.secondary++;
+        }
+    }
+    info.write_ms += ms_since(t0);
+    info.upload_ms += upload_ms;
+    info.read_minimizers += n_rm;
+    info.anchors += n_anchors;
+    info.groups += n_groups;
+    info.chained_groups += n_chained;
+    info.chunks++;
+    return TKSMSEQ_OK;
+}
+
+}  // namespace
+
+extern "C" int tksmseq_map(tksmseq_ctx* ctx, const tksmseq_map_params* params, const char* reads_paths, const char* paf_out, tksmseq_map_info* info_out) {
+    if (!ctx) return TKSMSEQ_EINVAL;
+    if (!reads_paths || !paf_out || !*paf_out) { ctx->err = "map: null argument"; return TKSMSEQ_EINVAL; }
+    tksmseq_map_params p{};
+    p.k = 15; p.w = 10; p.max_occ = 500; p.max_gap = 5000; p.bandwidth = 500; p.min_count = 3; p.min_score = 40; p.secondary_ratio = 0.8; p.max_secondary = 5;
+    if (params) p = *params;
+    if (!tkh::map_check_params(p, ctx->err)) return TKSMSEQ_EINVAL;
+    if (ctx->contigs.empty()) { ctx->err = "map: the context has no reference"; return TKSMSEQ_EINVAL; }
+    if (ctx->n_declared) { ctx->err = "map: the reference has contigs that are declared only"; return TKSMSEQ_EINVAL; }
+    if (ctx->contigs.size() / 2 >= MAP_LIMIT) { ctx->err = "map: 2^31 targets or more"; return TKSMSEQ_ELIMIT; }
+    for (size_t t = 0; t < ctx->contigs.size() / 2; t++)
+        if (ctx->contigs[2 * t + 1] >= MAP_LIMIT) { ctx->err = "map: target " + ctx->contig_names[t] + " has 2^31 bases or more"; return TKSMSEQ_ELIMIT; }
+
+    // ---- the host reads
+    auto t0 = std::chrono::steady_clock::now();
+    tkh::MsReads reads;
+    {
+        std::string text;
+        const std::string list = reads_paths;
+        for (size_t a = 0; a <= list.size();) {
+            size_t b = list.find(',', a);
+            if (b == std::string::npos) b = list.size();
+            if (b > a) {
+                const std::string path = list.substr(a, b - a);
+                text.clear();
+                if (!tkh::abund_read_file(path, text, ctx->err)) return TKSMSEQ_EIO;
+                std::string e;
+                if (!tkh::parse_fastq(text.data(), text.size(), reads, e)) {
+                    const bool malformed = e.compare(0, 5, "FASTQ") == 0;
+                    ctx->err = malformed ? path + ": " + e : "map: 2^31 reads or more";
+                    return malformed ? TKSMSEQ_EINVAL : TKSMSEQ_ELIMIT;
+                }
+                if (reads.size() >= MAP_LIMIT) { ctx->err = "map: 2^31 reads or more"; return TKSMSEQ_ELIMIT; }
+            }
+            a = b + 1;
+        }
+        if (!reads.size()) { ctx->err = "map: no reads in " + list; return TKSMSEQ_EINVAL; }
+    }
+    const uint32_t n_reads = (uint32_t)reads.size();
+    for (uint32_t r = 0; r < n_reads; r++)
+        if (reads.off[r + 1] - reads.off[r] >= MAP_LIMIT) { ctx->err = "map: a read of 2^31 bases or more"; return TKSMSEQ_ELIMIT; }
+
+    MapRun run(ctx, p);
+    run.reads = &reads;
+    run.names.resize(n_reads);
+    for (const auto& kv : reads.index) run.names[kv.second] = kv.first;
+    run.info.reads = n_reads;
+    run.info.read_ms = ms_since(t0);
+
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    for (auto& e : run.ev) HIPCHK(ctx, hipEventCreate(&e));
+    if (int rc = run.build_index()) return rc;
+
+    uint64_t chunk_reads = p.chunk_reads;
+    {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
+        run.anchor_budget = std::max(MAP_ANCHORS_MIN, std::min<uint64_t>(MAP_ANCHORS_MAX, free_b / 4 / MAP_ANCHOR_BYTES));
+        if (!chunk_reads) {
+            // per read: its packed letters, and about two minimizers in w + 1 positions through sketch and seed
+            const uint64_t mean = reads.off[n_reads] / n_reads + 1;
+            chunk_reads = std::max<uint64_t>(1ull << 10, std::min<uint64_t>(free_b / 8 / (mean * 16 + 64), 1ull << 20));
+        }
+    }
+    // chunks in input order; one with more anchors than the budget is halved and tried again
+    std::vector<std::pair<uint32_t, uint32_t>> todo;
+    for (uint64_t r0 = ((uint64_t)n_reads - 1) / chunk_reads * chunk_reads;; r0 -= chunk_reads) {
+        todo.emplace_back((uint32_t)r0, (uint32_t)std::min<uint64_t>(n_reads, r0 + chunk_reads));
+        if (!r0) break;
+    }
+    while (!todo.empty()) {
+        const auto c = todo.back();
+        todo.pop_back();
+        const int rc = run.chunk(c.first, c.second);
+        if (rc == RC_SPLIT) {
+            const uint32_t mid = c.first + (c.second - c.first) / 2;
+            todo.emplace_back(mid, c.second);
+            todo.emplace_back(c.first, mid);
+        } else if (rc) return rc;
+    }
+    tksmseq_map_info& info = run.info;
+    for (float ms : info.stage_ms) info.device_ms += ms;
+
+    t0 = std::chrono::steady_clock::now();
+    std::string e;
+    if (!tkh::write_abundance_file(paf_out, run.paf, e)) { ctx->err = "map: cannot write " + std::string(paf_out); return TKSMSEQ_EIO; }
+    info.write_ms += ms_since(t0);
+    if (info_out) *info_out = info;
+    return TKSMSEQ_OK;
+}

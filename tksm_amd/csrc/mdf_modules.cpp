@@ -22,6 +22,7 @@
 //   abundance               py/transcript_abundance.py:32-139, :326-389 (behind src/abundance.cpp) PAF in, expression TSV out: no MDF, one context
 //   model-sequence          the model_sequence rule (Snakefile:507-546: badread error_model + qscore_model) reference, FASTQ and PAF in, two model files out: no MDF, one context
 //   barcode-match           the three scTagger rules (Snakefile, "Preprocessing rules") FASTQ and whitelist in, lr_matches.tsv out: no MDF, one context
+//   map                     the two minimap2 rules (Snakefile: minimap_cdna, minimap_cdna_for_badread_models) reference and FASTQ in, PAF out: no MDF, one context
 //   utility flags           src/module.h:75-104      -s/--seed (default 42), --verbosity, --log-file, -h
 // All stream: `truncate` and the four segment edits read the input in batches of whole molecules (--batch-bytes), `pcr` amplifies its templates in slices
 // of about --slice-molecules output molecules (tksmseq_pcr_params::template_begin / _end); the pieces go round the entries of
@@ -1300,6 +1301,87 @@ extern "C" int tksmseq_barcode_match_main(int argc, char** argv) {
                 (unsigned long long)info.no_barcode);
         log.log(Logger::INFO, "barcode-match: %llu pairs in %llu chunks, written to %s in %.2f s (device %.2f ms)", (unsigned long long)info.pairs,
                 (unsigned long long)info.chunks, c.output.c_str(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), info.device_ms);
+    }
+    tksmseq_destroy(ctx);
+    return rc ? 1 : 0;
+}
+
+// `tksm map`: the two minimap2 rules of the reference's workflow (Snakefile: minimap_cdna, minimap_cdna_for_badread_models) without -c: FASTQ
+// reads and a cDNA FASTA in, the PAF of `tksm abundance -p` and `tksm model-truncation -i` out (include/tksmseq.h).  Exit codes as the model
+// modules: 2 for a missing required option, an unknown option or a value out of range, all before any device is opened; 1 for everything later.
+extern "C" int tksmseq_map_main(int argc, char** argv) {
+    Common c;
+    tksmseq_map_params p{};
+    p.k = 15; p.w = 10; p.max_occ = 500; p.max_gap = 5000; p.bandwidth = 500; p.min_count = 3; p.min_score = 40; p.secondary_ratio = 0.8; p.max_secondary = 5;
+    std::string reference, reads;
+    std::string range_error;
+    auto integer = [](const char* v, long long& out) { char* e = nullptr; out = strtoll(v, &e, 10); return e != v && !*e; };
+    if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
+            // (the common flags know -i, -s, --batch-bytes and --slice-molecules, which this module does not have)
+            if (o == "-i" || o == "--input" || o == "-s" || o == "--seed" || o == "--batch-bytes" || o == "--slice-molecules") return NO_SUCH;
+            long long iv = 0;
+            auto ranged = [&](long long lo, long long hi, const char* what) {
+                if (!integer(v, iv)) return false;
+                if ((iv < lo || iv > hi) && range_error.empty()) range_error = o + " " + what;
+                iv = std::max(-1ll, std::min(iv, 0x7FFFFFFFll));
+                return true;
+            };
+            if ((o == "-r" || o == "--reference") && v) reference = v;
+            else if (o == "--reads" && v) reads = v;
+            else if (o == "-k" && v) { if (!ranged(4, 28, "must be between 4 and 28")) return MALFORMED; p.k = (int32_t)iv; }
+            else if (o == "-w" && v) { if (!ranged(1, 64, "must be between 1 and 64")) return MALFORMED; p.w = (int32_t)iv; }
+            else if (o == "--max-occ" && v) { if (!ranged(1, 0x7FFFFFFF, "must be between 1 and 2147483647")) return MALFORMED; p.max_occ = (int32_t)iv; }
+            else if (o == "--max-gap" && v) { if (!ranged(0, 0x7FFFFFFF, "must be between 0 and 2147483647")) return MALFORMED; p.max_gap = (int32_t)iv; }
+            else if (o == "--bandwidth" && v) { if (!ranged(0, 0x7FFFFFFF, "must be between 0 and 2147483647")) return MALFORMED; p.bandwidth = (int32_t)iv; }
+            else if (o == "--min-count" && v) { if (!ranged(1, 0x7FFFFFFF, "must be between 1 and 2147483647")) return MALFORMED; p.min_count = (int32_t)iv; }
+            else if (o == "--min-score" && v) { if (!ranged(0, 0x7FFFFFFF, "must be between 0 and 2147483647")) return MALFORMED; p.min_score = (int32_t)iv; }
+            else if (o == "-N" && v) { if (!ranged(0, 1000, "must be between 0 and 1000")) return MALFORMED; p.max_secondary = (int32_t)iv; }
+            else if (o == "--chunk-reads" && v) { if (!ranged(0, 0x7FFFFFFF, "must be between 0 and 2147483647")) return MALFORMED; p.chunk_reads = (uint64_t)std::max(0ll, iv); }
+            else if (o == "-p" && v) {
+                char* e = nullptr;
+                const double d = strtod(v, &e);
+                if (e == v || *e) return MALFORMED;
+                if (!(d >= 0.0 && d <= 1.0) && range_error.empty()) range_error = o + " must be between 0 and 1";
+                p.secondary_ratio = d;
+            }
+            else return NOT_MINE;
+            return TOOK_VALUE;
+        })) return 2;
+    if (c.help) { printf("Maps long reads to transcripts by chains of minimizers: seeding and chaining only, the PAF that minimap2 writes without -c.\n"
+                         "usage: map -r REF.fa[.gz][,REF2.fa] --reads F.fq[.gz][,MORE] -o OUT.paf[.gz] [-k 15] [-w 10] [--max-occ 500] [--max-gap 5000] [--bandwidth 500]\n"
+                         "           [--min-count 3] [--min-score 40] [-p 0.8] [-N 5] [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L]\n"
+                         "the output is the file `tksm abundance -p` and `tksm model-truncation -i` read; it has no cg:Z: tags (model-sequence needs them)\n"); return 0; }
+    std::string missing;
+    for (const auto& need : {std::make_pair(&reference, "-r/--reference"), std::make_pair(&reads, "--reads"), std::make_pair(&c.output, "-o/--output")})
+        if (need.first->empty()) missing += (missing.empty() ? "" : ", ") + std::string(need.second);
+    if (!missing.empty()) { fprintf(stderr, "map: error: the following arguments are required: %s\n", missing.c_str()); return 2; }
+    if (!range_error.empty()) { fprintf(stderr, "map: error: %s\n", range_error.c_str()); return 2; }
+    Logger log;
+    if (!open_log(c, "map", log)) return 1;
+    tksmseq_ctx* ctx = nullptr;
+    if (tksmseq_create(c.devices[0], &ctx)) { fprintf(stderr, "Error: %s\n", tksmseq_last_error(nullptr)); return 1; }
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = 0;
+    for (size_t a = 0; a <= reference.size() && !rc;) {
+        size_t b = reference.find(',', a);
+        if (b == std::string::npos) b = reference.size();
+        if (b > a) {
+            log.log(Logger::INFO, "Reading %s", reference.substr(a, b - a).c_str());
+            rc = tksmseq_reference_add_fasta(ctx, reference.substr(a, b - a).c_str());
+        }
+        a = b + 1;
+    }
+    tksmseq_map_info info{};
+    if (!rc) rc = tksmseq_map(ctx, &p, reads.c_str(), c.output.c_str(), &info);
+    if (rc) fprintf(stderr, "Error: %s\n", tksmseq_last_error(ctx));
+    else {
+        log.log(Logger::INFO, "map: %llu target minimizers under %llu hashes (%llu over --max-occ); %llu read minimizers, %llu anchors, %llu groups, %llu chained",
+                (unsigned long long)info.target_minimizers, (unsigned long long)info.distinct_hashes, (unsigned long long)info.dropped_hashes,
+                (unsigned long long)info.read_minimizers, (unsigned long long)info.anchors, (unsigned long long)info.groups, (unsigned long long)info.chained_groups);
+        log.log(Logger::INFO, "map: %llu reads: %llu mapped, %llu unmapped; %llu lines (%llu secondary) in %llu chunks, written to %s in %.2f s (device %.2f ms)",
+                (unsigned long long)info.reads, (unsigned long long)info.mapped, (unsigned long long)info.unmapped, (unsigned long long)info.lines,
+                (unsigned long long)info.secondary, (unsigned long long)info.chunks, c.output.c_str(),
+                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), info.device_ms);
     }
     tksmseq_destroy(ctx);
     return rc ? 1 : 0;

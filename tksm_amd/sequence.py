@@ -605,6 +605,21 @@ class Sequencer:
         out["stage_ms"] = list(info.stage_ms)
         return out
 
+    def map(self, reads, paf_out, k=15, w=10, max_occ=500, max_gap=5000, bandwidth=500, min_count=3, min_score=40, secondary_ratio=0.8, max_secondary=5,
+            chunk_reads=0):
+        """Long reads to the contigs of this context's reference (a cDNA FASTA) by minimizer chains on the device (tksmseq_map, the rules in
+        include/tksmseq.h): `reads` (one FASTQ path or a list of them, .gz or plain) -> `paf_out`, the PAF `abundance(paf=...)` and
+        `model_truncation` read (no cg:Z: tags).  Returns the counters of tksmseq_map_info as a dict."""
+        if not isinstance(reads, (list, tuple)):
+            reads = [reads]
+        p = L.MapParams(int(k), int(w), int(max_occ), int(max_gap), int(bandwidth), int(min_count), int(min_score), 0, float(secondary_ratio), int(max_secondary), 0,
+                        int(chunk_reads))
+        info = L.MapInfo()
+        self._chk(self._lib.tksmseq_map(self._ctx, C.byref(p), ",".join(str(r) for r in reads).encode(), str(paf_out).encode(), C.byref(info)))
+        out = {n: getattr(info, n) for n, _ in L.MapInfo._fields_ if n != "stage_ms"}
+        out["stage_ms"] = list(info.stage_ms)
+        return out
+
     # ---- random-wgs: whole-genome fragments made on the device
     def wgs(self, dist, a, b=0, base_count=None, depth=None, seed=42, first_candidate=0, n_candidates=1 << 20, state=None):
         """The loop of RWGS_module::run (src/random_wgs.cpp:181-207) for candidates [first_candidate, first_candidate + n_candidates)
