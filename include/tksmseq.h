@@ -998,8 +998,8 @@ int tksmseq_barcode_match_main(int argc, char** argv);
 /* ---- map: long reads to transcripts by minimizer chains on the device --------------------------------------------------------------------------
  * Replaces the two minimap2 rules of the reference's workflow (minimap_cdna, minimap_cdna_for_badread_models: Snakefile): FASTQ reads and the
  * context's reference (a cDNA FASTA) in, the PAF that `abundance -p` (columns 1, 2, 6, 8, 10, 11) and `model-truncation -i` (columns 7, 8, 9)
- * read out.  Seeding and chaining only, the PAF minimap2 writes without -c: no base-level alignment and no cg:Z: tag, which model-sequence
- * needs.  minimap2's source is not part of the reference tree: the FILE FORMAT is the consumers', the RULES below are this build's own, and so
+ * read out.  tksmseq_map seeds and chains only, the PAF minimap2 writes without -c; tksmseq_map_align ("map, alignment" below) adds the
+ * base-level alignment of the written chains and the cg:Z: tag model-sequence reads.  minimap2's source is not part of the reference tree: the FILE FORMAT is the consumers', the RULES below are this build's own, and so
  * are the defaults (choices, not measurements of anything).  These are not minimap2's rules ("map").  Everything is integer: the
  * output is the same bytes on every run and for every chunk size.
  *
@@ -1072,10 +1072,58 @@ typedef struct tksmseq_map_info {
 } tksmseq_map_info;
 /* params NULL: the defaults above */
 int tksmseq_map(tksmseq_ctx* ctx, const tksmseq_map_params* params, const char* reads_paths /* comma list */, const char* paf_out, tksmseq_map_info* info /* or NULL */);
+
+/* ---- map, alignment: base-level alignment of the written chains on the device (map -c: cg:Z:, NM:i:) ------------------------------------------
+ * Applies to every line map writes, primary and secondary, after the selection: a chain that is not written is never aligned.  These are
+ * this build's rules, not minimap2's: unit cost, a static band, no end extension, a waypoint at every anchor ("map").
+ *
+ * Waypoints.  A written chain has anchors a_0 .. a_{n-1}, a_i = (p_i, qa_i): the target position and the position in the read in the strand
+ * of rel.  Along a chain dt = p_{i+1} - p_i > 0 and dq = qa_{i+1} - qa_i > 0 (the chain rule).  The alignment passes through every
+ * (p_i, qa_i) and through (p_{n-1} + k, qa_{n-1} + k): n segments, n - 1 between consecutive anchors and the last anchor's k-mer
+ * (dt = dq = k).  It covers exactly [tstart, tend) x [qs, qe) of the chain.  Columns 1-9 and 12 and the tp, cm and s1 tags of a line are
+ * the same with and without alignment.
+ *
+ * Letters.  T[i] is the target letter at p + i.  Q[j] is the read letter at qa + j for rel = 0, and the complement of the read letter at
+ * qlen - 1 - (qa + j) for rel = 1.  Two letters match when both are ACGT and equal: a letter outside ACGT matches nothing, itself included.
+ *
+ * Segment.  A global, unit-cost alignment of T[0, dt) against Q[0, dq) inside a static band around the straight line between the two
+ * corners: cell (i, j), 0 <= i <= dt, 0 <= j <= dq, is allowed iff 2 |i dq - j dt| <= W (dt + dq) in 64-bit integers, W the band in
+ * [1, 63] (63).  D[0][0] = 0; otherwise D[i][j] is the minimum over the allowed predecessors of D[i-1][j-1] + (T[i-1] matches Q[j-1] ? 0 : 1),
+ * D[i-1][j] + 1 and D[i][j-1] + 1.  (dt, dq) is reachable for every W >= 1; an anti-diagonal i + j = s holds at most W + 1 allowed cells,
+ * with consecutive i; when 2 dt dq <= W (dt + dq) every cell is allowed and D is the Levenshtein distance.
+ *
+ * Traceback.  From (dt, dq), at each cell the first of these moves that reproduces D[i][j] from an allowed predecessor: the diagonal (a
+ * column = or X), then (i-1, j) (a column D, which consumes the target), then (i, j-1) (a column I, which consumes the read).
+ *
+ * Line.  The columns of the segments in chain order, run-length encoded: = X I D with eqx, else = and X merged into M.  Column 10 becomes
+ * the number of = columns and column 11 the number of all columns; after s1:i: come NM:i: (the sum of the segments' D[dt][dq], which is the
+ * number of X, I and D columns) and cg:Z: (the CIGAR).  The CIGAR consumes tend - tstart target letters and qend - qstart read letters;
+ * for rel = 1 it is in target order, like minimap2's.  Everything is integer: the same bytes on every run and for every chunk size.
+ *
+ * On the device: the anchors of a written chain are walked back from its end anchor, found by binary search in the sorted group, through
+ * the predecessors the chain kernel left; one wave aligns the segments of one line, lane i % 64 owning cell (i, s - i) of anti-diagonal s
+ * with its neighbours' values one lane below; two traceback bits per cell go to a store of the wave, which the same wave walks back; the
+ * columns are run-length encoded on the device.  A chunk whose alignment does not fit its budget of device bytes is split like one with
+ * too many anchors.
+ *
+ * TKSMSEQ_EINVAL: band outside [1, 63]; max_gap above 65536 with alignment (a segment's traceback store is sized by dt + dq).
+ * TKSMSEQ_ELIMIT: one read whose alignment does not fit a chunk's budget. */
+typedef struct tksmseq_align_params {
+    int32_t band;                    /* --align-band (63) */
+    int32_t eqx;                     /* --eqx: = and X in place of M */
+} tksmseq_align_params;
+typedef struct tksmseq_align_info {
+    uint64_t lines, segments, longest_segment /* dt + dq */, cells /* allowed cells computed */;
+    uint64_t columns, matches, mismatches, inserted, deleted;   /* columns = the sum of the other four */
+    float align_ms, reserved;        /* by HIP events, all chunks */
+} tksmseq_align_info;
+/* align NULL: exactly tksmseq_map.  align_info may be NULL. */
+int tksmseq_map_align(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const char* reads_paths, const char* paf_out,
+                      tksmseq_map_info* info, tksmseq_align_info* align_info);
 /* `tksm map`: -r REF.fa[.gz][,REF2.fa] --reads F.fq[.gz][,MORE] -o OUT.paf[.gz] [-k 15] [-w 10] [--max-occ 500] [--max-gap 5000] [--bandwidth 500]
- * [--min-count 3] [--min-score 40] [-p 0.8] [-N 5] [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L].  Exit codes as the other model
- * modules: 2 for a missing required option, an unknown option or a value out of range ("map: error: ..."), checked before any device is opened;
- * 1 for everything that fails later. */
+ * [--min-count 3] [--min-score 40] [-p 0.8] [-N 5] [-c [--eqx] [--align-band 63]] [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L].
+ * Exit codes as the other model modules: 2 for a missing required option, an unknown option or a value out of range ("map: error: ..."; also
+ * --eqx or --align-band without -c, and --max-gap above 65536 with -c), checked before any device is opened; 1 for everything that fails later. */
 int tksmseq_map_main(int argc, char** argv);
 
 /* The batch as MDF text, the way molecule_descriptor::operator<< writes it (src/interval.h:898-905): "+id<TAB>depth<TAB>comment",

@@ -1,6 +1,7 @@
-// map_api.cpp -- C-ABI of map: tksmseq_map (include/tksmseq.h).  The host reads and checks (ms_host.cpp's FASTQ reader, map_host.cpp), packs
+// map_api.cpp -- C-ABI of map: tksmseq_map and tksmseq_map_align (include/tksmseq.h).  The host reads and checks (ms_host.cpp's FASTQ reader, map_host.cpp), packs
 // the reads of a chunk and formats the PAF; the sketch of targets and reads, the index, the seeds, the chains and the choice of the lines run
-// on the device (map_kernels.hip, with the radix sort of abundance and the run kernels of model-sequence).
+// on the device (map_kernels.hip, with the radix sort of abundance and the run kernels of model-sequence), and with alignment the anchors of
+// the written chains, their banded alignment and the run-length code of its columns (map_align_kernels.hip).
 #include <chrono>
 #include <cstring>
 #include <string>
@@ -8,6 +9,7 @@
 
 #include "abund_host.h"
 #include "ctx.h"
+#include "map_align_kernels.h"
 #include "map_host.h"
 #include "map_kernels.h"
 #include "ms_kernels.h"
@@ -38,9 +40,13 @@ struct MapRun {
     tksmseq_map_params p;
     uint32_t permille;
     tksmseq_map_info info{};
+    bool aligned = false;
+    tksmseq_align_params ap{63, 0};
+    tksmseq_align_info ainfo{};
+    uint64_t align_budget = tkh::MAP_ALN_BYTES_MAX;
     hipEvent_t ev[2] = {};
     // the index: distinct hashes with their runs in the sorted entries
-    TmpBuf d_tvalid, d_dkey, d_dcount, d_dstart, d_iseq, d_ips;
+    TmpBuf d_tvalid, d_tseq, d_dkey, d_dcount, d_dstart, d_iseq, d_ips;
     uint32_t n_distinct = 0;
     uint64_t anchor_budget = MAP_ANCHORS_MAX;
     const tkh::MsReads* reads = nullptr;
@@ -48,16 +54,17 @@ struct MapRun {
     std::string paf;
 
     MapRun(tksmseq_ctx* c, const tksmseq_map_params& q)
-        : ctx(c), s(c->stream), p(q), permille(tkh::map_permille(q.secondary_ratio)), d_tvalid(s), d_dkey(s), d_dcount(s), d_dstart(s), d_iseq(s), d_ips(s) {}
+        : ctx(c), s(c->stream), p(q), permille(tkh::map_permille(q.secondary_ratio)), d_tvalid(s), d_tseq(s), d_dkey(s), d_dcount(s), d_dstart(s), d_iseq(s), d_ips(s) {}
     ~MapRun() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 
     int begin() { HIPCHK(ctx, hipEventRecord(ev[0], s)); return TKSMSEQ_OK; }
-    int end(int stage) {
+    int end(int stage) { return end(info.stage_ms[stage]); }
+    int end(float& sum) {
         HIPCHK(ctx, hipEventRecord(ev[1], s));
         HIPCHK(ctx, hipStreamSynchronize(s));
         float ms = 0.f;
         HIPCHK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
-        info.stage_ms[stage] += ms;
+        sum += ms;
         return TKSMSEQ_OK;
     }
     // out[0 .. n] = the exclusive scan of in[0 .. n)
@@ -109,6 +116,9 @@ struct MapRun {
 
     int build_index();
     int chunk(uint32_t r0, uint32_t r1);
+    int align(const std::vector<tkh::MapAlnLine>& lines, uint64_t segments, uint64_t col_words, bool alone, const std::string& first_name, const TmpBuf& d_codes,
+              const TmpBuf& d_valid, const TmpBuf& d_seqs, const TmpBuf& d_chain, const TmpBuf& d_list, const TmpBuf& d_gstart, const TmpBuf& d_k1f, const TmpBuf& d_pred,
+              std::vector<tkh::MapAlnOut>& outs, std::vector<uint64_t>& run_off, std::vector<uint64_t>& runs);
 };
 
 int MapRun::build_index() {
@@ -121,7 +131,7 @@ int MapRun::build_index() {
     }
     const tk::RefView R{ctx->d_packed.as<uint32_t>(), ctx->d_blocktab.as<uint32_t>(), ctx->d_pool.as<uint8_t>(), ctx->d_contigs.as<uint64_t>(), (uint32_t)n_t};
     const uint64_t n_vwords = ctx->total_alloc / 32;
-    TmpBuf d_tseq(s), d_tiles(s), d_hash(s), d_seq(s), d_ps(s);
+    TmpBuf d_tiles(s), d_hash(s), d_seq(s), d_ps(s);
     auto t0 = std::chrono::steady_clock::now();
     HIPCHK(ctx, upload(d_tseq, tseq.data(), tseq.size(), s));
     HIPCHK(ctx, d_tvalid.ensure(std::max<size_t>(n_vwords, 1) * 4));
@@ -276,20 +286,42 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
     if (nc) HIPCHK(ctx, hipMemcpyAsync(chains.data(), d_chain.p, (size_t)nc * sizeof(tk::MapChain), hipMemcpyDeviceToHost, s));
     if (int rc = end(ST_SELECT)) return rc;
 
-    // ---- the lines of the chunk
-    t0 = std::chrono::steady_clock::now();
+    // ---- the lines of the chunk: checked, with alignment aligned, then written
+    std::vector<tkh::MapAlnLine> alines;
+    std::vector<tkh::MapAlnOut> outs;
+    std::vector<uint64_t> run_off, runs;
+    uint64_t segments = 0, col_words = 0;
     for (uint32_t r = 0; r < n; r++) {
         if (n_lines[r] > slots) { ctx->err = "map: more lines for a read than it may have"; return TKSMSEQ_EDEVICE; }
-        if (!n_lines[r]) { info.unmapped++; continue; }
-        info.mapped++;
         for (uint32_t i = 0; i < n_lines[r]; i++) {
             const uint32_t c = lines[(size_t)r * slots + i];
             if (c >= nc || chains[c].read != r || (chains[c].tr >> 1) >= ctx->contig_names.size()) { ctx->err = "map: a line of a chain that does not exist"; return TKSMSEQ_EDEVICE; }
-            const uint32_t t = chains[c].tr >> 1;
-            tkh::map_paf_line(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], chains[c], i ? 0u : mapq[r], i == 0, paf);
+            if (aligned) tkh::map_align_add_line(c, chains[c], segments, col_words, alines);
+        }
+    }
+    if (aligned && !alines.empty())
+        if (int rc = align(alines, segments, col_words, n == 1, names[r0], d_codes, d_valid, d_seqs, d_chain, d_list, d_gstart, d_k1f, d_pred, outs, run_off, runs)) return rc;
+    t0 = std::chrono::steady_clock::now();
+    size_t at = 0;
+    for (uint32_t r = 0; r < n; r++) {
+        if (!n_lines[r]) { info.unmapped++; continue; }
+        info.mapped++;
+        for (uint32_t i = 0; i < n_lines[r]; i++, at++) {
+            const uint32_t c = lines[(size_t)r * slots + i], t = chains[c].tr >> 1;
+            if (aligned)
+                tkh::map_paf_line_aligned(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], chains[c], i ? 0u : mapq[r], i == 0, outs[at],
+                                          runs.data() + run_off[at], ap.eqx != 0, paf);
+            else
+                tkh::map_paf_line(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], chains[c], i ? 0u : mapq[r], i == 0, paf);
             info.lines++;
             if (i) info.secondary++;
         }
+    }
+    for (size_t l = 0; l < outs.size(); l++) {
+        ainfo.lines++;
+        ainfo.segments += chains[alines[l].chain].cnt;
+        ainfo.cells += outs[l].cells;
+        ainfo.columns += outs[l].ncols; ainfo.matches += outs[l].eq; ainfo.mismatches += outs[l].x; ainfo.inserted += outs[l].ins; ainfo.deleted += outs[l].del;
     }
     info.write_ms += ms_since(t0);
     info.upload_ms += upload_ms;
@@ -301,15 +333,77 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
     return TKSMSEQ_OK;
 }
 
+// the alignment of the chunk's lines: outs[l], and runs[run_off[l] .. run_off[l + 1]) of line l.  RC_SPLIT (no counter touched) when it does not
+// fit the budget and the chunk has more than one read
+int MapRun::align(const std::vector<tkh::MapAlnLine>& lines, uint64_t segments, uint64_t col_words, bool alone, const std::string& first_name, const TmpBuf& d_codes,
+                  const TmpBuf& d_valid, const TmpBuf& d_seqs, const TmpBuf& d_chain, const TmpBuf& d_list, const TmpBuf& d_gstart, const TmpBuf& d_k1f, const TmpBuf& d_pred,
+                  std::vector<tkh::MapAlnOut>& outs, std::vector<uint64_t>& run_off, std::vector<uint64_t>& runs) {
+    const uint32_t nl = (uint32_t)lines.size();
+    auto over = [&](const char* what) {
+        if (!alone) return (int)RC_SPLIT;
+        ctx->err = "map: the alignment of read " + first_name + " (" + what + ") does not fit the device bytes a chunk may take";
+        return (int)TKSMSEQ_ELIMIT;
+    };
+    if (tkh::map_align_fixed_bytes(nl, segments, col_words, 0) >= align_budget) return over("its anchors and columns");
+    TmpBuf d_lines(s), d_path(s), d_cols(s), d_out(s), d_words(s), d_tb(s), d_roff(s), d_runs(s);
+    if (int rc = begin()) return rc;
+    HIPCHK(ctx, upload(d_lines, lines.data(), lines.size(), s));
+    HIPCHK(ctx, d_path.ensure(segments * 8));
+    HIPCHK(ctx, d_cols.ensure(std::max<uint64_t>(col_words, 1) * 4));
+    HIPCHK(ctx, d_out.ensure((size_t)nl * sizeof(tk::MapAlnOut)));
+    HIPCHK(ctx, d_words.ensure(16));                               // longest, flags
+    HIPCHK(ctx, hipMemsetAsync(d_words.p, 0, 16, s));
+    uint32_t* words = d_words.as<uint32_t>();
+    HIPCHK(ctx, tk::launch_map_align_path(d_lines.as<tk::MapAlnLine>(), nl, d_chain.as<tk::MapChain>(), d_list.as<uint32_t>(), d_gstart.as<uint32_t>(), d_k1f.as<uint64_t>(),
+                                          d_pred.as<uint32_t>(), (uint32_t)p.k, d_path.as<uint64_t>(), words, words + 1, s));
+    uint32_t h_words[4] = {};
+    HIPCHK(ctx, hipMemcpyAsync(h_words, words, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (h_words[1]) { ctx->err = "map: the anchors of a written chain were not found again (flags " + std::to_string(h_words[1]) + ")"; return TKSMSEQ_EDEVICE; }
+    const uint32_t longest = h_words[0];
+    const uint32_t waves = tkh::map_align_waves(align_budget, tkh::map_align_fixed_bytes(nl, segments, col_words, 0), nl, longest);
+    if (!waves) { if (int rc = end(ainfo.align_ms)) return rc; return over("its traceback store"); }
+    const uint32_t tb_stride = longest + 1u;
+    HIPCHK(ctx, d_tb.ensure((size_t)waves * tb_stride * tkh::MAP_ALN_TB_BYTES));
+    const tk::MapAlnSeqs Q{ctx->d_packed.as<uint32_t>(), d_tvalid.as<uint32_t>(), d_tseq.as<tk::MapSeq>(), d_codes.as<uint32_t>(), d_valid.as<uint32_t>(), d_seqs.as<tk::MapSeq>()};
+    HIPCHK(ctx, tk::launch_map_align(d_lines.as<tk::MapAlnLine>(), nl, d_chain.as<tk::MapChain>(), d_path.as<uint64_t>(), Q, (uint32_t)p.k, (uint32_t)ap.band, ap.eqx ? 1u : 0u,
+                                     waves, tb_stride, d_tb.as<uint64_t>(), d_cols.as<uint32_t>(), d_out.as<tk::MapAlnOut>(), words + 1, s));
+    outs.resize(nl);
+    HIPCHK(ctx, hipMemcpyAsync(outs.data(), d_out.p, (size_t)nl * sizeof(tk::MapAlnOut), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(h_words, words, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (h_words[1]) { ctx->err = "map: an alignment left its segment (flags " + std::to_string(h_words[1]) + ")"; return TKSMSEQ_EDEVICE; }
+    run_off.assign((size_t)nl + 1, 0);
+    for (uint32_t l = 0; l < nl; l++) {
+        if (outs[l].ncols > lines[l].cap || outs[l].runs > outs[l].ncols) { ctx->err = "map: more columns than a line may have"; return TKSMSEQ_EDEVICE; }
+        run_off[l + 1] = run_off[l] + outs[l].runs;
+    }
+    const uint64_t n_runs = run_off[nl];
+    // (the traceback stores have gone by now: the runs take their place in the budget)
+    if (tkh::map_align_fixed_bytes(nl, segments, col_words, n_runs) >= align_budget) { if (int rc = end(ainfo.align_ms)) return rc; return over("its CIGAR"); }
+    d_tb.release();
+    HIPCHK(ctx, upload(d_roff, run_off.data(), run_off.size(), s));
+    HIPCHK(ctx, d_runs.ensure(std::max<uint64_t>(n_runs, 1) * 8));
+    HIPCHK(ctx, tk::launch_map_align_encode(d_lines.as<tk::MapAlnLine>(), nl, d_out.as<tk::MapAlnOut>(), d_cols.as<uint32_t>(), d_roff.as<uint64_t>(), ap.eqx ? 1u : 0u,
+                                            d_runs.as<uint64_t>(), s));
+    runs.resize((size_t)n_runs + 1);
+    if (n_runs) HIPCHK(ctx, hipMemcpyAsync(runs.data(), d_runs.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost, s));
+    if (int rc = end(ainfo.align_ms)) return rc;
+    ainfo.longest_segment = std::max<uint64_t>(ainfo.longest_segment, longest);
+    return TKSMSEQ_OK;
+}
+
 }  // namespace
 
-extern "C" int tksmseq_map(tksmseq_ctx* ctx, const tksmseq_map_params* params, const char* reads_paths, const char* paf_out, tksmseq_map_info* info_out) {
+extern "C" int tksmseq_map_align(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const char* reads_paths, const char* paf_out,
+                                 tksmseq_map_info* info_out, tksmseq_align_info* align_info) {
     if (!ctx) return TKSMSEQ_EINVAL;
     if (!reads_paths || !paf_out || !*paf_out) { ctx->err = "map: null argument"; return TKSMSEQ_EINVAL; }
     tksmseq_map_params p{};
     p.k = 15; p.w = 10; p.max_occ = 500; p.max_gap = 5000; p.bandwidth = 500; p.min_count = 3; p.min_score = 40; p.secondary_ratio = 0.8; p.max_secondary = 5;
     if (params) p = *params;
     if (!tkh::map_check_params(p, ctx->err)) return TKSMSEQ_EINVAL;
+    if (align && !tkh::map_check_align(p, *align, ctx->err)) return TKSMSEQ_EINVAL;
     if (ctx->contigs.empty()) { ctx->err = "map: the context has no reference"; return TKSMSEQ_EINVAL; }
     if (ctx->n_declared) { ctx->err = "map: the reference has contigs that are declared only"; return TKSMSEQ_EINVAL; }
     if (ctx->contigs.size() / 2 >= MAP_LIMIT) { ctx->err = "map: 2^31 targets or more"; return TKSMSEQ_ELIMIT; }
@@ -347,6 +441,7 @@ extern "C" int tksmseq_map(tksmseq_ctx* ctx, const tksmseq_map_params* params, c
 
     MapRun run(ctx, p);
     run.reads = &reads;
+    if (align) { run.aligned = true; run.ap = *align; }
     run.names.resize(n_reads);
     for (const auto& kv : reads.index) run.names[kv.second] = kv.first;
     run.info.reads = n_reads;
@@ -361,10 +456,13 @@ extern "C" int tksmseq_map(tksmseq_ctx* ctx, const tksmseq_map_params* params, c
         size_t free_b = 0, total_b = 0;
         HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
         run.anchor_budget = std::max(MAP_ANCHORS_MIN, std::min<uint64_t>(MAP_ANCHORS_MAX, free_b / 4 / MAP_ANCHOR_BYTES));
+        run.align_budget = std::min<uint64_t>(tkh::MAP_ALN_BYTES_MAX, std::max<uint64_t>(free_b / 4, 1ull << 20));
         if (!chunk_reads) {
             // per read: its packed letters, and about two minimizers in w + 1 positions through sketch and seed
             const uint64_t mean = reads.off[n_reads] / n_reads + 1;
             chunk_reads = std::max<uint64_t>(1ull << 10, std::min<uint64_t>(free_b / 8 / (mean * 16 + 64), 1ull << 20));
+            // with alignment about four bytes a base: a line's anchors (8 bytes every w + 1 bases or so), its columns and its runs
+            if (run.aligned) chunk_reads = std::max<uint64_t>(1ull << 10, std::min<uint64_t>(chunk_reads, run.align_budget / (mean * 4 + 64)));
         }
     }
     // chunks in input order; one with more anchors than the budget is halved and tried again
@@ -391,5 +489,10 @@ extern "C" int tksmseq_map(tksmseq_ctx* ctx, const tksmseq_map_params* params, c
     if (!tkh::write_abundance_file(paf_out, run.paf, e)) { ctx->err = "map: cannot write " + std::string(paf_out); return TKSMSEQ_EIO; }
     info.write_ms += ms_since(t0);
     if (info_out) *info_out = info;
+    if (align_info) *align_info = run.ainfo;
     return TKSMSEQ_OK;
+}
+
+extern "C" int tksmseq_map(tksmseq_ctx* ctx, const tksmseq_map_params* params, const char* reads_paths, const char* paf_out, tksmseq_map_info* info_out) {
+    return tksmseq_map_align(ctx, params, nullptr, reads_paths, paf_out, info_out, nullptr);
 }

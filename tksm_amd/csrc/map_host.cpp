@@ -53,11 +53,13 @@ void map_pack_reads(const MsReads& reads, uint32_t r0, uint32_t r1, std::vector<
     }
 }
 
-void map_paf_line(const std::string& qname, uint32_t qlen, const std::string& tname, uint64_t tlen, const MapChain& c, uint32_t mapq, bool primary, std::string& out) {
+namespace {
+// the fifteen fields both forms of a line share, without the line's end
+void paf_fields(const std::string& qname, uint32_t qlen, const std::string& tname, uint64_t tlen, const MapChain& c, uint32_t mapq, bool primary, uint32_t nmatch, uint32_t blen,
+                std::string& out) {
     const bool rel = (c.tr & 1u) != 0;
     // a reverse chain lies in the reverse-complemented read: the interval is given in the read as it was sequenced
     const uint32_t qstart = rel ? qlen - c.qe : c.qs, qend = rel ? qlen - c.qs : c.qe;
-    const uint32_t blen = std::max(c.tend - c.tstart, c.qe - c.qs);
     out += qname; out += '\t';
     out += std::to_string(qlen); out += '\t';
     out += std::to_string(qstart); out += '\t';
@@ -67,12 +69,49 @@ void map_paf_line(const std::string& qname, uint32_t qlen, const std::string& tn
     out += std::to_string(tlen); out += '\t';
     out += std::to_string(c.tstart); out += '\t';
     out += std::to_string(c.tend); out += '\t';
-    out += std::to_string(c.nmatch); out += '\t';
+    out += std::to_string(nmatch); out += '\t';
     out += std::to_string(blen); out += '\t';
     out += std::to_string(mapq); out += '\t';
     out += primary ? "tp:A:P" : "tp:A:S";
     out += "\tcm:i:"; out += std::to_string(c.cnt);
     out += "\ts1:i:"; out += std::to_string(c.score);
+}
+}  // namespace
+
+void map_paf_line(const std::string& qname, uint32_t qlen, const std::string& tname, uint64_t tlen, const MapChain& c, uint32_t mapq, bool primary, std::string& out) {
+    paf_fields(qname, qlen, tname, tlen, c, mapq, primary, c.nmatch, std::max(c.tend - c.tstart, c.qe - c.qs), out);
+    out += '\n';
+}
+
+bool map_check_align(const tksmseq_map_params& p, const tksmseq_align_params& a, std::string& err) {
+    if (a.band < 1 || a.band > 63) { err = "map: align band must be in [1, 63]"; return false; }
+    if (p.max_gap > MAP_ALN_MAX_GAP) { err = "map: max_gap must be at most 65536 with alignment"; return false; }
+    return true;
+}
+
+uint64_t map_align_fixed_bytes(uint64_t lines, uint64_t segments, uint64_t col_words, uint64_t runs) {
+    return lines * (sizeof(MapAlnLine) + sizeof(MapAlnOut) + 8) + 8 + segments * 8 + col_words * 4 + runs * 8;
+}
+
+uint32_t map_align_waves(uint64_t budget, uint64_t fixed, uint64_t lines, uint32_t longest) {
+    if (fixed >= budget) return 0;
+    const uint64_t per_wave = ((uint64_t)longest + 1) * MAP_ALN_TB_BYTES;
+    uint64_t waves = std::min<uint64_t>((budget - fixed) / per_wave, MAP_ALN_WAVES) / 4 * 4;
+    waves = std::min(waves, (lines + 3) / 4 * 4);
+    return (uint32_t)waves;
+}
+
+void map_paf_line_aligned(const std::string& qname, uint32_t qlen, const std::string& tname, uint64_t tlen, const MapChain& c, uint32_t mapq, bool primary,
+                          const MapAlnOut& a, const uint64_t* runs, bool eqx, std::string& out) {
+    paf_fields(qname, qlen, tname, tlen, c, mapq, primary, a.eq, a.ncols, out);
+    out += "\tNM:i:"; out += std::to_string((uint64_t)a.x + a.ins + a.del);
+    out += "\tcg:Z:";
+    const char* ops = eqx ? "=XID" : "MMID";
+    for (uint32_t r = 0; r < a.runs; r++) {
+        const uint64_t first = runs[r] >> 2, next = r + 1 < a.runs ? runs[r + 1] >> 2 : a.ncols;
+        out += std::to_string(next - first);
+        out += ops[runs[r] & 3u];
+    }
     out += '\n';
 }
 

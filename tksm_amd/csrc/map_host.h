@@ -35,4 +35,33 @@ void map_pack_reads(const MsReads& reads, uint32_t r0, uint32_t r1, std::vector<
 // one line of the PAF for a chain of read `qname` (qlen letters) on target `tname` (tlen letters)
 void map_paf_line(const std::string& qname, uint32_t qlen, const std::string& tname, uint64_t tlen, const MapChain& c, uint32_t mapq, bool primary, std::string& out);
 
+// ---- map -c ("map, alignment" in include/tksmseq.h; the kernels are described in map_align_kernels.h)
+constexpr int32_t MAP_ALN_MAX_GAP = 65536;         // a segment's traceback store is sized by dt + dq
+constexpr uint32_t MAP_ALN_TB_BYTES = 16;          // traceback bytes per anti-diagonal
+constexpr uint32_t MAP_ALN_WAVES = 8192;           // waves of the alignment at the most: eight on each of 1 024 SIMDs
+constexpr uint64_t MAP_ALN_BYTES_MAX = 128ull << 20;   // device bytes the alignment of one chunk may take at the most
+// a line before the alignment: its chain, where its anchors go, where its columns go (words, 16 columns a word) and how many it has room for
+struct MapAlnLine { uint32_t chain, seg_off, col_off, cap; };
+// ... and after: its columns by kind, the runs of its CIGAR, the allowed cells computed
+struct MapAlnOut { uint32_t ncols, eq, x, ins, del, runs; uint64_t cells; };
+
+// band in [1, 63]; with alignment max_gap is at most MAP_ALN_MAX_GAP; false: err says which
+bool map_check_align(const tksmseq_map_params& p, const tksmseq_align_params& a, std::string& err);
+// appends the line of chain c: where its anchors and columns go in a chunk that holds `segments` anchors and `col_words` words so far
+inline void map_align_add_line(uint32_t chain, const MapChain& c, uint64_t& segments, uint64_t& col_words, std::vector<MapAlnLine>& lines) {
+    const uint32_t cap = (c.tend - c.tstart) + (c.qe - c.qs);
+    lines.push_back({chain, (uint32_t)segments, (uint32_t)col_words, cap});
+    segments += c.cnt;
+    col_words += ((uint64_t)cap + 15) / 16;
+}
+// device bytes of a chunk's alignment without the traceback stores: lines, results, anchors, columns, run offsets and the runs (at most
+// a run a column is what the first sizing assumes; the exact count is known before the runs are written)
+uint64_t map_align_fixed_bytes(uint64_t lines, uint64_t segments, uint64_t col_words, uint64_t runs);
+// the waves that fit beside `fixed` bytes when a segment spans up to `longest` anti-diagonals: at most min(lines, MAP_ALN_WAVES), in whole
+// workgroups of four; 0: not even one workgroup fits in `budget`
+uint32_t map_align_waves(uint64_t budget, uint64_t fixed, uint64_t lines, uint32_t longest);
+// the aligned form of map_paf_line: columns 10 and 11 from the columns, NM:i: and cg:Z: appended.  runs[r] = first column << 2 | op.
+void map_paf_line_aligned(const std::string& qname, uint32_t qlen, const std::string& tname, uint64_t tlen, const MapChain& c, uint32_t mapq, bool primary,
+                          const MapAlnOut& a, const uint64_t* runs, bool eqx, std::string& out);
+
 }  // namespace tkh

@@ -1191,7 +1191,7 @@ extern "C" int tksmseq_model_sequence_main(int argc, char** argv) {
                          "usage: model-sequence --reference R[,R] --reads F[,F] --alignment PAF [--error-model OUT] [--qscore-model OUT] [--error-k 7] [--qscore-k 9]\n"
                          "                      [--max_alignments 0] [--max_alt 25] [--max_del 6] [--min_occur 100] [--max_output 10000] [--devices D] [--verbosity V]\n"
                          "                      [--log-file L]\n"
-                         "PAF: minimap2 -c output (cg:Z: tags); FASTQ and model files may be .gz; at least one of --error-model, --qscore-model\n"); return 0; }
+                         "PAF: `tksm map -c` or minimap2 -c output (cg:Z: tags); FASTQ and model files may be .gz; at least one of --error-model, --qscore-model\n"); return 0; }
     std::string missing;
     for (const auto& need : {std::make_pair(&reference, "--reference"), std::make_pair(&reads, "--reads"), std::make_pair(&paf, "--alignment")})
         if (need.first->empty()) missing += (missing.empty() ? "" : ", ") + std::string(need.second);
@@ -1306,19 +1306,23 @@ extern "C" int tksmseq_barcode_match_main(int argc, char** argv) {
     return rc ? 1 : 0;
 }
 
-// `tksm map`: the two minimap2 rules of the reference's workflow (Snakefile: minimap_cdna, minimap_cdna_for_badread_models) without -c: FASTQ
+// `tksm map`: the two minimap2 rules of the reference's workflow (Snakefile: minimap_cdna, minimap_cdna_for_badread_models), -c included: FASTQ
 // reads and a cDNA FASTA in, the PAF of `tksm abundance -p` and `tksm model-truncation -i` out (include/tksmseq.h).  Exit codes as the model
 // modules: 2 for a missing required option, an unknown option or a value out of range, all before any device is opened; 1 for everything later.
 extern "C" int tksmseq_map_main(int argc, char** argv) {
     Common c;
     tksmseq_map_params p{};
     p.k = 15; p.w = 10; p.max_occ = 500; p.max_gap = 5000; p.bandwidth = 500; p.min_count = 3; p.min_score = 40; p.secondary_ratio = 0.8; p.max_secondary = 5;
+    tksmseq_align_params ap{63, 0};
+    bool align = false, band_given = false;
     std::string reference, reads;
     std::string range_error;
     auto integer = [](const char* v, long long& out) { char* e = nullptr; out = strtoll(v, &e, 10); return e != v && !*e; };
     if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
             // (the common flags know -i, -s, --batch-bytes and --slice-molecules, which this module does not have)
             if (o == "-i" || o == "--input" || o == "-s" || o == "--seed" || o == "--batch-bytes" || o == "--slice-molecules") return NO_SUCH;
+            if (o == "-c") { align = true; return TOOK_FLAG; }
+            if (o == "--eqx") { ap.eqx = 1; return TOOK_FLAG; }
             long long iv = 0;
             auto ranged = [&](long long lo, long long hi, const char* what) {
                 if (!integer(v, iv)) return false;
@@ -1328,6 +1332,7 @@ extern "C" int tksmseq_map_main(int argc, char** argv) {
             };
             if ((o == "-r" || o == "--reference") && v) reference = v;
             else if (o == "--reads" && v) reads = v;
+            else if (o == "--align-band" && v) { if (!ranged(1, 63, "must be between 1 and 63")) return MALFORMED; ap.band = (int32_t)iv; band_given = true; }
             else if (o == "-k" && v) { if (!ranged(4, 28, "must be between 4 and 28")) return MALFORMED; p.k = (int32_t)iv; }
             else if (o == "-w" && v) { if (!ranged(1, 64, "must be between 1 and 64")) return MALFORMED; p.w = (int32_t)iv; }
             else if (o == "--max-occ" && v) { if (!ranged(1, 0x7FFFFFFF, "must be between 1 and 2147483647")) return MALFORMED; p.max_occ = (int32_t)iv; }
@@ -1347,15 +1352,17 @@ extern "C" int tksmseq_map_main(int argc, char** argv) {
             else return NOT_MINE;
             return TOOK_VALUE;
         })) return 2;
-    if (c.help) { printf("Maps long reads to transcripts by chains of minimizers: seeding and chaining only, the PAF that minimap2 writes without -c.\n"
+    if (c.help) { printf("Maps long reads to transcripts by chains of minimizers; with -c the written chains are aligned base by base (cg:Z: and NM:i: tags).\n"
                          "usage: map -r REF.fa[.gz][,REF2.fa] --reads F.fq[.gz][,MORE] -o OUT.paf[.gz] [-k 15] [-w 10] [--max-occ 500] [--max-gap 5000] [--bandwidth 500]\n"
-                         "           [--min-count 3] [--min-score 40] [-p 0.8] [-N 5] [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L]\n"
-                         "the output is the file `tksm abundance -p` and `tksm model-truncation -i` read; it has no cg:Z: tags (model-sequence needs them)\n"); return 0; }
+                         "           [--min-count 3] [--min-score 40] [-p 0.8] [-N 5] [-c [--eqx] [--align-band 63]] [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L]\n"
+                         "the output is the file `tksm abundance -p` and `tksm model-truncation -i` read; with -c also the one `tksm model-sequence --alignment` reads\n"); return 0; }
     std::string missing;
     for (const auto& need : {std::make_pair(&reference, "-r/--reference"), std::make_pair(&reads, "--reads"), std::make_pair(&c.output, "-o/--output")})
         if (need.first->empty()) missing += (missing.empty() ? "" : ", ") + std::string(need.second);
     if (!missing.empty()) { fprintf(stderr, "map: error: the following arguments are required: %s\n", missing.c_str()); return 2; }
     if (!range_error.empty()) { fprintf(stderr, "map: error: %s\n", range_error.c_str()); return 2; }
+    if (!align && (ap.eqx || band_given)) { fprintf(stderr, "map: error: %s needs -c\n", ap.eqx ? "--eqx" : "--align-band"); return 2; }
+    if (align && p.max_gap > 65536) { fprintf(stderr, "map: error: --max-gap must be at most 65536 with -c\n"); return 2; }
     Logger log;
     if (!open_log(c, "map", log)) return 1;
     tksmseq_ctx* ctx = nullptr;
@@ -1372,7 +1379,8 @@ extern "C" int tksmseq_map_main(int argc, char** argv) {
         a = b + 1;
     }
     tksmseq_map_info info{};
-    if (!rc) rc = tksmseq_map(ctx, &p, reads.c_str(), c.output.c_str(), &info);
+    tksmseq_align_info ainfo{};
+    if (!rc) rc = tksmseq_map_align(ctx, &p, align ? &ap : nullptr, reads.c_str(), c.output.c_str(), &info, &ainfo);
     if (rc) fprintf(stderr, "Error: %s\n", tksmseq_last_error(ctx));
     else {
         log.log(Logger::INFO, "map: %llu target minimizers under %llu hashes (%llu over --max-occ); %llu read minimizers, %llu anchors, %llu groups, %llu chained",
@@ -1382,6 +1390,11 @@ extern "C" int tksmseq_map_main(int argc, char** argv) {
                 (unsigned long long)info.reads, (unsigned long long)info.mapped, (unsigned long long)info.unmapped, (unsigned long long)info.lines,
                 (unsigned long long)info.secondary, (unsigned long long)info.chunks, c.output.c_str(),
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), info.device_ms);
+        if (align)
+            log.log(Logger::INFO, "map: %llu lines aligned in %llu segments (the longest spans %llu anti-diagonals), %llu cells: %llu columns, %llu =, %llu X, %llu I, %llu D (device %.2f ms)",
+                    (unsigned long long)ainfo.lines, (unsigned long long)ainfo.segments, (unsigned long long)ainfo.longest_segment, (unsigned long long)ainfo.cells,
+                    (unsigned long long)ainfo.columns, (unsigned long long)ainfo.matches, (unsigned long long)ainfo.mismatches, (unsigned long long)ainfo.inserted,
+                    (unsigned long long)ainfo.deleted, ainfo.align_ms);
     }
     tksmseq_destroy(ctx);
     return rc ? 1 : 0;

@@ -2,13 +2,16 @@
 """map: where the time goes on a generated transcriptome (profiles/map_times.log).
 
   python tools/map_times.py [--transcripts 20000] [--reads 200000] [--molecules 2000] [--out profiles/map_times.log]
+  python tools/map_times.py --align [--out profiles/map_align_times.log]
 
 Makes --transcripts random transcripts of 600 to 2 500 bases; every tenth shares its first half with the one before it (isoforms, so that
 secondary chains exist).  --reads reads are substrings of at least 200 bases on a random strand with 5 % substitutions.  Runs Sequencer.map
 once at the defaults and records the call's wall time split into reading, packing and uploads, device (HIP events, per stage) and writing.
 There is no earlier implementation of these rules to compare a time against.  Then, as an observation: --molecules molecules of 40
 transcripts made by transcribe on the device, sequenced as perfect and as Badread reads (nanopore2020, identity 84 / 99 / 5.5), and the
-share of them whose primary line names their own transcript.  One machine, one run."""
+share of them whose primary line names their own transcript.  With --align the same reads are mapped a second time with align=True (map -c)
+in place of that observation: the new stage's milliseconds beside the totals of both calls, the lines, segments and allowed cells, cells
+per second, and the device bytes the stage may take.  One machine, one run."""
 import argparse
 import os
 import sys
@@ -51,8 +54,10 @@ def main():
     ap.add_argument("--transcripts", type=int, default=20000)
     ap.add_argument("--reads", type=int, default=200000)
     ap.add_argument("--molecules", type=int, default=2000)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "map_times.log"))
+    ap.add_argument("--align", action="store_true", help="a second call with align=True in place of the observation on transcribed molecules")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "map_align_times.log" if a.align else "map_times.log")
     import numpy as np
     import torch  # noqa: F401  (its ROCm runtime has to be loaded before libtksmseq.so)
     from tksm_amd.sequence import Sequencer
@@ -102,6 +107,10 @@ def main():
         t0 = time.time()
         i = s.map(fq, paf)
         wall = time.time() - t0
+        if a.align:
+            t0 = time.time()
+            j = s.map(fq, os.path.join(d, "aligned.paf"), align=True)
+            wall_c = time.time() - t0
         s.close()
         say("== device (MI355X, 1 GPU; Sequencer.map at the defaults: k 15, w 10) ==")
         say(f"reference read and packed in {t_ref:.2f} s; map wall {wall:.2f} s: reading and parsing {i['read_ms'] / 1e3:.2f} s, packing and uploads {i['upload_ms'] / 1e3:.2f} s, "
@@ -120,6 +129,23 @@ def main():
         say(f"{i['reads'] / wall:.3g} reads per second of wall time, {total / (i['device_ms'] / 1e3):.3g} read bases per second of device time")
         say("There is no earlier implementation of these rules to compare a time against.")
         say()
+        if a.align:
+            al = j["align"]
+            say("== the same call with align=True (map -c at the defaults: band 63, M for = and X), after the call above on the same context ==")
+            say(f"map wall {wall_c:.2f} s: reading and parsing {j['read_ms'] / 1e3:.2f} s, packing and uploads {j['upload_ms'] / 1e3:.2f} s, device {j['device_ms'] / 1e3:.3f} s "
+                f"+ alignment {al['align_ms'] / 1e3:.3f} s, formatting and writing {j['write_ms'] / 1e3:.2f} s")
+            say(f"device by HIP events, {j['chunks']} chunk(s): " + ", ".join(f"{n} {ms:.1f} ms" for n, ms in zip(STAGES, j["stage_ms"])) + f", align {al['align_ms']:.1f} ms")
+            say(f"(plain call above: wall {wall:.2f} s, device {i['device_ms'] / 1e3:.3f} s in {i['chunks']} chunk(s))")
+            say(f"{al['lines']} lines aligned in {al['segments']} segments ({al['segments'] / max(1, al['lines']):.1f} a line, the longest spans {al['longest_segment']} "
+                f"anti-diagonals); {al['cells']} allowed cells, {al['cells'] / max(1e-9, al['align_ms'] / 1e3):.3g} cells per second of the stage")
+            say(f"{al['columns']} columns: {al['matches']} =, {al['mismatches']} X, {al['inserted']} I, {al['deleted']} D; "
+                f"{os.path.getsize(os.path.join(d, 'aligned.paf')) >> 20} MB of PAF against {os.path.getsize(paf) >> 20} MB")
+            say("extra device bytes: the stage's anchors, columns, traceback stores and runs take at most 128 MiB in a chunk (MAP_ALN_BYTES_MAX, map_host.h); "
+                "the reads of a chunk are sized to that, which is why this call has more chunks than the plain one")
+            say("There is no earlier implementation of these rules to compare a time against.")
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+            return
 
         # ---- observation: molecules made on the device, mapped back
         contigs, gtf, spliced = transcriptome(rs, acgt)
