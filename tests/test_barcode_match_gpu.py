@@ -185,6 +185,28 @@ def test_gz_inputs_two_read_files_and_gz_output(s, default_case, tmp_path):
         assert open(paths[k], "rb").read(2) == b"\x1f\x8b" and gzip.open(paths[k], "rt").read() == g["out"][k], k
 
 
+def test_reads_list_with_an_empty_entry_and_the_loaders_messages(s, tmp_path):
+    """the comma list of read files as the C-ABI takes it: "a.fq,,b.fq" is the one file with both; the loader's messages word for word"""
+    from tksm_amd import _lib as L
+    from tksm_amd.sequence import TksmSeqError
+    g = B.generate(tmp_path, seed=3, n_barcodes=8, n_seen=4)
+    reads = head_fastq(g["reads"], 30, str(tmp_path / "thirty.fq"))
+    lines = open(reads).read().split("\n")
+    (tmp_path / "a.fq").write_text("\n".join(lines[:4 * 13]) + "\n")
+    (tmp_path / "b.fq").write_text("\n".join(lines[4 * 13:]))
+    one = device(s, reads, g["whitelist"], tmp_path, tag="one")
+    both = device(s, [tmp_path / "a.fq", "", tmp_path / "b.fq"], g["whitelist"], tmp_path, tag="list")
+    same(one, B.run(reads, g["whitelist"]))
+    assert all(both[k] == one[k] for k in FILES) and one["info"]["reads"] == 30
+    (tmp_path / "empty.fq").write_text("\n")
+    (tmp_path / "bad.fq").write_text("@a\nACGT\n+\nIII\n")
+    for reads, message in ((tmp_path / "empty.fq", f"barcode-match: no reads in {tmp_path / 'empty.fq'}"),
+                           ([tmp_path / "a.fq", tmp_path / "bad.fq"], f"{tmp_path / 'bad.fq'}: FASTQ record 1: sequence and quality differ in length")):
+        with pytest.raises(TksmSeqError) as e:
+            s.barcode_match(reads, g["whitelist"], tmp_path / "never.tsv")
+        assert e.value.code == L.EINVAL and str(e.value) == f"tksmseq error {L.EINVAL}: {message}" and not (tmp_path / "never.tsv").exists()
+
+
 def test_cli_against_the_python_call_and_the_hand_counted_case(s, default_case, tmp_path):
     g = default_case
     out = {k: str(tmp_path / f"cli.{k}.tsv") for k in FILES}

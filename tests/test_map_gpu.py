@@ -281,6 +281,32 @@ def test_error_codes(default_case, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ the round trip
+def test_reads_list_with_an_empty_entry_and_the_loaders_messages(tmp_path):
+    """the comma list of read files as the C-ABI takes it: "a.fq,,b.fq" is the one file with both; the loader's messages word for word"""
+    from tksm_amd import _lib
+    from tksm_amd.sequence import Sequencer, TksmSeqError
+    g = M.generate(tmp_path, seed=3, n_targets=2, n_reads=20, lengths=(300, 500), min_read=100)
+    qa, qb = M.write_fastq(tmp_path / "a.fq", g["read_list"][:7]), M.write_fastq(tmp_path / "b.fq", g["read_list"][7:])
+    (tmp_path / "empty.fq").write_text("\n\n")
+    (tmp_path / "bad.fq").write_text("@r\nACGT\n+\nII\n")
+    s = Sequencer(0)
+    try:
+        for name, seq in g["targets"]:
+            s.add_contig(name, seq)
+        s.map(g["reads"], tmp_path / "one.paf")
+        s.map([qa, "", qb], tmp_path / "list.paf")
+        assert (tmp_path / "list.paf").read_bytes() == (tmp_path / "one.paf").read_bytes() and (tmp_path / "one.paf").read_text() == M.map_reads(g["targets"], g["read_list"])["paf"]
+        with pytest.raises(TksmSeqError) as e:
+            s.map(tmp_path / "empty.fq", tmp_path / "o.paf")
+        assert e.value.code == _lib.EINVAL and str(e.value) == f"tksmseq error {_lib.EINVAL}: map: no reads in {tmp_path / 'empty.fq'}"
+        with pytest.raises(TksmSeqError) as e:
+            s.map([qa, tmp_path / "bad.fq"], tmp_path / "o.paf")
+        assert e.value.code == _lib.EINVAL and str(e.value) == f"tksmseq error {_lib.EINVAL}: {tmp_path / 'bad.fq'}: FASTQ record 1: sequence and quality differ in length"
+        assert not (tmp_path / "o.paf").exists()
+    finally:
+        s.close()
+
+
 def transcriptome(rs, n=40):
     """n transcripts of 600 - 2 500 letters, two exons each on a contig of its own, half of them on the minus strand: (genome contigs,
     GTF text, [(transcript id, spliced letters)])"""

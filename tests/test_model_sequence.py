@@ -168,6 +168,24 @@ def test_host_readers_on_malformed_input(host_program):
     assert set(cases) == ok | set(why) | {"second_line_bad"}
 
 
+def test_fastq_list_loader_under_sanitizers(host_program):
+    """load_fastq_list (ms_host.cpp), the one loader of model-sequence, barcode-match and map: the library's return codes: 0 ok, 2 I/O (EIO), 1 malformed (EINVAL), 6 limit (ELIMIT)"""
+    d, out = host_program
+    cases = {c.split(" ")[0]: c.split(" ", 4) for c in out["list_case"]}
+    assert set(cases) == {"two", "empty_entries", "empty", "comma", "missing", "cut", "duplicate", "gz", "limit_after_second", "limit_after_first"}
+    for name in ("two", "empty_entries", "gz"):                   # the same MsReads as the two files' text laid end to end; empty entries are skipped
+        assert cases[name][1:] == ["0", "4", "1", ""], name
+    assert cases["empty"][1:] == ["0", "0", "1", ""] and cases["comma"][1:] == ["0", "0", "1", ""]
+    # a missing second file: abund_read_file's own message, and the first file's reads stay appended
+    assert cases["missing"][1:4] == ["2", "2", "1"] and cases["missing"][4] == out["list_io_message"][0] and "nosuch.fq" in cases["missing"][4]
+    assert cases["cut"][1:4] == ["1", "3", "-1"] and cases["cut"][4].startswith(f"{d}/cut.fq: FASTQ record 2: ") and "ends inside the record" in cases["cut"][4]
+    assert cases["duplicate"][1:4] == ["1", "3", "-1"] and cases["duplicate"][4] == f"{d}/dup.fq: FASTQ record 2: a read of this name came before"
+    # the count after every file (map, barcode-match): the limit is met by the file that brings the reads to it, what was read stays
+    # (no message of the loader's: the two callers that count word the limit themselves)
+    assert cases["limit_after_second"][1:] == ["6", "4", "1", ""] and cases["limit_after_first"][1:] == ["6", "2", "1", ""]
+    assert out["list_names"] == ["a1 a2 b1 b2 "]
+
+
 def test_host_writers_under_sanitizers(host_program):
     d, out = host_program
     assert out["error_lines"] == ["64"] and out["select"] == ["1 3"] and out["select_all"] == ["1 4"]

@@ -145,6 +145,34 @@ def test_no_insertion_column_is_refused(tmp_path):
         s.close()
 
 
+def test_reads_list_with_an_empty_entry_and_the_loaders_messages(tmp_path):
+    """the comma list of read files as the C-ABI takes it: "a.fq,,b.fq" is the one file with both; the loader's messages word for word"""
+    from tksm_amd.sequence import Sequencer, TksmSeqError
+    g = M.generate(tmp_path, seed=5, n_alignments=20, extra_columns=(), group=0)
+    lines = open(g["reads"]).read().split("\n")
+    half = 4 * (len(lines) // 8)
+    (tmp_path / "a.fq").write_text("\n".join(lines[:half]) + "\n")
+    (tmp_path / "b.fq").write_text("\n".join(lines[half:]))
+    (tmp_path / "bad.fq").write_text("@r\nACGT\n+\nII\n")
+    s = Sequencer(0)
+    try:
+        s.get_reference_seqs([g["reference"]])
+        s.model_sequence(g["reads"], g["alignment"], tmp_path / "e1", tmp_path / "q1", min_occur=1)
+        s.model_sequence([tmp_path / "a.fq", "", tmp_path / "b.fq"], g["alignment"], tmp_path / "e2", tmp_path / "q2", min_occur=1)
+        want = M.run(g["reference"], g["reads"], g["alignment"], min_occur=1)
+        assert (tmp_path / "e1").read_text() == want["error"] and (tmp_path / "q1").read_text() == want["qscore"]
+        assert (tmp_path / "e2").read_bytes() == (tmp_path / "e1").read_bytes() and (tmp_path / "q2").read_bytes() == (tmp_path / "q1").read_bytes()
+        with pytest.raises(TksmSeqError) as err:
+            s.model_sequence([tmp_path / "a.fq", tmp_path / "bad.fq"], g["alignment"], tmp_path / "e3", tmp_path / "q3")
+        assert err.value.code == 1 and str(err.value) == f"tksmseq error 1: {tmp_path / 'bad.fq'}: FASTQ record 1: sequence and quality differ in length"
+        with pytest.raises(TksmSeqError) as err:
+            s.model_sequence(g["reads"], g["alignment"], None, None)
+        assert err.value.code == 1 and str(err.value) == "tksmseq error 1: model-sequence: neither an error-model nor a q-score-model output"
+        assert not (tmp_path / "e3").exists() and not (tmp_path / "q3").exists()
+    finally:
+        s.close()
+
+
 def test_built_models_drive_the_simulator_like_the_oracle(tmp_path, po):
     """the existing parity route on a new model file: 32 reads of 300 bases, records byte for byte.  The reads here carry single-base
     errors at 4 %: the simulator's loader holds at most 5 bases per slot of an alternative (models.cpp), which runs of insertions next to

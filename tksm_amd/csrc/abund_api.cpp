@@ -9,6 +9,7 @@
 #include "abund_host.h"
 #include "abund_kernels.h"
 #include "ctx.h"
+#include "tool_run.h"
 
 struct tksmseq_abundance_result {
     std::vector<std::string> tnames, rnames, cells;
@@ -27,18 +28,7 @@ namespace {
 
 constexpr uint64_t ABUND_LIMIT = 1ull << 31;
 
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
-int bits_for(uint64_t n_values) { int b = 1; while (b < 64 && (1ull << b) < n_values) b++; return b; }
-
-int scan_u64(tksmseq_ctx* ctx, const uint64_t* in, uint64_t* out, uint64_t n) {
-    HIPCHK(ctx, ctx->w_scan.ensure(tk::scan_temp_bytes(n) + 64));
-    HIPCHK(ctx, tk::launch_scan(in, out, n, ctx->w_scan.p, ctx->w_scan.cap, ctx->stream));
-    return TKSMSEQ_OK;
-}
+int bits_for(uint64_t n_values) { int b = 1; while (b < 64 && (1ull << b) < n_values) b++; return b; }      // bits that tell n_values values apart (not map_api.cpp's bit_length)
 
 // a segmented sum over perm: the chunk list (made once per index) and the buffers of a round
 struct SegSum {
@@ -54,8 +44,7 @@ struct SegSum {
         HIPCHK(ctx, tk::launch_abund_chunk_counts(off, n_seg, counts.as<uint64_t>(), s));
         if (int rc = scan_u64(ctx, counts.as<uint64_t>(), chunk_off.as<uint64_t>(), n_seg)) return rc;
         uint64_t nc = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&nc, chunk_off.as<uint64_t>() + n_seg, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
+        if (int rc = fetch_u64(ctx, chunk_off.as<uint64_t>() + n_seg, nc)) return rc;
         if (nc >= (1ull << 32)) { ctx->err = "abundance: 2^32 chunks or more"; return TKSMSEQ_ELIMIT; }
         n_chunks = (uint32_t)nc;
         HIPCHK(ctx, chunk_seg.ensure(((size_t)n_chunks + 1) * 4));
@@ -73,18 +62,6 @@ struct SegSum {
         return TKSMSEQ_OK;
     }
 };
-
-template <class T>
-hipError_t upload(TmpBuf& d, const std::vector<T>& v, hipStream_t s) {
-    hipError_t e = d.ensure(std::max<size_t>(v.size(), 1) * sizeof(T));
-    if (e != hipSuccess || v.empty()) return e;
-    return hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s);
-}
-template <class T>
-hipError_t download(std::vector<T>& v, const TmpBuf& d, size_t n, hipStream_t s) {
-    v.resize(n);
-    return n ? hipMemcpyAsync(v.data(), d.p, n * sizeof(T), hipMemcpyDeviceToHost, s) : hipSuccess;
-}
 
 // the argument checks of parse_args (:121-138)
 int check_params(tksmseq_ctx* ctx, const tksmseq_abundance_params* p) {
@@ -169,9 +146,8 @@ extern "C" int tksmseq_abundance(tksmseq_ctx* ctx, const tksmseq_abundance_param
 
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    EventPair ev;
-    HIPCHK(ctx, hipEventCreate(&ev.a));
-    HIPCHK(ctx, hipEventCreate(&ev.b));
+    Events<2> ev;
+    if (int rc = ev.create(ctx)) return rc;
     TmpBuf d_rec_off(s), d_tid(s), d_tstart(s), d_nmatch(s), d_blen(s), d_qlen(s), d_read_cell(s), d_cdf(s), d_cell_of(s);
     HIPCHK(ctx, upload(d_rec_off, in.rec_off, s));
     HIPCHK(ctx, upload(d_tid, in.tid, s));
@@ -181,7 +157,7 @@ extern "C" int tksmseq_abundance(tksmseq_ctx* ctx, const tksmseq_abundance_param
     HIPCHK(ctx, upload(d_qlen, in.qlen, s));
     if (lr_mode) HIPCHK(ctx, upload(d_read_cell, read_cell, s));
     if (cb_mode) { HIPCHK(ctx, upload(d_cdf, cdf, s)); HIPCHK(ctx, upload(d_cell_of, cell_of, s)); }
-    HIPCHK(ctx, hipEventRecord(ev.a, s));
+    if (int rc = ev.mark(ctx, 0)) return rc;
 
     // ---- get_compatibility: count, scan, write
     TmpBuf d_best(s), d_packed(s), d_scanned(s), d_bad(s);
@@ -264,8 +240,7 @@ extern "C" int tksmseq_abundance(tksmseq_ctx* ctx, const tksmseq_abundance_param
         HIPCHK(ctx, tk::launch_abund_seg_flags(d_skeys.as<uint64_t>(), n_hits, d_flag.as<uint64_t>(), s));
         if (int rc = scan_u64(ctx, d_flag.as<uint64_t>(), d_fscan.as<uint64_t>(), n_hits)) return rc;
         uint64_t ns = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&ns, d_fscan.as<uint64_t>() + n_hits, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
+        if (int rc = fetch_u64(ctx, d_fscan.as<uint64_t>() + n_hits, ns)) return rc;
         if (ns == 0 || ns > n_hits) { ctx->err = "abundance: the split counted more (transcript, cell) pairs than hits"; return TKSMSEQ_EDEVICE; }
         n_seg = (uint32_t)ns;
         HIPCHK(ctx, tk::launch_abund_seg_write(d_skeys.as<uint64_t>(), n_hits, d_flag.as<uint64_t>(), d_fscan.as<uint64_t>(), d_soff.as<uint32_t>(), d_segkey.as<uint64_t>(), s));
@@ -280,7 +255,7 @@ extern "C" int tksmseq_abundance(tksmseq_ctx* ctx, const tksmseq_abundance_param
     HIPCHK(ctx, d_order.ensure((size_t)n_seg * 4));
     HIPCHK(ctx, tk::launch_abund_ranks(split_perm, split_off, n_seg, d_rank.as<uint32_t>(), s));
     if (int rc = sort_pairs<uint32_t>(ctx, tk::abund_sort_u32, d_rank.as<uint32_t>(), d_rank_sorted.as<uint32_t>(), d_order.as<uint32_t>(), n_seg, 32)) return rc;
-    HIPCHK(ctx, hipEventRecord(ev.b, s));
+    if (int rc = ev.mark(ctx, 1)) return rc;
 
     std::vector<uint32_t> order, rank_sorted;
     std::vector<uint64_t> seg_key;
@@ -290,7 +265,7 @@ extern "C" int tksmseq_abundance(tksmseq_ctx* ctx, const tksmseq_abundance_param
     HIPCHK(ctx, download(rank_sorted, d_rank_sorted, n_seg, s));
     HIPCHK(ctx, download(sums, split->sum, n_seg, s));
     if (!one_cell) HIPCHK(ctx, download(seg_key, d_segkey, n_seg, s));
-    HIPCHK(ctx, hipMemcpyAsync(&total, split->total.p, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, download(&total, split->total, 1, s));
     HIPCHK(ctx, download(R->abundance, d_abund, T, s));
     HIPCHK(ctx, download(R->surv_read, d_surv, n_surv, s));
     if (p->keep_hits) {
@@ -302,7 +277,7 @@ extern "C" int tksmseq_abundance(tksmseq_ctx* ctx, const tksmseq_abundance_param
         R->have_hits = true;
     }
     HIPCHK(ctx, hipStreamSynchronize(s));
-    HIPCHK(ctx, hipEventElapsedTime(&R->device_ms, ev.a, ev.b));
+    if (int rc = ev.add(ctx, 0, R->device_ms)) return rc;
     for (uint32_t r : R->surv_read) if (r < n_reads) R->kept[r] = 1;
     for (uint32_t j = 0; j < n_seg && rank_sorted[j] != tk::ABUND_NO_READ; j++) {
         const uint32_t g = order[j];

@@ -8,6 +8,7 @@
 #include "ctx.h"
 #include "kde_host.h"
 #include "kde_kernels.h"
+#include "tool_run.h"
 
 namespace {
 
@@ -55,18 +56,15 @@ extern "C" int tksmseq_kde_grid(tksmseq_ctx* ctx, const double* xy, uint64_t n, 
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     TmpBuf d_xy(s), d_px(s), d_py(s), d_partial(s), d_out(s);
-    HIPCHK(ctx, d_xy.ensure(n * 16));
-    HIPCHK(ctx, d_px.ensure((size_t)gx * 8));
-    HIPCHK(ctx, d_py.ensure((size_t)gy * 8));
+    HIPCHK(ctx, upload(d_xy, xy, 2 * n, s));
+    HIPCHK(ctx, upload(d_px, px, gx, s));
+    HIPCHK(ctx, upload(d_py, py, gy, s));
     HIPCHK(ctx, d_partial.ensure(n_chunks * cells * 8));
     HIPCHK(ctx, d_out.ensure(cells * 8));
-    HIPCHK(ctx, hipMemcpyAsync(d_xy.p, xy, n * 16, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(d_px.p, px, (size_t)gx * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(d_py.p, py, (size_t)gy * 8, hipMemcpyHostToDevice, s));
     HIPCHK(ctx, tk::launch_kde_grid(d_xy.as<double>(), n, d_px.as<double>(), gx, d_py.as<double>(), gy, 1.0 / bandwidth, chunk, d_partial.as<double>(), s));
     const double scale = 1.0 / ((double)n * (KDE_TWO_PI * bandwidth * bandwidth));
     HIPCHK(ctx, tk::launch_kde_sum(d_partial.as<double>(), n_chunks, cells, scale, d_out.as<double>(), s));
-    HIPCHK(ctx, hipMemcpyAsync(out, d_out.p, cells * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, download(out, d_out, cells, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return TKSMSEQ_OK;
 }
@@ -106,8 +104,8 @@ extern "C" int tksmseq_kde_cv_bandwidth(tksmseq_ctx* ctx, const double* xy, uint
             HIPCHK(ctx, tk::launch_kde_cv_min(d_pts.as<double>(), m, fb[1], fb[2], u0, std::min(m, u0 + tk::KDE_CV_SLAB), d_min.as<double>(), s));
         for (uint32_t u0 = 0; u0 < m; u0 += tk::KDE_CV_SLAB)
             HIPCHK(ctx, tk::launch_kde_cv_sum(d_pts.as<double>(), m, fb[1], fb[2], u0, std::min(m, u0 + tk::KDE_CV_SLAB), d_min.as<double>(), sc, d_sums.as<double>(), s));
-        HIPCHK(ctx, hipMemcpyAsync(h_min.data(), d_min.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(h_sums.data(), d_sums.p, (size_t)m * 8 * tk::KDE_N_BW, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, download(h_min.data(), d_min, m, s));
+        HIPCHK(ctx, download(h_sums.data(), d_sums, (size_t)m * tk::KDE_N_BW, s));
         HIPCHK(ctx, hipStreamSynchronize(s));
         // the score of a fold and bandwidth: its test points in order, then the normalisation; the mean over the folds in fold order
         double mean[tk::KDE_N_BW];

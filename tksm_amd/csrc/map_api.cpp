@@ -2,7 +2,6 @@
 // the reads of a chunk and formats the PAF; the sketch of targets and reads, the index, the seeds, the chains and the choice of the lines run
 // on the device (map_kernels.hip, with the radix sort of abundance and the run kernels of model-sequence), and with alignment the anchors of
 // the written chains, their banded alignment and the run-length code of its columns (map_align_kernels.hip).
-#include <chrono>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -13,6 +12,7 @@
 #include "map_host.h"
 #include "map_kernels.h"
 #include "ms_kernels.h"
+#include "tool_run.h"
 
 namespace {
 
@@ -22,16 +22,11 @@ constexpr uint64_t MAP_ANCHOR_BYTES = 128;                                      
 enum { ST_SKETCH, ST_INDEX, ST_SEED, ST_CHAIN, ST_SELECT };
 constexpr int RC_SPLIT = -1000;                                                      // (internal) the chunk has more anchors than the budget
 
-double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+int bit_length(uint64_t n) { int b = 1; while (b < 64 && (n >> b)) b++; return b; }    // the bits of n itself (at least 1).  Not abund_api.cpp's bits_for, which holds n VALUES
 
-template <class T>
-hipError_t upload(TmpBuf& d, const T* v, size_t n, hipStream_t s) {
-    hipError_t e = d.ensure(std::max<size_t>(n, 1) * sizeof(T));
-    if (e != hipSuccess || !n) return e;
-    return hipMemcpyAsync(d.p, v, n * sizeof(T), hipMemcpyHostToDevice, s);
-}
-
-int bits_for(uint64_t n) { int b = 1; while (b < 64 && (n >> b)) b++; return b; }      // bits that hold every value below n (at least 1)
+// what align reads of a chunk, and what it hands back: outs[l], and runs[run_off[l] .. run_off[l + 1]) of line l
+struct MapChunkBufs { const TmpBuf &d_codes, &d_valid, &d_seqs, &d_chain, &d_list, &d_gstart, &d_k1f, &d_pred; };
+struct MapAligned { std::vector<tkh::MapAlnOut> outs; std::vector<uint64_t> run_off, runs; };
 
 // the state of one call
 struct MapRun {
@@ -44,7 +39,7 @@ struct MapRun {
     tksmseq_align_params ap{63, 0};
     tksmseq_align_info ainfo{};
     uint64_t align_budget = tkh::MAP_ALN_BYTES_MAX;
-    hipEvent_t ev[2] = {};
+    Events<2> ev;
     // the index: distinct hashes with their runs in the sorted entries
     TmpBuf d_tvalid, d_tseq, d_dkey, d_dcount, d_dstart, d_iseq, d_ips;
     uint32_t n_distinct = 0;
@@ -55,28 +50,14 @@ struct MapRun {
 
     MapRun(tksmseq_ctx* c, const tksmseq_map_params& q)
         : ctx(c), s(c->stream), p(q), permille(tkh::map_permille(q.secondary_ratio)), d_tvalid(s), d_tseq(s), d_dkey(s), d_dcount(s), d_dstart(s), d_iseq(s), d_ips(s) {}
-    ~MapRun() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 
-    int begin() { HIPCHK(ctx, hipEventRecord(ev[0], s)); return TKSMSEQ_OK; }
+    // a stage's device time: one synchronization per stage
+    int begin() { return ev.mark(ctx, 0); }
     int end(int stage) { return end(info.stage_ms[stage]); }
     int end(float& sum) {
-        HIPCHK(ctx, hipEventRecord(ev[1], s));
+        if (int rc = ev.mark(ctx, 1)) return rc;
         HIPCHK(ctx, hipStreamSynchronize(s));
-        float ms = 0.f;
-        HIPCHK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
-        sum += ms;
-        return TKSMSEQ_OK;
-    }
-    // out[0 .. n] = the exclusive scan of in[0 .. n)
-    int scan(const uint64_t* in, uint64_t* out, uint64_t n) {
-        HIPCHK(ctx, ctx->w_scan.ensure(tk::scan_temp_bytes(n) + 64));
-        HIPCHK(ctx, tk::launch_scan(in, out, n, ctx->w_scan.p, ctx->w_scan.cap, s));
-        return TKSMSEQ_OK;
-    }
-    int fetch(const uint64_t* d, uint64_t& v) {
-        HIPCHK(ctx, hipMemcpyAsync(&v, d, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        return TKSMSEQ_OK;
+        return ev.add(ctx, 0, sum);
     }
     // the minimizers of the tiled sequences: count, scan, write.  n_out minimizers in d_hash / d_seq / d_ps
     int sketch(const uint32_t* codes, const uint32_t* valid, const tk::MapSeq* seqs, const std::vector<tkh::MapTile>& tiles, TmpBuf& d_tiles, TmpBuf& d_hash, TmpBuf& d_seq,
@@ -91,8 +72,8 @@ struct MapRun {
         HIPCHK(ctx, d_off.ensure(((size_t)n_tiles + 1) * 8));
         const tk::MapSketch S{codes, valid, seqs, d_tiles.as<tk::MapTile>(), n_tiles, (uint32_t)p.k, (uint32_t)p.w};
         HIPCHK(ctx, tk::launch_map_sketch_count(S, d_cnt.as<uint64_t>(), s));
-        if (int rc = scan(d_cnt.as<uint64_t>(), d_off.as<uint64_t>(), n_tiles)) return rc;
-        if (int rc = fetch(d_off.as<uint64_t>() + n_tiles, n_out)) return rc;
+        if (int rc = scan_u64(ctx, d_cnt.as<uint64_t>(), d_off.as<uint64_t>(), n_tiles)) return rc;
+        if (int rc = fetch_u64(ctx, d_off.as<uint64_t>() + n_tiles, n_out)) return rc;
         if (n_out >= (1ull << 32)) { ctx->err = "map: 2^32 minimizers or more in one pass"; return TKSMSEQ_ELIMIT; }
         HIPCHK(ctx, d_hash.ensure(std::max<size_t>(n_out, 1) * 8));
         HIPCHK(ctx, d_seq.ensure(std::max<size_t>(n_out, 1) * 4));
@@ -101,24 +82,10 @@ struct MapRun {
         HIPCHK(ctx, hipStreamSynchronize(s));                   // (d_cnt and d_off go with this scope)
         return TKSMSEQ_OK;
     }
-    // keys[0 .. n) sorted: start[run] of the runs of equal keys, start[n_runs] = n
-    int runs(const uint64_t* sorted, uint32_t n, TmpBuf& d_start, uint64_t& n_runs) {
-        TmpBuf d_flag(s), d_scanned(s), d_info(s);
-        HIPCHK(ctx, d_flag.ensure(((size_t)n + 1) * 8));
-        HIPCHK(ctx, d_scanned.ensure(((size_t)n + 1) * 8));
-        HIPCHK(ctx, d_info.ensure(16));
-        HIPCHK(ctx, d_start.ensure(((size_t)n + 2) * 4));
-        HIPCHK(ctx, tk::launch_ms_run_flags(sorted, nullptr, n, d_flag.as<uint64_t>(), s));
-        if (int rc = scan(d_flag.as<uint64_t>(), d_scanned.as<uint64_t>(), n)) return rc;
-        HIPCHK(ctx, tk::launch_ms_run_starts(sorted, n, d_flag.as<uint64_t>(), d_scanned.as<uint64_t>(), d_start.as<uint32_t>(), d_info.as<uint64_t>(), s));
-        return fetch(d_info.as<uint64_t>(), n_runs);
-    }
 
     int build_index();
     int chunk(uint32_t r0, uint32_t r1);
-    int align(const std::vector<tkh::MapAlnLine>& lines, uint64_t segments, uint64_t col_words, bool alone, const std::string& first_name, const TmpBuf& d_codes,
-              const TmpBuf& d_valid, const TmpBuf& d_seqs, const TmpBuf& d_chain, const TmpBuf& d_list, const TmpBuf& d_gstart, const TmpBuf& d_k1f, const TmpBuf& d_pred,
-              std::vector<tkh::MapAlnOut>& outs, std::vector<uint64_t>& run_off, std::vector<uint64_t>& runs);
+    int align(const std::vector<tkh::MapAlnLine>& lines, uint64_t segments, uint64_t col_words, bool alone, const std::string& first_name, const MapChunkBufs& c, MapAligned& a);
 };
 
 int MapRun::build_index() {
@@ -159,8 +126,9 @@ int MapRun::build_index() {
     if (int rc = sort_pairs<uint64_t>(ctx, tk::abund_sort_u64, d_hash.as<uint64_t>(), d_sorted.as<uint64_t>(), d_perm.as<uint32_t>(), n, 64)) return rc;
     HIPCHK(ctx, tk::launch_ms_gather_u32(d_seq.as<uint32_t>(), d_perm.as<uint32_t>(), n, d_iseq.as<uint32_t>(), s));
     HIPCHK(ctx, tk::launch_ms_gather_u32(d_ps.as<uint32_t>(), d_perm.as<uint32_t>(), n, d_ips.as<uint32_t>(), s));
-    uint64_t n_runs = 0;
-    if (int rc = runs(d_sorted.as<uint64_t>(), n, d_dstart, n_runs)) return rc;
+    uint64_t run_info[2] = {};                                  // (word 0: the runs)
+    if (int rc = run_starts(ctx, d_sorted.as<uint64_t>(), nullptr, n, d_dstart, run_info)) return rc;
+    const uint64_t n_runs = run_info[0];
     if (n_runs > n) { ctx->err = "map: more distinct hashes than minimizers"; return TKSMSEQ_EDEVICE; }
     n_distinct = (uint32_t)n_runs;
     HIPCHK(ctx, d_dkey.ensure((size_t)n_distinct * 8));
@@ -169,7 +137,7 @@ int MapRun::build_index() {
                                         d_dcount.as<uint64_t>(), s));
     HIPCHK(ctx, tk::launch_map_dropped(d_dcount.as<uint64_t>(), n_distinct, (uint64_t)p.max_occ, (unsigned long long*)d_dropped.p, s));
     uint64_t dropped = 0;
-    if (int rc = fetch(d_dropped.as<uint64_t>(), dropped)) return rc;
+    if (int rc = fetch_u64(ctx, d_dropped.as<uint64_t>(), dropped)) return rc;
     if (int rc = end(ST_INDEX)) return rc;
     info.distinct_hashes = n_distinct;
     info.dropped_hashes = dropped;
@@ -209,8 +177,8 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
     if (n_rm) {
         HIPCHK(ctx, tk::launch_map_seed_count(d_rh.as<uint64_t>(), n_rm, d_dkey.as<uint64_t>(), d_dcount.as<uint64_t>(), n_distinct, (uint64_t)p.max_occ, d_run.as<uint32_t>(),
                                               d_cnt.as<uint64_t>(), s));
-        if (int rc = scan(d_cnt.as<uint64_t>(), d_off.as<uint64_t>(), n_rm)) return rc;
-        if (int rc = fetch(d_off.as<uint64_t>() + n_rm, n_anchors)) return rc;
+        if (int rc = scan_u64(ctx, d_cnt.as<uint64_t>(), d_off.as<uint64_t>(), n_rm)) return rc;
+        if (int rc = fetch_u64(ctx, d_off.as<uint64_t>() + n_rm, n_anchors)) return rc;
     }
     if (n_anchors > anchor_budget) {
         if (int rc = end(ST_SEED)) return rc;
@@ -236,16 +204,18 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
                                               d_k2.as<uint64_t>(), s));
         if (int rc = sort_pairs<uint64_t>(ctx, tk::abund_sort_u64, d_k1.as<uint64_t>(), d_k1s.as<uint64_t>(), d_perm1.as<uint32_t>(), na, 62)) return rc;
         HIPCHK(ctx, tk::launch_ms_gather_u64(d_k2.as<uint64_t>(), d_perm1.as<uint32_t>(), na, d_k2g.as<uint64_t>(), s));
-        if (int rc = sort_pairs<uint64_t>(ctx, tk::abund_sort_u64, d_k2g.as<uint64_t>(), d_k2s.as<uint64_t>(), d_perm2.as<uint32_t>(), na, 32 + bits_for(n))) return rc;
+        if (int rc = sort_pairs<uint64_t>(ctx, tk::abund_sort_u64, d_k2g.as<uint64_t>(), d_k2s.as<uint64_t>(), d_perm2.as<uint32_t>(), na, 32 + bit_length(n))) return rc;
         HIPCHK(ctx, tk::launch_ms_gather_u64(d_k1s.as<uint64_t>(), d_perm2.as<uint32_t>(), na, d_k1f.as<uint64_t>(), s));
-        if (int rc = runs(d_k2s.as<uint64_t>(), na, d_gstart, n_groups)) return rc;
+        uint64_t run_info[2] = {};
+        if (int rc = run_starts(ctx, d_k2s.as<uint64_t>(), nullptr, na, d_gstart, run_info)) return rc;
+        n_groups = run_info[0];
         if (n_groups > na) { ctx->err = "map: more groups than anchors"; return TKSMSEQ_EDEVICE; }
         // groups that cannot reach min_count anchors leave before any chaining
         HIPCHK(ctx, d_flag.ensure(((size_t)n_groups + 1) * 8));
         HIPCHK(ctx, d_scanned.ensure(((size_t)n_groups + 1) * 8));
         HIPCHK(ctx, tk::launch_map_group_flags(d_gstart.as<uint32_t>(), (uint32_t)n_groups, (uint32_t)p.min_count, d_flag.as<uint64_t>(), s));
-        if (int rc = scan(d_flag.as<uint64_t>(), d_scanned.as<uint64_t>(), n_groups)) return rc;
-        if (int rc = fetch(d_scanned.as<uint64_t>() + n_groups, n_chained)) return rc;
+        if (int rc = scan_u64(ctx, d_flag.as<uint64_t>(), d_scanned.as<uint64_t>(), n_groups)) return rc;
+        if (int rc = fetch_u64(ctx, d_scanned.as<uint64_t>() + n_groups, n_chained)) return rc;
         if (n_chained > n_groups) { ctx->err = "map: more surviving groups than groups"; return TKSMSEQ_EDEVICE; }
         HIPCHK(ctx, tk::launch_map_group_list(d_flag.as<uint64_t>(), d_scanned.as<uint64_t>(), (uint32_t)n_groups, d_list.as<uint32_t>(), s));
         HIPCHK(ctx, hipStreamSynchronize(s));                   // (the temporaries of this scope go)
@@ -288,8 +258,7 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
 
     // ---- the lines of the chunk: checked, with alignment aligned, then written
     std::vector<tkh::MapAlnLine> alines;
-    std::vector<tkh::MapAlnOut> outs;
-    std::vector<uint64_t> run_off, runs;
+    MapAligned al;
     uint64_t segments = 0, col_words = 0;
     for (uint32_t r = 0; r < n; r++) {
         if (n_lines[r] > slots) { ctx->err = "map: more lines for a read than it may have"; return TKSMSEQ_EDEVICE; }
@@ -300,7 +269,7 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
         }
     }
     if (aligned && !alines.empty())
-        if (int rc = align(alines, segments, col_words, n == 1, names[r0], d_codes, d_valid, d_seqs, d_chain, d_list, d_gstart, d_k1f, d_pred, outs, run_off, runs)) return rc;
+        if (int rc = align(alines, segments, col_words, n == 1, names[r0], {d_codes, d_valid, d_seqs, d_chain, d_list, d_gstart, d_k1f, d_pred}, al)) return rc;
     t0 = std::chrono::steady_clock::now();
     size_t at = 0;
     for (uint32_t r = 0; r < n; r++) {
@@ -309,19 +278,19 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
         for (uint32_t i = 0; i < n_lines[r]; i++, at++) {
             const uint32_t c = lines[(size_t)r * slots + i], t = chains[c].tr >> 1;
             if (aligned)
-                tkh::map_paf_line_aligned(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], chains[c], i ? 0u : mapq[r], i == 0, outs[at],
-                                          runs.data() + run_off[at], ap.eqx != 0, paf);
+                tkh::map_paf_line_aligned(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], chains[c], i ? 0u : mapq[r], i == 0, al.outs[at],
+                                          al.runs.data() + al.run_off[at], ap.eqx != 0, paf);
             else
                 tkh::map_paf_line(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], chains[c], i ? 0u : mapq[r], i == 0, paf);
             info.lines++;
             if (i) info.secondary++;
         }
     }
-    for (size_t l = 0; l < outs.size(); l++) {
+    for (size_t l = 0; l < al.outs.size(); l++) {
         ainfo.lines++;
         ainfo.segments += chains[alines[l].chain].cnt;
-        ainfo.cells += outs[l].cells;
-        ainfo.columns += outs[l].ncols; ainfo.matches += outs[l].eq; ainfo.mismatches += outs[l].x; ainfo.inserted += outs[l].ins; ainfo.deleted += outs[l].del;
+        ainfo.cells += al.outs[l].cells;
+        ainfo.columns += al.outs[l].ncols; ainfo.matches += al.outs[l].eq; ainfo.mismatches += al.outs[l].x; ainfo.inserted += al.outs[l].ins; ainfo.deleted += al.outs[l].del;
     }
     info.write_ms += ms_since(t0);
     info.upload_ms += upload_ms;
@@ -335,9 +304,7 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
 
 // the alignment of the chunk's lines: outs[l], and runs[run_off[l] .. run_off[l + 1]) of line l.  RC_SPLIT (no counter touched) when it does not
 // fit the budget and the chunk has more than one read
-int MapRun::align(const std::vector<tkh::MapAlnLine>& lines, uint64_t segments, uint64_t col_words, bool alone, const std::string& first_name, const TmpBuf& d_codes,
-                  const TmpBuf& d_valid, const TmpBuf& d_seqs, const TmpBuf& d_chain, const TmpBuf& d_list, const TmpBuf& d_gstart, const TmpBuf& d_k1f, const TmpBuf& d_pred,
-                  std::vector<tkh::MapAlnOut>& outs, std::vector<uint64_t>& run_off, std::vector<uint64_t>& runs) {
+int MapRun::align(const std::vector<tkh::MapAlnLine>& lines, uint64_t segments, uint64_t col_words, bool alone, const std::string& first_name, const MapChunkBufs& c, MapAligned& a) {
     const uint32_t nl = (uint32_t)lines.size();
     auto over = [&](const char* what) {
         if (!alone) return (int)RC_SPLIT;
@@ -354,8 +321,8 @@ int MapRun::align(const std::vector<tkh::MapAlnLine>& lines, uint64_t segments, 
     HIPCHK(ctx, d_words.ensure(16));                               // longest, flags
     HIPCHK(ctx, hipMemsetAsync(d_words.p, 0, 16, s));
     uint32_t* words = d_words.as<uint32_t>();
-    HIPCHK(ctx, tk::launch_map_align_path(d_lines.as<tk::MapAlnLine>(), nl, d_chain.as<tk::MapChain>(), d_list.as<uint32_t>(), d_gstart.as<uint32_t>(), d_k1f.as<uint64_t>(),
-                                          d_pred.as<uint32_t>(), (uint32_t)p.k, d_path.as<uint64_t>(), words, words + 1, s));
+    HIPCHK(ctx, tk::launch_map_align_path(d_lines.as<tk::MapAlnLine>(), nl, c.d_chain.as<tk::MapChain>(), c.d_list.as<uint32_t>(), c.d_gstart.as<uint32_t>(), c.d_k1f.as<uint64_t>(),
+                                          c.d_pred.as<uint32_t>(), (uint32_t)p.k, d_path.as<uint64_t>(), words, words + 1, s));
     uint32_t h_words[4] = {};
     HIPCHK(ctx, hipMemcpyAsync(h_words, words, 16, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
@@ -365,29 +332,29 @@ int MapRun::align(const std::vector<tkh::MapAlnLine>& lines, uint64_t segments, 
     if (!waves) { if (int rc = end(ainfo.align_ms)) return rc; return over("its traceback store"); }
     const uint32_t tb_stride = longest + 1u;
     HIPCHK(ctx, d_tb.ensure((size_t)waves * tb_stride * tkh::MAP_ALN_TB_BYTES));
-    const tk::MapAlnSeqs Q{ctx->d_packed.as<uint32_t>(), d_tvalid.as<uint32_t>(), d_tseq.as<tk::MapSeq>(), d_codes.as<uint32_t>(), d_valid.as<uint32_t>(), d_seqs.as<tk::MapSeq>()};
-    HIPCHK(ctx, tk::launch_map_align(d_lines.as<tk::MapAlnLine>(), nl, d_chain.as<tk::MapChain>(), d_path.as<uint64_t>(), Q, (uint32_t)p.k, (uint32_t)ap.band, ap.eqx ? 1u : 0u,
+    const tk::MapAlnSeqs Q{ctx->d_packed.as<uint32_t>(), d_tvalid.as<uint32_t>(), d_tseq.as<tk::MapSeq>(), c.d_codes.as<uint32_t>(), c.d_valid.as<uint32_t>(), c.d_seqs.as<tk::MapSeq>()};
+    HIPCHK(ctx, tk::launch_map_align(d_lines.as<tk::MapAlnLine>(), nl, c.d_chain.as<tk::MapChain>(), d_path.as<uint64_t>(), Q, (uint32_t)p.k, (uint32_t)ap.band, ap.eqx ? 1u : 0u,
                                      waves, tb_stride, d_tb.as<uint64_t>(), d_cols.as<uint32_t>(), d_out.as<tk::MapAlnOut>(), words + 1, s));
-    outs.resize(nl);
-    HIPCHK(ctx, hipMemcpyAsync(outs.data(), d_out.p, (size_t)nl * sizeof(tk::MapAlnOut), hipMemcpyDeviceToHost, s));
+    a.outs.resize(nl);
+    HIPCHK(ctx, hipMemcpyAsync(a.outs.data(), d_out.p, (size_t)nl * sizeof(tk::MapAlnOut), hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipMemcpyAsync(h_words, words, 16, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     if (h_words[1]) { ctx->err = "map: an alignment left its segment (flags " + std::to_string(h_words[1]) + ")"; return TKSMSEQ_EDEVICE; }
-    run_off.assign((size_t)nl + 1, 0);
+    a.run_off.assign((size_t)nl + 1, 0);
     for (uint32_t l = 0; l < nl; l++) {
-        if (outs[l].ncols > lines[l].cap || outs[l].runs > outs[l].ncols) { ctx->err = "map: more columns than a line may have"; return TKSMSEQ_EDEVICE; }
-        run_off[l + 1] = run_off[l] + outs[l].runs;
+        if (a.outs[l].ncols > lines[l].cap || a.outs[l].runs > a.outs[l].ncols) { ctx->err = "map: more columns than a line may have"; return TKSMSEQ_EDEVICE; }
+        a.run_off[l + 1] = a.run_off[l] + a.outs[l].runs;
     }
-    const uint64_t n_runs = run_off[nl];
+    const uint64_t n_runs = a.run_off[nl];
     // (the traceback stores have gone by now: the runs take their place in the budget)
     if (tkh::map_align_fixed_bytes(nl, segments, col_words, n_runs) >= align_budget) { if (int rc = end(ainfo.align_ms)) return rc; return over("its CIGAR"); }
     d_tb.release();
-    HIPCHK(ctx, upload(d_roff, run_off.data(), run_off.size(), s));
+    HIPCHK(ctx, upload(d_roff, a.run_off.data(), a.run_off.size(), s));
     HIPCHK(ctx, d_runs.ensure(std::max<uint64_t>(n_runs, 1) * 8));
     HIPCHK(ctx, tk::launch_map_align_encode(d_lines.as<tk::MapAlnLine>(), nl, d_out.as<tk::MapAlnOut>(), d_cols.as<uint32_t>(), d_roff.as<uint64_t>(), ap.eqx ? 1u : 0u,
                                             d_runs.as<uint64_t>(), s));
-    runs.resize((size_t)n_runs + 1);
-    if (n_runs) HIPCHK(ctx, hipMemcpyAsync(runs.data(), d_runs.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost, s));
+    a.runs.resize((size_t)n_runs + 1);
+    if (n_runs) HIPCHK(ctx, hipMemcpyAsync(a.runs.data(), d_runs.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost, s));
     if (int rc = end(ainfo.align_ms)) return rc;
     ainfo.longest_segment = std::max<uint64_t>(ainfo.longest_segment, longest);
     return TKSMSEQ_OK;
@@ -413,28 +380,12 @@ extern "C" int tksmseq_map_align(tksmseq_ctx* ctx, const tksmseq_map_params* par
     // ---- the host reads
     auto t0 = std::chrono::steady_clock::now();
     tkh::MsReads reads;
-    {
-        std::string text;
-        const std::string list = reads_paths;
-        for (size_t a = 0; a <= list.size();) {
-            size_t b = list.find(',', a);
-            if (b == std::string::npos) b = list.size();
-            if (b > a) {
-                const std::string path = list.substr(a, b - a);
-                text.clear();
-                if (!tkh::abund_read_file(path, text, ctx->err)) return TKSMSEQ_EIO;
-                std::string e;
-                if (!tkh::parse_fastq(text.data(), text.size(), reads, e)) {
-                    const bool malformed = e.compare(0, 5, "FASTQ") == 0;
-                    ctx->err = malformed ? path + ": " + e : "map: 2^31 reads or more";
-                    return malformed ? TKSMSEQ_EINVAL : TKSMSEQ_ELIMIT;
-                }
-                if (reads.size() >= MAP_LIMIT) { ctx->err = "map: 2^31 reads or more"; return TKSMSEQ_ELIMIT; }
-            }
-            a = b + 1;
-        }
-        if (!reads.size()) { ctx->err = "map: no reads in " + list; return TKSMSEQ_EINVAL; }
+    const std::string list = reads_paths;
+    if (int rc = tkh::load_fastq_list(list, reads, ctx->err, MAP_LIMIT)) {
+        if (rc == TKSMSEQ_ELIMIT) ctx->err = "map: 2^31 reads or more";
+        return rc;
     }
+    if (!reads.size()) { ctx->err = "map: no reads in " + list; return TKSMSEQ_EINVAL; }
     const uint32_t n_reads = (uint32_t)reads.size();
     for (uint32_t r = 0; r < n_reads; r++)
         if (reads.off[r + 1] - reads.off[r] >= MAP_LIMIT) { ctx->err = "map: a read of 2^31 bases or more"; return TKSMSEQ_ELIMIT; }
@@ -442,13 +393,12 @@ extern "C" int tksmseq_map_align(tksmseq_ctx* ctx, const tksmseq_map_params* par
     MapRun run(ctx, p);
     run.reads = &reads;
     if (align) { run.aligned = true; run.ap = *align; }
-    run.names.resize(n_reads);
-    for (const auto& kv : reads.index) run.names[kv.second] = kv.first;
+    run.names = reads.names();
     run.info.reads = n_reads;
     run.info.read_ms = ms_since(t0);
 
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    for (auto& e : run.ev) HIPCHK(ctx, hipEventCreate(&e));
+    if (int rc = run.ev.create(ctx)) return rc;
     if (int rc = run.build_index()) return rc;
 
     uint64_t chunk_reads = p.chunk_reads;

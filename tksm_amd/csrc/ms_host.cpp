@@ -1,6 +1,9 @@
 // ms_host.cpp -- host side of model-sequence (see ms_host.h; the rules are stated in include/tksmseq.h).
 #include "ms_host.h"
 
+#include "../../include/tksmseq.h"
+#include "abund_host.h"
+
 #include <algorithm>
 #include <cstddef>
 #include <cstdio>
@@ -64,6 +67,23 @@ bool parse_fastq(const char* text, size_t len, MsReads& out, std::string& err) {
         out.off.push_back(out.bases.size());
     }
     return true;
+}
+
+int load_fastq_list(const std::string& list, MsReads& out, std::string& err, uint64_t read_limit) {
+    std::string text, e;
+    for (size_t a = 0; a <= list.size();) {
+        size_t b = list.find(',', a);
+        if (b == std::string::npos) b = list.size();
+        if (b > a) {
+            const std::string path = list.substr(a, b - a);
+            text.clear();
+            if (!abund_read_file(path, text, err)) return TKSMSEQ_EIO;
+            if (!parse_fastq(text.data(), text.size(), out, e)) { err = path + ": " + e; return e.compare(0, 5, "FASTQ") ? TKSMSEQ_ELIMIT : TKSMSEQ_EINVAL; }
+            if (read_limit && out.size() >= read_limit) { err.clear(); return TKSMSEQ_ELIMIT; }
+        }
+        a = b + 1;
+    }
+    return TKSMSEQ_OK;
 }
 
 bool parse_paf_ms(const char* text, size_t len, const MsReads& reads, const std::unordered_map<std::string, uint32_t>& targets,

@@ -15,11 +15,21 @@ struct MsReads {
     std::vector<uint64_t> off{0};                        // [n_reads + 1] into both pools
     std::unordered_map<std::string, uint32_t> index;     // name (the header up to the first white space) -> read
     size_t size() const { return off.size() - 1; }
+    std::vector<std::string> names() const {             // the names in read order
+        std::vector<std::string> v(size());
+        for (const auto& kv : index) v[kv.second] = kv.first;
+        return v;
+    }
 };
 // appends the records of one file's text.  false with err = "FASTQ record N: ..." (a record of fewer than four lines, a header without
 // '@', a third line without '+', sequence and quality of different lengths, a quality outside [0, 93], a name seen before) or
 // "model-sequence: 2^32 reads or more"
 bool parse_fastq(const char* text, size_t len, MsReads& out, std::string& err);
+// appends the records of every file of a comma-separated list (empty entries are passed over; .gz is read as such), in list order.  What was
+// read before a failure stays appended.  Returns TKSMSEQ_OK, or TKSMSEQ_EIO: err = abund_read_file's; TKSMSEQ_EINVAL: err = "<path>: FASTQ
+// record N: ..."; TKSMSEQ_ELIMIT: err = "<path>: " + parse_fastq's limit, or, with read_limit > 0, no message once a file has brought the
+// reads to read_limit (the callers that count word that limit themselves)
+int load_fastq_list(const std::string& list, MsReads& out, std::string& err, uint64_t read_limit = 0);
 
 // alignment column ops as the kernels read them: length << 2 | MS_OP_*
 enum { MS_OP_M = 0, MS_OP_I = 1, MS_OP_D = 2 };

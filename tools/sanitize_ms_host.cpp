@@ -1,5 +1,6 @@
 // AddressSanitizer + UBSan over the host-only code of model-sequence (csrc/ms_host.cpp): the FASTQ reader and interner, the PAF / cg:Z:
-// reader incl. truncated and garbage input, and the writers of the two model files.  CPU only, never loaded into Python:
+// reader incl. truncated and garbage input, the FASTQ list loader of the three tools that read reads, and the writers of the two model files.
+// CPU only, never loaded into Python:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -I tksm_amd/csrc -o /tmp/sanitize_ms_host \
 //       tools/sanitize_ms_host.cpp tksm_amd/csrc/ms_host.cpp tksm_amd/csrc/abund_host.cpp -lz
 //   /tmp/sanitize_ms_host ref.fa reads.fq aln.paf /tmp/ms_host_out
@@ -19,6 +20,37 @@ static void paf_case(const char* label, const std::string& text, const MsReads& 
     const bool ok = parse_paf_ms(copy.data(), copy.size(), reads, targets, tlen, max_aln, a, err);
     printf("paf_case %s %d %zu %zu %llu %llu %llu %llu %llu %llu %s\n", label, (int)ok, a.aln.size(), a.ops.size(), (unsigned long long)a.lines, (unsigned long long)a.no_cigar,
            (unsigned long long)a.supplementary, (unsigned long long)a.unknown_read, (unsigned long long)a.unknown_target, (unsigned long long)a.cigar_op, err.c_str());
+}
+
+static bool same_reads(const MsReads& a, const MsReads& b) { return a.bases == b.bases && a.quals == b.quals && a.off == b.off && a.index == b.index; }
+
+// the FASTQ list loader on files written into dir: "list_case label result reads same-as-`want` message"
+static void list_cases(const std::string& dir) {
+    const std::string a = "@a1 x\nACGT\n+\nIIII\n@a2\nGG\n+\n#I\n", b = "@b1\nTTTAA\n+\n!!!~~\n\n@b2\nC\n+\n5\n", dup = "@b3\nAC\n+\nII\n@a2\nT\n+\nI\n";
+    const std::string cut = b.substr(0, b.size() - 5);                                   // ends inside the record of b2
+    std::string e;
+    for (const auto& f : {std::make_pair("a.fq", a), std::make_pair("b.fq", b), std::make_pair("b.fq.gz", b), std::make_pair("cut.fq", cut), std::make_pair("dup.fq", dup)})
+        if (!write_abundance_file(dir + "/" + f.first, f.second, e)) { printf("error %s\n", e.c_str()); return; }
+    MsReads both, first, none;
+    const std::string ab = a + b;
+    parse_fastq(ab.data(), ab.size(), both, e);
+    parse_fastq(a.data(), a.size(), first, e);
+    const std::string A = dir + "/a.fq", B = dir + "/b.fq";
+    struct Case { const char* label; std::string list; const MsReads* want; uint64_t limit; };
+    const Case cases[] = {{"two", A + "," + B, &both, 0}, {"empty_entries", A + ",," + B + ",", &both, 0}, {"empty", "", &none, 0}, {"comma", ",", &none, 0},
+                          {"missing", A + "," + dir + "/nosuch.fq", &first, 0}, {"cut", A + "," + dir + "/cut.fq", nullptr, 0}, {"duplicate", A + "," + dir + "/dup.fq", nullptr, 0},
+                          {"gz", A + "," + B + ".gz", &both, 0}, {"limit_after_second", A + "," + B, &both, 3}, {"limit_after_first", A + "," + B, &first, 2}};
+    for (const Case& c : cases) {
+        MsReads r; std::string err;
+        const int res = load_fastq_list(c.list, r, err, c.limit);
+        printf("list_case %s %d %zu %d %s\n", c.label, res, r.size(), c.want ? (int)same_reads(r, *c.want) : -1, err.c_str());
+    }
+    std::string text, io;
+    abund_read_file(dir + "/nosuch.fq", text, io);
+    printf("list_io_message %s\n", io.c_str());
+    std::string names;
+    for (const std::string& n : both.names()) names += n + " ";
+    printf("list_names %s\n", names.c_str());
 }
 
 int main(int argc, char** argv) {
@@ -142,5 +174,6 @@ int main(int argc, char** argv) {
            (int)write_abundance_file(dir + "/q.model", qtext, e), (int)write_abundance_file(dir + "/no/such/dir/q.model", qtext, e));
     std::string back;
     printf("gz_round_trip %d\n", (int)(abund_read_file(dir + "/e.model.gz", back, e) && back == etext));
+    list_cases(dir);
     return 0;
 }
