@@ -2,6 +2,7 @@
 anchors of a written chain as waypoints, the banded unit-cost alignment of a segment with its traceback order, the columns of a line, its
 CIGAR and its counters.  Everything else of map comes from tests/map_spec.py.  tests/test_map_align.py pins this file against an
 independent Levenshtein and hand-worked cases; tests/test_map_align_gpu.py compares the device with it byte for byte."""
+import functools
 import os
 import random
 
@@ -128,13 +129,13 @@ def align_chain(tseq, seq, rel, anchors, k, W=63):
     return "".join(columns), nm, spans, cells
 
 
-def map_reads(targets, reads, band=63, eqx=False, **params):
+def map_reads(targets, reads, band=63, eqx=False, memo=None, **params):
     """map_spec.map_reads with every line aligned: {"paf", "info", "align": counters, "plain": the same run's plain PAF, "other": the PAF with
-    eqx the other way, "nm": {read name: NM of its primary}, "shapes": the (dt, dq) of all segments}"""
+    eqx the other way, "nm": {read name: NM of its primary}, "shapes": the (dt, dq) of all segments, "lines": those of the plain run}"""
     p = dict(M.DEFAULTS, **params)
     if not 1 <= band <= 63 or p["max_gap"] > MAX_GAP:
         raise ValueError("map: a parameter out of range")
-    plain = M.map_reads(targets, reads, **params)
+    plain = M.map_reads(targets, reads, memo=memo, **params)          # (memo: see M.map_reads)
     index, _ = M.build_index([s for _, s in targets], p["k"], p["w"])
     info = dict.fromkeys(COUNTERS, 0)
     rows = plain["paf"].splitlines()
@@ -172,7 +173,7 @@ def map_reads(targets, reads, band=63, eqx=False, **params):
             info["inserted"] += n["I"]
             info["deleted"] += n["D"]
     assert at == len(rows)
-    return {"paf": "".join(out), "info": plain["info"], "align": info, "plain": plain["paf"], "other": "".join(other), "nm": nms, "shapes": shapes}
+    return {"paf": "".join(out), "info": plain["info"], "align": info, "plain": plain["paf"], "other": "".join(other), "nm": nms, "shapes": shapes, "lines": plain["lines"]}
 
 
 def cigar_spans(text):
@@ -221,3 +222,19 @@ def generate(d, seed, n_targets=8, n_reads=60, lengths=(700, 1500), read_lengths
         planted["r%04d" % r] = edits
     return {"ref": M.write_fasta(os.path.join(str(d), tag + ".ref.fa"), targets), "reads": M.write_fastq(os.path.join(str(d), tag + ".reads.fq"), reads),
             "targets": targets, "read_list": reads, "planted": planted}
+
+
+DENSE = {4: 120, 5: 200, 6: 300}                     # k: the length of its target
+
+
+@functools.lru_cache(maxsize=None)
+def dense_case(k):
+    """-w 1 with a small k on one random target and six reads with 5 % planted edits on alternating strands: groups of some hundred anchors
+    with many admissible predecessors of equal score in the window of every anchor (M.classes_of_lines says which kinds)"""
+    rs = random.Random(4600 + k)
+    target = M.random_seq(rs, DENSE[k])
+    reads = []
+    for r in range(6):
+        read = plant(rs, target, 0.05)[0]
+        reads.append(("d%d_%d" % (k, r), M.revcomp(read) if r % 2 else read))
+    return [("dense%d" % k, target)], reads, dict(k=k, w=1, min_score=10, secondary_ratio=0.0)

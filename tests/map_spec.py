@@ -2,6 +2,7 @@
 hashes, window minimizers, the index with its occurrence filter, anchors, the chain of a (read, target, strand) group, the lines of a read.
 Everything is integer.  tests/test_map.py pins this file against brute force and hand-worked cases; tests/test_map_gpu.py compares the
 device with it byte for byte."""
+import functools
 import gzip
 import math
 import os
@@ -44,22 +45,27 @@ def kmer(seq, p, k):
     return mix(min(fwd, rev)), 1 if rev < fwd else 0
 
 
-def minimizers(seq, k, w):
-    """[(h, p, strand)] by ascending p"""
+def window_choices(seq, k, w):
+    """(the valid k-mers by position, the position each window selects or None): window j holds the positions j .. j + w - 1"""
     seq = seq.upper()
     n = len(seq) - k + 1
     if n <= 0:
-        return []
+        return [], []
     km = [kmer(seq, p, k) for p in range(n)]
-    chosen = {}
+    choice = []
     for j in range(max(0, n - w) + 1):
         best = None
         for p in range(j, min(j + w, n)):
             if km[p] is not None and (best is None or (km[p][0], p) < best):
                 best = (km[p][0], p)
-        if best is not None:
-            chosen[best[1]] = km[best[1]]
-    return [(chosen[p][0], p, chosen[p][1]) for p in sorted(chosen)]
+        choice.append(None if best is None else best[1])
+    return km, choice
+
+
+def minimizers(seq, k, w):
+    """[(h, p, strand)] by ascending p"""
+    km, choice = window_choices(seq, k, w)
+    return [(km[p][0], p, km[p][1]) for p in sorted({p for p in choice if p is not None})]
 
 
 def build_index(targets, k, w):
@@ -76,21 +82,27 @@ def cost(g, k):
     return 0 if g == 0 else g * k // 100 + (g.bit_length() - 1) // 2
 
 
-def chain(anchors, k, max_gap=5000, bandwidth=500):
-    """the chain of a group: anchors = [(p, qa)] by (p, qa)"""
-    f, pred = [], []
+def chain(anchors, k, max_gap=5000, bandwidth=500, window=PRED_WINDOW):
+    """the chain of a group: anchors = [(p, qa)] by (p, qa); `window` predecessors are looked at (None: all of them).  Beside the chain,
+    what the one loop that decides it saw: f and pred of every anchor, ties[i] = the candidates of i that reach its best candidate score,
+    ascending (the last one is the predecessor when the anchor links), best_is_k[i] = that score was exactly k (no link: the rule is > k)"""
+    f, pred, ties, best_is_k = [], [], [], []
     for i, (p, q) in enumerate(anchors):
-        best, who = None, None
-        for j in range(max(0, i - PRED_WINDOW), i):
+        best, tied = None, []
+        for j in range(0 if window is None else max(0, i - window), i):
             dt, dq = p - anchors[j][0], q - anchors[j][1]
             if dt <= 0 or dq <= 0 or dt > max_gap or dq > max_gap or abs(dt - dq) > bandwidth:
                 continue
             sc = f[j] + min(k, dt, dq) - cost(abs(dt - dq), k)
-            if best is None or sc >= best:
-                best, who = sc, j
+            if best is None or sc > best:
+                best, tied = sc, [j]
+            elif sc == best:
+                tied.append(j)
+        ties.append(tied)
+        best_is_k.append(best == k)
         if best is not None and best > k:
             f.append(best)
-            pred.append(who)
+            pred.append(tied[-1])
         else:
             f.append(k)
             pred.append(None)
@@ -105,7 +117,41 @@ def chain(anchors, k, max_gap=5000, bandwidth=500):
     first, last = anchors[path[0]], anchors[path[-1]]
     out = dict(cnt=len(path), score=f[end], nmatch=nmatch, tstart=first[0], tend=last[0] + k, qs=first[1], qe=last[1] + k, path=path)
     out["blen"] = max(out["tend"] - out["tstart"], out["qe"] - out["qs"])
+    out.update(f=f, pred=pred, ties=ties, best_is_k=best_is_k)
     return out
+
+
+CLASSES = ("distance_64", "ties_same_tile", "ties_previous_tile", "ties_both_tiles", "best_is_k", "end_ties")
+
+
+def classes_of_chain(c):
+    """what a group asked of a device that keeps the last 64 anchors in the lanes of a wave and loads the anchors in tiles of 64 (anchor i
+    is in tile i // 64), counted from what chain() returned.  distance_64: links to i - 64, the slot that anchor i itself takes over.
+    ties_*: anchors i >= 64 that link and had two or more candidates of the best score, by where these lie: all in i's tile, all in the one
+    before, some in each.  best_is_k: anchors whose best candidate scored exactly k.  end_ties: 1 when several anchors hold the largest f"""
+    out = dict.fromkeys(CLASSES, 0)
+    for i, (j, tied) in enumerate(zip(c["pred"], c["ties"])):
+        out["distance_64"] += j is not None and i - j == 64
+        out["best_is_k"] += c["best_is_k"][i]
+        if j is not None and i >= 64 and len(tied) > 1:
+            own = sum(t // 64 == i // 64 for t in tied)
+            out["ties_same_tile" if own == len(tied) else "ties_both_tiles" if own else "ties_previous_tile"] += 1
+    out["end_ties"] = int(c["f"].count(max(c["f"])) > 1)
+    return out
+
+
+def chain_classes(anchors, k, max_gap=5000, bandwidth=500):
+    return classes_of_chain(chain(anchors, k, max_gap, bandwidth))
+
+
+def classes_of_lines(out):
+    """the sum of classes_of_chain over the chains that map_reads wrote: what a comparison of the PAF can see"""
+    total = dict.fromkeys(CLASSES, 0)
+    for lines in out["lines"].values():
+        for _, _, _, c in lines:
+            for what, n in classes_of_chain(c).items():
+                total[what] += n
+    return total
 
 
 def permille(ratio):
@@ -118,7 +164,7 @@ def check_params(p):
         raise ValueError("map: a parameter out of range")
 
 
-def map_read(seq, index, p):
+def map_read(seq, index, p, window=PRED_WINDOW):
     """what one read's letters give: (read minimizers, anchors, groups, chained groups, [kept chains in output order])"""
     k = p["k"]
     groups = {}
@@ -137,7 +183,7 @@ def map_read(seq, index, p):
         if len(anchors) < p["min_count"]:
             continue
         chained += 1
-        c = chain(sorted(anchors), k, p["max_gap"], p["bandwidth"])
+        c = chain(sorted(anchors), k, p["max_gap"], p["bandwidth"], window)
         if c["cnt"] >= p["min_count"] and c["score"] >= p["min_score"]:
             c["t"], c["rel"] = t, rel
             kept.append(c)
@@ -145,20 +191,23 @@ def map_read(seq, index, p):
     return len(mins), n_anchors, len(groups), chained, kept
 
 
-def map_reads(targets, reads, **params):
-    """targets, reads: [(name, letters)].  {"paf": text, "info": counters, "lines": per read name its [(target name, rel, tp, chain)]}"""
+def map_reads(targets, reads, pred_window=PRED_WINDOW, memo=None, **params):
+    """targets, reads: [(name, letters)].  {"paf": text, "info": counters, "lines": per read name its [(target name, rel, tp, chain)]}.
+    pred_window: the window of chain(), to show what another one would give.  memo: a dict that the caller keeps between calls with the
+    same targets and parameters, so that a read's letters are worked on once"""
     p = dict(DEFAULTS, **params)
     check_params(p)
     index, n_entries = build_index([s for _, s in targets], p["k"], p["w"])
     info = dict.fromkeys(COUNTERS, 0)
     info.update(reads=len(reads), target_minimizers=n_entries, distinct_hashes=len(index), dropped_hashes=sum(len(v) > p["max_occ"] for v in index.values()))
     P = permille(p["secondary_ratio"])
-    paf, lines, memo = [], {}, {}
+    paf, lines = [], {}
+    memo = {} if memo is None else memo
     for name, seq in reads:
         seq = seq.upper()
-        if seq not in memo:                     # (a read's result depends on its letters alone)
-            memo[seq] = map_read(seq, index, p)
-        n_min, n_anchors, n_groups, chained, kept = memo[seq]
+        if (seq, pred_window) not in memo:      # (a read's result depends on its letters alone)
+            memo[seq, pred_window] = map_read(seq, index, p, pred_window)
+        n_min, n_anchors, n_groups, chained, kept = memo[seq, pred_window]
         info["read_minimizers"] += n_min
         info["anchors"] += n_anchors
         info["groups"] += n_groups
@@ -273,3 +322,74 @@ def generate(d, seed, n_targets=40, n_reads=300, lengths=(600, 2500), min_read=2
         truth["r%04d" % r] = (name, strand, a, a + n)
     return {"ref": write_fasta(os.path.join(str(d), tag + ".ref.fa"), targets), "reads": write_fastq(os.path.join(str(d), tag + ".reads.fq"), reads),
             "targets": targets, "read_list": reads, "truth": truth}
+
+
+# ----------------------------------------------------------------------------- inputs that reach one case each
+TANDEM_REPEATS = (63, 64, 65, 66)
+TANDEM = dict(k=15, w=1, min_count=1, min_score=0)
+
+
+@functools.lru_cache(maxsize=None)
+def tandem_case():
+    """A target with 3 copies of a 20-base unit, and reads of r copies of it, each with its reverse complement.  With w = 1 the group of a
+    read holds, for every position p of the target's repeat, the about r read positions in phase with it: sorted by (p, q), the diagonal
+    predecessor (p - 1, q - 1) lies exactly r anchors back.  r = 63 and 64 reach it (64: in the slot that the anchor itself is about to
+    take), 65 does not and chains through what the window still holds, 66 links nothing.  "memo" is for map_reads: the tests of three
+    files share what the reads gave"""
+    rs = random.Random(640)
+    unit = random_seq(rs, 20)
+    targets = [("tandem", random_seq(rs, 40) + unit * 3 + random_seq(rs, 40))]
+    reads = []
+    for r in TANDEM_REPEATS:
+        reads += [("f%d" % r, unit * r), ("r%d" % r, revcomp(unit * r))]
+    return {"targets": targets, "reads": reads, "params": dict(TANDEM), "memo": {}}
+
+
+SKETCH_WINDOWS = (191, 192, 193, 383, 384, 385)
+
+
+def sketch_case(k, w):
+    """sequences whose numbers of windows lie around one and two tiles of 192: each a target, its copy and its reverse complement the reads"""
+    rs = random.Random(192000 + 100 * k + w)
+    targets = [("w%d" % n, random_seq(rs, n + k + w - 2)) for n in SKETCH_WINDOWS]
+    reads = [("c%d" % n, seq) for (_, seq), n in zip(targets, SKETCH_WINDOWS)] + [("rc%d" % n, revcomp(seq)) for (_, seq), n in zip(targets, SKETCH_WINDOWS)]
+    return targets, reads
+
+
+def tile_boundaries(seq, k, w, tile=192):
+    """how the windows of seq meet at the multiples of `tile`: (boundaries where the window before selects the same position as the window
+    after, so that the later tile must not write it again; boundaries where it selects another; pairs of consecutive minimizers with a
+    boundary above the first and not above the second)"""
+    km, choice = window_choices(seq, k, w)
+    same = sum(choice[j] is not None and choice[j] == choice[j - 1] for j in range(tile, len(choice), tile))
+    other = sum(choice[j] is not None and choice[j - 1] is not None and choice[j] != choice[j - 1] for j in range(tile, len(choice), tile))
+    mins = [p for _, p, _ in minimizers(seq, k, w)]
+    straddle = sum(1 for a, b in zip(mins, mins[1:]) for j in range(tile, len(choice), tile) if a < j <= b)
+    return same, other, straddle
+
+
+SELECT = dict(k=15, w=1, secondary_ratio=0.8)
+
+
+@functools.lru_cache(maxsize=None)
+def select_case():
+    """Reads of 100 bases with w = 1: a target that holds all of a read chains to 100, one that holds its first n bases to n, when the base
+    after the prefix differs from the read's (set here) and no 15-mer of a flank matches by chance (asserted where this is used).  `exact`
+    has a second chain of 80 = 0.8 * 100, `below` one of 79; `three` and `four` lie on that many identical targets"""
+    rs = random.Random(800)
+    targets, reads = [], []
+
+    def other_than(c):
+        return rs.choice([x for x in "ACGT" if x != c])
+
+    for name, copies in (("three", 3), ("four", 4)):
+        read = random_seq(rs, 100)
+        target = random_seq(rs, 30) + read + random_seq(rs, 30)
+        targets += [("%s%d" % (name, i), target) for i in range(copies)]
+        reads.append((name, read))
+    for name, n in (("exact", 80), ("below", 79)):
+        read = random_seq(rs, 100)
+        targets.append((name + "_all", random_seq(rs, 30) + read + random_seq(rs, 30)))
+        targets.append((name + "_prefix", random_seq(rs, 30) + read[:n] + other_than(read[n]) + random_seq(rs, 29)))
+        reads.append((name, read))
+    return targets, reads

@@ -292,9 +292,84 @@ def _cigar(cols, style):
     return "".join(out)
 
 
+def host_ops(cigar):
+    """the ops of a CIGAR as the host hands them to the device: M, = and X are one code ('M'), an op of length 0 is dropped, neighbours of
+    the same code are joined: [(length, 'M' | 'I' | 'D')]"""
+    out = []
+    for n, o in re.findall(r"([0-9]+)([A-Za-z=])", cigar):
+        n, o = int(n), "M" if o in "M=X" else o
+        if not n:
+            continue
+        if out and out[-1][1] == o:
+            out[-1] = (out[-1][0] + n, o)
+        else:
+            out.append((n, o))
+    return out
+
+
+def pass_columns(cigar, width=64):
+    """the columns of every pass of `width` ops over host_ops(cigar)"""
+    ops = host_ops(cigar)
+    return [sum(n for n, _ in ops[a:a + width]) for a in range(0, len(ops), width)]
+
+
+def columns_of_ops(n_ops, lengths=None, first="="):
+    """a column string of exactly n_ops host ops that ends on '=': `first`, then '=' and an 'I' or a 'D' by turns, with one 'ID' pair
+    where the count needs it; op x has lengths.get(x, 1) columns"""
+    lengths = lengths or {}
+    codes = [first]
+    while len(codes) < n_ops:
+        left = n_ops - len(codes)
+        if codes[-1] != "=":
+            codes.append("=")
+        elif left % 2 == 0:
+            codes.append("ID"[len(codes) // 2 % 2])
+        else:                                               # an odd number to go after an '=': two ops that are not '=' in a row
+            codes += ["I", "D"]
+    assert len(codes) == n_ops and (n_ops == 1 or codes[-1] == "=") and all(a != b for a, b in zip(codes, codes[1:]))
+    return "".join(c * lengths.get(x, 1) for x, c in enumerate(codes))
+
+
+def op_of(n_ops, at, code, length):
+    """columns_of_ops(n_ops) with op `at` being `length` columns of `code` ('I' or 'D') between two '=' runs of 12 (none before op 0)"""
+    first = "=" if at else code
+    was = columns_of_ops(n_ops, first=first)[at]          # (every op has one column there)
+    assert was in "ID", (n_ops, at)
+    cols = columns_of_ops(n_ops, {at - 1: 12, at: length, at + 1: 12}, first=first)
+    return cols if was == code else cols.translate(str.maketrans("ID", "DI"))
+
+
+def shape_cases(max_del=6):
+    """{name: column string}: what k_ms_expand takes another path for.  Op counts around one, two and three passes of 64 ops; a first pass
+    of 64 ops whose columns end on, just past and just before a step of 64 columns; one op of many steps; a long deletion (a spliced
+    alignment) and a long insertion in the first lane, the last lane and the first lane of the second pass; 'D' runs of max_del and
+    max_del + 1 behind a window that is already longer than 29 letters"""
+    cases = {}
+    for n in (1, 2, 63, 64, 65, 127, 128, 129, 192, 193):
+        cases["ops_%d" % n] = "=" * 20 + "I" if n == 2 else columns_of_ops(n)
+    for total in (64, 65, 127, 128, 129):
+        cases["first_pass_%d_columns" % total] = columns_of_ops(71, {0: total - 63})
+    for n in (63, 64, 65, 1000, 5000):
+        cases["one_op_%d" % n] = "=" * n
+    for code, length in (("D", 3000), ("I", 300)):
+        for n_ops, at in ((4, 0), (3, 1), (65, 63), (66, 64)):
+            cases["%s%d_as_op_%d" % (code, length, at)] = op_of(n_ops, at, code, length)
+    full = ("=" + "D" * max_del) * 5 + "="                 # 6 read positions, 6 + 5 max_del letters
+    cases["del_max_del_behind_a_long_window"] = "=" * 12 + full + "D" * max_del + "=" * 12
+    cases["del_max_del_plus_1_behind_a_long_window"] = "=" * 12 + full + "D" * (max_del + 1) + "=" * 12
+    return cases
+
+
+def generate_shapes(out_dir, max_del=6):
+    """20 ordinary alignments and every case of shape_cases() on both strands, on contigs that a 3 000-base deletion fits in"""
+    return generate(out_dir, seed=21, n_alignments=20, extra_columns=(), group=0, contig_len=8000, max_del=max_del, shapes=list(shape_cases(max_del).items()))
+
+
 def generate(out_dir, seed=1, n_alignments=200, col_lo=60, col_hi=400, K=7, max_del=6, extra_columns=(63, 64, 65), long_columns=0, group=65,
-             no_ins=False, contig_len=6000, n_contigs=3, plant=True, p_err=0.12, max_run=3, progress=None):
-    """writes ref.fa, reads.fq, aln.paf under out_dir; returns {"reference", "reads", "alignment", "classes": {class: how often planted}}"""
+             no_ins=False, contig_len=6000, n_contigs=3, plant=True, p_err=0.12, max_run=3, progress=None, shapes=()):
+    """writes ref.fa, reads.fq, aln.paf under out_dir; returns {"reference", "reads", "alignment", "classes": {class: how often planted}}.
+    shapes: column strings, or (name, column string) pairs, that are placed as they are, once on either strand, after everything else:
+    "shape_reads"[name] = the names of their two reads"""
     rng = random.Random(seed)
     os.makedirs(out_dir, exist_ok=True)
     classes = {}
@@ -406,7 +481,18 @@ def generate(out_dir, seed=1, n_alignments=200, col_lo=60, col_hi=400, K=7, max_
         paf.insert(7, "\t".join(["nobody"] + first[1:])); note("unknown_read")
         paf.insert(9, "\t".join(first[:5] + ["nowhere"] + first[6:])); note("unknown_target")
         paf.insert(11, "\t".join(first[:13] + ["cg:Z:5S" + first[13][5:]])); note("other_cigar_op")
+    shape_reads = {}
+    for x, shape in enumerate(shapes):
+        what, cols = shape if isinstance(shape, tuple) else ("shape%d" % x, shape)
+        for strand in "+-":
+            contig, tstart, cols, style = place(cols)
+            while "N" in contigs[contig][tstart:tstart + len(cols)]:
+                contig, tstart, cols, style = place(cols)
+            shape_reads.setdefault(what, []).append("read%05d" % (serial[0] + 1))
+            add_read(name(), [(contig, tstart, cols, style)], strand, with_n=False)
+            note(what)
     paths = {k: os.path.join(str(out_dir), v) for k, v in (("reference", "ref.fa"), ("reads", "reads.fq"), ("alignment", "aln.paf"))}
+    paths["shape_reads"] = shape_reads
     with open(paths["reference"], "w") as f:
         for cname, s in shown.items():
             f.write(">%s generated\n" % cname)

@@ -1,6 +1,8 @@
 """map without a device: the specification (tests/map_spec.py) against things that are not the specification -- a second statement of the
-window definition, exhaustive search over the chains of small groups, recorded cases small enough to follow by hand -- the host-only code
-under ASan / UBSan, the exports, and the argument checks of `tksm map`."""
+window definition, exhaustive search over the chains of small groups, recorded cases small enough to follow by hand -- the proof that
+the inputs of the device's tests reach their cases (a predecessor at the edge of the window of 64 and past it, ties across tiles of
+anchors, windows around the sketch tiles, a secondary chain on the ratio), the host-only code under ASan / UBSan, the exports, and the
+argument checks of `tksm map`."""
 import ctypes
 import itertools
 import json
@@ -13,6 +15,7 @@ import pytest
 
 from conftest import GOLDEN, ROOT
 
+import map_align_spec as A
 import map_spec as M
 
 EXE = os.path.join(ROOT, "tksm_amd", "tksm")
@@ -76,7 +79,8 @@ def exhaustive(anchors, k, max_gap, bandwidth):
 
 def test_chain_score_against_exhaustive_search():
     """The recurrence restarts a chain at f = k where a link would not lift it above k, and so does the best subsequence (a prefix worth
-    less than nothing is dropped): with at most 10 anchors the 64-predecessor window never binds and the maxima agree."""
+    less than nothing is dropped): with at most 10 anchors the 64-predecessor window never binds and the maxima agree (where the window
+    binds: test_tandem_repeats_put_the_diagonal_predecessor_at_the_edge_of_the_window)."""
     rs = random.Random(3)
     for trial in range(150):
         k = rs.choice([5, 15])
@@ -106,6 +110,127 @@ def test_chain_tie_takes_the_later_predecessor_and_the_earlier_end():
     # two ends with the same f: the smaller index ends the chain
     c = M.chain([(0, 0), (5, 5), (7000, 7000), (7005, 7005)], k, 5000, 500)
     assert c["score"] == 10 and c["path"] == [0, 1]
+
+
+def test_chain_reports_what_its_loop_decided():
+    """f, pred, ties and best_is_k of every anchor against the step stated once more over the f that chain() returned, for the window of
+    64, a window of 3 and none; window = 64 is the default, and None is what the exhaustive search knows"""
+    rs = random.Random(4)
+    for trial in range(60):
+        k = rs.choice([5, 15])
+        anchors = sorted({(rs.randint(0, 40), rs.randint(0, 40)) for _ in range(rs.randint(1, 12))})
+        gap, bw = rs.choice([(5000, 500), (20, 3)])
+        assert M.chain(anchors, k, gap, bw) == M.chain(anchors, k, gap, bw, 64)
+        if len(anchors) <= 10:
+            assert M.chain(anchors, k, gap, bw, None)["score"] == exhaustive(anchors, k, gap, bw)
+        for window in (64, 3, None):
+            c = M.chain(anchors, k, gap, bw, window)
+            for i, (p, q) in enumerate(anchors):
+                sc = {}
+                for j in range(i):
+                    dt, dq = p - anchors[j][0], q - anchors[j][1]
+                    if (window is None or i - j <= window) and 0 < dt <= gap and 0 < dq <= gap and abs(dt - dq) <= bw:
+                        sc[j] = c["f"][j] + min(k, dt, dq) - M.cost(abs(dt - dq), k)
+                top = max(sc.values()) if sc else None
+                assert c["ties"][i] == [j for j in sorted(sc) if sc[j] == top] and c["best_is_k"][i] == (top == k)
+                linked = top is not None and top > k
+                assert c["pred"][i] == (c["ties"][i][-1] if linked else None) and c["f"][i] == (top if linked else k)
+            assert all(c["pred"][b] == a for a, b in zip(c["path"], c["path"][1:])) and c["pred"][c["path"][0]] is None
+
+
+def test_chain_classes_on_groups_made_by_hand():
+    k = 5
+    none = dict.fromkeys(M.CLASSES, 0)
+    # 63 anchors that link to nothing (dt = 0 from the first, dq < 0 to the last) between (0, 0) and (1, 1): the one link spans 64
+    group = [(0, 0)] + [(0, 1000 + x) for x in range(63)] + [(1, 1)]
+    assert M.chain_classes(group, k, 5000, 500) == dict(none, distance_64=1)
+    assert M.chain(group, k)["pred"][64] == 0 and M.chain(group, k, window=63)["pred"][64] is None
+    # the tie of test_chain_tie_takes_the_later_predecessor_and_the_earlier_end behind 62, 63 and 64 anchors that link to nothing
+    for fill, what in ((62, "ties_previous_tile"), (63, "ties_both_tiles"), (64, "ties_same_tile")):
+        group = [(x, 9000 - x) for x in range(fill)] + [(100, 0), (100, 2), (110, 10)]
+        c = M.chain(group, k)
+        assert c["ties"][fill + 2] == [fill, fill + 1] and c["pred"][fill + 2] == fill + 1
+        assert M.chain_classes(group, k, 5000, 500) == dict(none, end_ties=0, **{what: 1}), fill
+    assert M.chain_classes([(0, 0), (0, 2), (10, 10)], k, 5000, 500) == none                     # (a tie below anchor 64 is in no class)
+    # dt = 1, dq = 5: 5 + min(5, 1, 5) - cost(4) = 5 + 1 - 1 = k exactly, which does not link
+    assert M.cost(4, k) == 1 and M.chain_classes([(0, 0), (1, 5)], k, 5000, 500) == dict(none, best_is_k=1, end_ties=1)
+    assert M.chain_classes([(0, 0), (5, 5), (7000, 7000), (7005, 7005)], k, 5000, 500) == dict(none, end_ties=1)
+
+
+def test_tandem_repeats_put_the_diagonal_predecessor_at_the_edge_of_the_window():
+    """M.tandem_case: the predecessor that continues the diagonal lies r anchors back.  What each r is there for is shown here from the
+    specification alone, so that the device's test can rely on it"""
+    case = M.tandem_case()
+    targets, reads, params = case["targets"], case["reads"], case["params"]
+    out = M.map_reads(targets, reads, memo=case["memo"], **params)
+    unbounded = M.map_reads(targets, [r for r in reads if r[0] in ("f65", "r65")], pred_window=None, **params)     # (all predecessors: a second a read)
+    assert out["info"]["mapped"] == 8 and out["info"]["lines"] == 8
+    chain = {name: lines[0][3] for name, lines in out["lines"].items()}
+    free = {name: lines[0][3] for name, lines in unbounded["lines"].items()}
+    for s in "fr":
+        back = {r: [i - j for i, j in enumerate(chain["%s%d" % (s, r)]["pred"]) if j is not None] for r in M.TANDEM_REPEATS}
+        assert back[63].count(63) > 1000 and 64 not in back[63]
+        assert back[64].count(64) > 1000 and M.classes_of_chain(chain[s + "64"])["distance_64"] == back[64].count(64)
+        path = chain[s + "64"]["path"]
+        # (20 r - 14 read positions: the first 6 phases of the unit have 64 of them, the other 14 have 63)
+        assert len(path) > 40 and {b - a for a, b in zip(path, path[1:])} == {63, 64} and sum(b - a == 64 for a, b in zip(path, path[1:])) >= 10
+        # 65: the diagonal is out of reach; what the window still holds gives a shorter chain than all predecessors would
+        assert chain[s + "65"]["cnt"] > 1 and chain[s + "65"]["score"] < free[s + "65"]["score"] == chain[s + "64"]["score"]
+        assert chain[s + "66"]["cnt"] == 1 and chain[s + "66"]["score"] == params["k"]
+    # a window that is one too small or one too large writes another PAF: 63 loses the links of r = 64 (and changes r = 65), 65 reaches
+    # the diagonal of r = 65.  (r = 64 alone cannot tell 65 from 64: every link it has is inside both.)
+    both = [r for r in reads if r[0] in ("f64", "r64", "f65", "r65")]
+    paf = {w: M.map_reads(targets, both, pred_window=w, **params)["paf"] for w in (63, 64, 65)}
+    assert paf[63] != paf[64] != paf[65]
+    for name, window, differs in (("f64", 63, True), ("f64", 65, False), ("f65", 63, True), ("f65", 65, True)):
+        one = [r for r in reads if r[0] == name]
+        assert (M.map_reads(targets, one, pred_window=window, **params)["paf"] != M.map_reads(targets, one, **params)["paf"]) == differs, (name, window)
+
+
+def test_dense_groups_reach_every_kind_of_tie():
+    """A.dense_case: over k = 4, 5 and 6 the written chains hold ties whose candidates lie in the anchor's own tile of 64, in the tile
+    before and in both, a best candidate of exactly k, and two ends of the same score.  (Where a count is 0 the seeds of the case change,
+    not this condition.)"""
+    total = dict.fromkeys(M.CLASSES, 0)
+    for k in A.DENSE:
+        targets, reads, params = A.dense_case(k)
+        out = M.map_reads(targets, reads, **params)
+        assert out["info"]["mapped"] == 6 and {lines[0][1] for lines in out["lines"].values()} == {0, 1}
+        for what, n in M.classes_of_lines(out).items():
+            total[what] += n
+    assert all(total[what] >= 1 for what in M.CLASSES if what != "distance_64"), total
+
+
+SKETCH_KW = [(15, 10), (15, 1), (15, 64), (4, 64), (28, 64)]
+
+
+@pytest.mark.parametrize("k,w", SKETCH_KW)
+def test_sketch_case_has_windows_around_the_tiles_and_minimizers_across_them(k, w):
+    targets, reads = M.sketch_case(k, w)
+    for (_, seq), n in zip(targets, M.SKETCH_WINDOWS):
+        assert max(0, len(seq) - k + 1 - w) + 1 == n
+    out = M.map_reads(targets, reads, k=k, w=w, min_count=1, min_score=0)
+    assert out["info"]["mapped"] == len(reads) == 12
+    same, other, straddle = (sum(x) for x in zip(*[M.tile_boundaries(seq, k, w) for _, seq in targets + reads]))
+    # 5 of the 6 lengths have a window 192, 3 of them a window 384: 2 * (5 + 3) boundaries over targets and reads
+    assert same + other <= 16 and straddle >= 1
+    assert (other >= 1) if w == 1 else (same >= 1)
+
+
+def test_select_case_scores_lie_on_the_ratio_and_one_below():
+    targets, reads = M.select_case()
+    every = M.map_reads(targets, reads, max_secondary=10, **dict(M.SELECT, secondary_ratio=0.0))
+    score = {name: [(l[0], l[3]["score"]) for l in lines] for name, lines in every["lines"].items()}
+    assert score["exact"] == [("exact_all", 100), ("exact_prefix", 80)] and score["below"] == [("below_all", 100), ("below_prefix", 79)]
+    assert score["three"] == [("three%d" % i, 100) for i in range(3)] and score["four"] == [("four%d" % i, 100) for i in range(4)]
+    assert 80 * 1000 == M.permille(0.8) * 100 > 79 * 1000
+    out = M.map_reads(targets, reads, max_secondary=2, **M.SELECT)
+    written = {name: [l[0] for l in lines] for name, lines in out["lines"].items()}
+    assert written == {"three": ["three0", "three1", "three2"], "four": ["four0", "four1", "four2"], "exact": ["exact_all", "exact_prefix"], "below": ["below_all"]}
+    alone = M.map_reads(targets, reads, max_secondary=0, **M.SELECT)
+    assert {name: [l[0] for l in lines] for name, lines in alone["lines"].items()} == {"three": ["three0"], "four": ["four0"], "exact": ["exact_all"], "below": ["below_all"]}
+    mapq = {l.split("\t")[0]: int(l.split("\t")[11]) for l in alone["paf"].splitlines()}
+    assert mapq == {"three": 0, "four": 0, "exact": 60 * 20 // 100, "below": 60 * 21 // 100}      # from the second score, written or not
 
 
 def test_recorded_cases():

@@ -1,6 +1,7 @@
 """map -c on the device against the specification (tests/map_align_spec.py): the PAF bytes and the integer counters of both info blocks, no
 tolerance.  Shapes: planted edits on both strands with secondary lines, segments around the wave width and the ring of 64 lanes, an indel
-outside and inside the band, one segment near max_gap and bandwidth, dense overlapping anchors with dt or dq below k, N runs, every offset
+outside and inside the band, chains whose links lie at the edge of the window of 64 predecessors (tandem repeats, at band 63 and 1), chains
+of dense groups with ties between predecessors of two tiles (k = 4, 5, 6), one segment near max_gap and bandwidth, dense overlapping anchors with dt or dq below k, N runs, every offset
 of a packed word on the reverse strand, chunk sizes and a chunk over the alignment's budget, recycled memory, reuse of a context, error
 codes, and the loop the mode is for: transcribe -> sequence -> map -c -> model-sequence."""
 import ctypes
@@ -54,8 +55,8 @@ def same(dev, spec, other=False):
         assert n["M"] or (int(f[9]) == n["="] and int(f[-2][5:]) == n["X"] + n["I"] + n["D"])
 
 
-def check(targets, reads, d, band=63, eqx=False, **params):
-    spec = A.map_reads(targets, reads, band=band, eqx=eqx, **params)
+def check(targets, reads, d, band=63, eqx=False, memo=None, **params):
+    spec = A.map_reads(targets, reads, band=band, eqx=eqx, memo=memo, **params)
     dev = device(targets, reads, d, align_band=band, eqx=eqx, **params)
     same(dev, spec)
     return dev, spec
@@ -141,6 +142,28 @@ def test_an_indel_outside_and_inside_the_band(tmp_path, band):
     assert (95, 55) in spec["shapes"]
     # 40 deletions and the 9 substitutions is what the band of 63 finds or beats; a band of 1 or 2 cannot hold 40 deletions in a row
     assert wide["nm"]["f"] <= 49 and (spec["nm"]["f"] > 49) == (band < 63)
+
+
+@pytest.mark.parametrize("band", [63, 1])
+def test_chains_of_tandem_repeats_at_the_edge_of_the_predecessor_window(tmp_path, band):
+    """M.tandem_case (what it reaches: tests/test_map.py): the chains that link at distance 63 and 64, the shorter one that the window of
+    64 leaves of r = 65, and the single anchors of r = 66, each aligned"""
+    case = M.tandem_case()
+    dev, spec = check(case["targets"], case["reads"], tmp_path, band=band, memo=case["memo"], **case["params"])
+    chain = {name: lines[0][3] for name, lines in spec["lines"].items()}
+    assert spec["align"]["lines"] == 8 and M.classes_of_chain(chain["f64"])["distance_64"] > 0 and M.classes_of_chain(chain["r64"])["distance_64"] > 0
+    assert 1 == chain["f66"]["cnt"] < chain["f65"]["cnt"] < chain["f64"]["cnt"] == chain["f63"]["cnt"]
+
+
+def test_chains_of_dense_groups_with_ties_in_both_tiles(tmp_path):
+    """A.dense_case for k = 4, 5 and 6 with --eqx: the written chains went through every kind of tie (M.CLASSES)"""
+    total = dict.fromkeys(M.CLASSES, 0)
+    for k in A.DENSE:
+        targets, reads, params = A.dense_case(k)
+        dev, spec = check(targets, reads, tmp_path, eqx=True, **params)
+        for what, n in M.classes_of_lines(spec).items():
+            total[what] += n
+    assert all(total[what] >= 1 for what in M.CLASSES if what != "distance_64"), total
 
 
 def test_one_long_segment_near_max_gap_and_bandwidth(tmp_path):

@@ -1,7 +1,10 @@
 """map on the device against the specification (tests/map_spec.py): the PAF bytes and the integer counters of the info block, no tolerance.
 Shapes: sequence lengths around k and the window, every offset of a packed word, N runs and a pool block inside k-mers, palindromes, the
-occurrence filter at its edge, groups around min_count, the wave width and the predecessor window, links at the edge of max_gap and
-bandwidth, a tie of two predecessors, both strands, k and w at their ends, read counts and chunk sizes, file kinds, reuse of a context,
+occurrence filter at its edge, groups around min_count and the wave width, links at the edge of max_gap and bandwidth, a tie of two
+predecessors, tandem repeats whose diagonal predecessor lies 63, 64, 65 and 66 anchors back (the window of 64 at its edge, and binding),
+dense groups (k = 4, 5, 6) with ties inside a tile of 64 anchors, in the tile before and across both, a best candidate of exactly k and
+ends of equal score, numbers of windows around one and two sketch tiles of 192, a secondary chain at the ratio exactly and one below,
+max_secondary 0 and lists that fill their row exactly and by one more, both strands, k and w at their ends, read counts and chunk sizes, file kinds, reuse of a context,
 recycled memory, error codes, the round trip through transcribe / sequence / abundance / model-truncation, and Badread reads."""
 import gzip
 import json
@@ -46,8 +49,8 @@ def same(dev, spec):
     assert i["reads"] == i["mapped"] + i["unmapped"] and i["lines"] == i["mapped"] + i["secondary"] and i["chunks"] >= 1 and len(i["stage_ms"]) == 5
 
 
-def check(targets, reads, d, chunk_reads=0, gz=False, **params):
-    spec = M.map_reads(targets, reads, **params)
+def check(targets, reads, d, chunk_reads=0, gz=False, memo=None, **params):
+    spec = M.map_reads(targets, reads, memo=memo, **params)
     dev = device(targets, reads, d, chunk_reads=chunk_reads, gz=gz, **params)
     same(dev, spec)
     return dev, spec
@@ -127,8 +130,9 @@ def test_occurrence_filter_at_its_edge(tmp_path, copies):
         assert len(spec["lines"]["seg"]) == 4
 
 
-def test_group_sizes_around_min_count_the_wave_and_the_predecessor_window(tmp_path):
-    """a read that is an exact copy of its target with w = 1: every position is an anchor, the group has len - k + 1 of them"""
+def test_group_sizes_around_min_count_and_the_wave(tmp_path):
+    """a read that is an exact copy of its target with w = 1: every position is an anchor, the group has len - k + 1 of them, and the
+    predecessor of each is the one before it (the window of 64: test_tandem_repeats_at_the_edge_of_the_predecessor_window)"""
     rs = random.Random(64)
     sizes = [1, 2, 3, 63, 64, 65, 127, 128, 129, 200]
     k = 15
@@ -167,6 +171,61 @@ def test_links_at_the_edge_of_max_gap_and_bandwidth_and_a_tie(tmp_path):
     assert span["band20"] == 100 and cnt["band20"] >= 52 and span["band21"] <= 61 and cnt["band21"] <= 30
     tie = spec["lines"]["tie"][0][3]
     assert tie["qs"] == 2 and tie["tstart"] == 0 and tie["cnt"] == 17
+
+
+def test_tandem_repeats_at_the_edge_of_the_predecessor_window(tmp_path):
+    """M.tandem_case: the diagonal predecessor lies r = 63, 64, 65, 66 anchors back in groups of about 2 900 anchors.  tests/test_map.py
+    shows from the specification that r = 64 links at distance 64 (the slot that the anchor's own lane holds), that the window binds for
+    r = 65, and that a window of 63 or 65 would write another PAF"""
+    case = M.tandem_case()
+    for chunk_reads in (0, 1):
+        dev, spec = check(case["targets"], case["reads"], tmp_path, chunk_reads=chunk_reads, memo=case["memo"], **case["params"])
+        assert dev["info"]["chunks"] == (8 if chunk_reads else 1)
+    chain = {name: lines[0][3] for name, lines in spec["lines"].items()}
+    for s in "fr":
+        path = chain[s + "64"]["path"]
+        assert M.classes_of_chain(chain[s + "64"])["distance_64"] > 1000 and sum(b - a == 64 for a, b in zip(path, path[1:])) >= 10
+        assert 1 == chain[s + "66"]["cnt"] < chain[s + "65"]["cnt"] < chain[s + "64"]["cnt"] == chain[s + "63"]["cnt"]
+        assert chain[s + "65"]["score"] < chain[s + "64"]["score"]
+
+
+def test_dense_groups_with_every_kind_of_tie(tmp_path):
+    """A.dense_case for k = 4, 5 and 6: over the three, the written chains hold ties with all candidates in the anchor's own tile of 64, all
+    in the tile before and some in each, best candidates of exactly k, and ends of equal score"""
+    import map_align_spec as A
+    total = dict.fromkeys(M.CLASSES, 0)
+    for k in A.DENSE:
+        targets, reads, params = A.dense_case(k)
+        dev, spec = check(targets, reads, tmp_path, **params)
+        assert spec["info"]["mapped"] == 6
+        for what, n in M.classes_of_lines(spec).items():
+            total[what] += n
+    assert all(total[what] >= 1 for what in M.CLASSES if what != "distance_64"), total
+
+
+@pytest.mark.parametrize("k,w", [(15, 10), (15, 1), (15, 64), (4, 64), (28, 64)])
+def test_numbers_of_windows_around_the_sketch_tiles(tmp_path, k, w):
+    """M.sketch_case: 191, 192, 193, 383, 384 and 385 windows, as targets and as reads on both strands; for w > 1 a window before a tile
+    and the first window of the tile select the same position somewhere, which the tile must not write again"""
+    targets, reads = M.sketch_case(k, w)
+    dev, spec = check(targets, reads, tmp_path, k=k, w=w, **LOOSE)
+    assert spec["info"]["mapped"] == 12
+    same, other, straddle = (sum(x) for x in zip(*[M.tile_boundaries(seq, k, w) for _, seq in targets + reads]))
+    assert straddle >= 1 and ((other >= 1) if w == 1 else (same >= 1))
+
+
+def test_secondary_lines_at_the_ratio_and_at_the_end_of_their_row(tmp_path):
+    """M.select_case (the scores: tests/test_map.py): a second chain of 80 under a first of 100 is written at -p 0.8, one of 79 is not; with
+    -N 2 three equal chains fill the row of their read, and of four one is cut; with -N 0 the first alone is written, and its mapping
+    quality still comes from the second score"""
+    targets, reads = M.select_case()
+    dev, spec = check(targets, reads, tmp_path, max_secondary=2, **M.SELECT)
+    assert {name: [(l[0], l[3]["score"]) for l in lines] for name, lines in spec["lines"].items()} == {
+        "three": [("three%d" % i, 100) for i in range(3)], "four": [("four%d" % i, 100) for i in range(3)],
+        "exact": [("exact_all", 100), ("exact_prefix", 80)], "below": [("below_all", 100)]}
+    dev, spec = check(targets, reads, tmp_path, max_secondary=0, **M.SELECT)
+    assert spec["info"]["lines"] == 4 and spec["info"]["secondary"] == 0
+    assert [l.split("\t")[11] for l in dev["paf"].splitlines()] == ["0", "0", str(60 * 20 // 100), str(60 * 21 // 100)]
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65])

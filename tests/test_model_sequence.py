@@ -1,6 +1,7 @@
 """model-sequence without a GPU: the specification (tests/model_seq_spec.py) against a case counted by hand
-(tests/golden/model_seq_known_answers.json), its files through the oracle's loaders, the host code (FASTQ and PAF readers, the writers)
-under ASan / UBSan in a stand-alone program, and the module's argument checks."""
+(tests/golden/model_seq_known_answers.json), its files through the oracle's loaders, the op counts, pass totals and counters of the
+shapes that the device's tests expand (M.shape_cases), the host code (FASTQ and PAF readers, the writers) under ASan / UBSan in a
+stand-alone program, and the module's argument checks."""
 import ctypes
 import gzip
 import json
@@ -85,6 +86,76 @@ def test_generator_plants_every_class(generated):
         assert info[k] >= 1, k
     assert re.search(r"[acgt]", open(generated["reference"]).read())
     assert any("N" in seq for seq in open(generated["reads"]).read().split("\n")[1::4])
+
+
+@pytest.fixture(scope="module")
+def shaped(tmp_path_factory):
+    """M.generate_shapes and, per shape, the CIGARs and the specification's counters of its two alignments taken alone"""
+    g = M.generate_shapes(tmp_path_factory.mktemp("model_seq_shapes"))
+    reads, ref = M.read_fastq(g["reads"]), M.read_fasta(g["reference"])
+    used, _ = M.parse_paf(g["alignment"], reads, ref)
+    by_read = {a["read"]: a for a in used}
+    cigar = {ln.split("\t")[0]: ln.rstrip("\n").split("\tcg:Z:")[1] for ln in open(g["alignment"]) if "\tcg:Z:" in ln and "\ttp:A:S" not in ln}
+    g["cigars"] = {what: [cigar[r] for r in names] for what, names in g["shape_reads"].items()}
+    g["strands"] = {what: [by_read[r]["strand"] for r in names] for what, names in g["shape_reads"].items()}
+    g["counters"] = {what: [M.count(ref, reads, [by_read[r]])[4] for r in names] for what, names in g["shape_reads"].items()}
+    return g
+
+
+def ops_of(shaped, what):
+    """the host's ops of a shape: the same on both strands and in both CIGAR styles"""
+    plus, minus = (M.host_ops(c) for c in shaped["cigars"][what])
+    assert plus == minus and shaped["strands"][what] == ["+", "-"]
+    return plus
+
+
+def test_host_merge_rule_of_the_helper():
+    assert M.host_ops("3M2=1X0I4I0D2D2D1M") == [(6, "M"), (4, "I"), (4, "D"), (1, "M")]
+    assert M.host_ops("5=") == M.host_ops("2X3M") == [(5, "M")] and M.pass_columns("1=1I1=1D", 2) == [2, 2] and M.pass_columns("1=1I1=", 2) == [2, 1]
+
+
+def test_shapes_have_the_op_counts_and_the_pass_totals(shaped):
+    """every shape of M.shape_cases is in the PAF with the number of ops, the columns per pass of 64 ops and the long op in the lane that it
+    is there for (counted by M.host_ops, the host's rule, from the CIGAR text as written)"""
+    assert set(shaped["cigars"]) == set(M.shape_cases()) and len(shaped["cigars"]) == 30
+    styles = {c for pair in shaped["cigars"].values() for c in pair}
+    assert any("M" in c for c in styles) and any("X" in c or "=" in c for c in styles)
+    passes = {1: [1], 2: [21], 63: [63], 64: [64], 65: [64, 1], 127: [64, 63], 128: [64, 64], 129: [64, 64, 1], 192: [64, 64, 64], 193: [64, 64, 64, 1]}
+    for n, columns in passes.items():
+        assert len(ops_of(shaped, "ops_%d" % n)) == n and [M.pass_columns(c) for c in shaped["cigars"]["ops_%d" % n]] == [columns, columns]
+    for total in (64, 65, 127, 128, 129):
+        what = "first_pass_%d_columns" % total
+        assert len(ops_of(shaped, what)) == 71 and M.pass_columns(shaped["cigars"][what][0]) == [total, 7]
+    for n in (63, 64, 65, 1000, 5000):
+        assert ops_of(shaped, "one_op_%d" % n) == [(n, "M")]
+    for code, length in (("D", 3000), ("I", 300)):
+        for at, n_ops in ((0, 4), (1, 3), (63, 65), (64, 66)):
+            ops = ops_of(shaped, "%s%d_as_op_%d" % (code, length, at))
+            assert len(ops) == n_ops and ops[at] == (length, code) and ops[at + 1] == (12, "M") and (at == 0 or ops[at - 1] == (12, "M"))
+            assert sum(n >= 7 for n, o in ops if o == code) == 1
+    for what, run in (("del_max_del_behind_a_long_window", 6), ("del_max_del_plus_1_behind_a_long_window", 7)):
+        assert [n for n, o in ops_of(shaped, what) if o == "D"] == [6, 6, 6, 6, 6, run]
+
+
+def test_counters_of_the_long_deletion_and_of_the_runs_at_max_del(shaped):
+    """By the header's rule a window with a run of more than max_del (6) 'D's is not counted, whatever its length.  The 3 000 'D's lie
+    between the read positions a - 1 and a, and the window of read position i and half-width h holds them when i - h <= a - 1 and
+    i + h >= a: for h = 1, 2, 3, 4 ((9 - 1) / 2) these are the 2 h positions a - h .. a - 1 + h, all inside the read, since 12 '=' stand on
+    either side: 2 + 4 + 6 + 8 = 20 windows.  No other run of the alignment is longer than 1.  A deletion that the alignment starts with
+    lies in no window."""
+    for at, want in ((0, 0), (1, 20), (63, 20), (64, 20)):
+        for info in shaped["counters"]["D3000_as_op_%d" % at]:
+            assert info["windows_max_del"] == want and info["keys_too_long"] == 0, at
+    for at in (0, 1, 63, 64):
+        for info in shaped["counters"]["I300_as_op_%d" % at]:
+            assert info["windows_max_del"] == 0 and info["alternatives_too_long"] == (7 - 1 if at else 0), at
+    # '=DDDDDD' five times and '=': 6 read positions over 36 letters.  The windows of 7 and 9 read positions (h = 3, 4) over them are longer
+    # than 29 letters; the one more run of 6 'D's leaves them keys_too_long, a run of 7 puts those that hold it under windows_max_del
+    six, seven = shaped["counters"]["del_max_del_behind_a_long_window"], shaped["counters"]["del_max_del_plus_1_behind_a_long_window"]
+    for info in six:
+        assert info["windows_max_del"] == 0 and info["keys_too_long"] > 0
+    for info, base in zip(seven, six):
+        assert info["windows_max_del"] == 20 and 0 < info["keys_too_long"] < base["keys_too_long"]
 
 
 def test_specifications_files_load_in_the_oracles_loaders(generated, po):

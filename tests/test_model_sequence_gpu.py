@@ -1,6 +1,9 @@
 """model-sequence on the device (tksmseq_model_sequence, `tksm model-sequence`, Sequencer.model_sequence) against the plain Python statement
 of its rules (tests/model_seq_spec.py): the two model files byte for byte, the counters, the chunking, the cuts, and the built pair used
-by the simulator."""
+by the simulator.  Shapes: about 200 drawn alignments with the generator's planted classes, and (M.shape_cases) alignments of 1, 2, 63,
+64, 65, 127, 128, 129, 192 and 193 ops, first passes of 64 ops with 64, 65, 127, 128 and 129 columns, single ops of 63 to 5 000 columns, a
+deletion of 3 000 and an insertion of 300 columns as op 0, 1, 63 and 64, runs of max_del and max_del + 1 deletions behind a window of more
+than 29 letters; 1 to 9 alignments in all, so that the last workgroup of four waves has idle ones."""
 import gzip
 import os
 import subprocess
@@ -112,6 +115,54 @@ def test_max_alignments_cuts_inside_the_file(S, data, tmp_path):
     want = spec(data, max_alignments=37, min_occur=1)
     assert info["used"] == 37 and info["lines"] < spec(data, min_occur=1)["info"]["lines"]
     assert e == want["error"] and q == want["qscore"]
+    same_counters(info, want["info"])
+
+
+# ------------------------------------------------------------------------------------------------ shapes of k_ms_expand
+@pytest.fixture(scope="module")
+def shapes(tmp_path_factory):
+    """M.generate_shapes (what is in it: tests/test_model_sequence.py); the specification's outputs are computed once per parameter set"""
+    d = tmp_path_factory.mktemp("model_seq_shapes")
+    g = M.generate_shapes(d)
+    g["dir"] = d
+    g["spec"] = {}
+    return g
+
+
+@pytest.fixture(scope="module")
+def SS(shapes):
+    from tksm_amd.sequence import Sequencer
+    s = Sequencer(0)
+    s.get_reference_seqs([shapes["reference"]])
+    yield s
+    s.close()
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(error_k=3, qscore_k=1), dict(error_k=8, qscore_k=29)], ids=["defaults", "k3_kq1", "k8_kq29"])
+def test_shapes_equal_the_specification(SS, shapes, tmp_path, kw):
+    e, q, info = build(SS, shapes, tmp_path, min_occur=1, **kw)
+    want = spec(shapes, min_occur=1, **kw)
+    assert e == want["error"] and e.count("\n") == 4 ** kw.get("error_k", 7)
+    assert q == want["qscore"]
+    same_counters(info, want["info"])
+    assert set(shapes["shape_reads"]) == set(M.shape_cases()) and info["used"] == 20 + (2 * 9 + 1 + 2) + 2 * 30       # drawn, planted, shapes
+    if kw.get("qscore_k", 9) > 1:
+        assert info["windows_max_del"] >= 6 * 20 and info["keys_too_long"] >= 1
+
+
+def test_shapes_in_chunks_between_and_inside_alignments(SS, shapes, tmp_path):
+    e, q, info = build(SS, shapes, tmp_path, min_occur=1, chunk_events=1000)
+    want = spec(shapes, min_occur=1)
+    assert info["chunks"] >= 20 and e == want["error"] and q == want["qscore"]
+    same_counters(info, want["info"])
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 8, 9])
+def test_small_numbers_of_alignments(SS, shapes, tmp_path, n):
+    """four alignments per workgroup: the last one has 3, 2, 1 or no idle waves"""
+    e, q, info = build(SS, shapes, tmp_path, min_occur=1, max_alignments=n)
+    want = spec(shapes, min_occur=1, max_alignments=n)
+    assert info["used"] == n and e == want["error"] and q == want["qscore"]
     same_counters(info, want["info"])
 
 
