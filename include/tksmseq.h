@@ -1075,12 +1075,13 @@ int tksmseq_map(tksmseq_ctx* ctx, const tksmseq_map_params* params, const char* 
 
 /* ---- map, alignment: base-level alignment of the written chains on the device (map -c: cg:Z:, NM:i:) ------------------------------------------
  * Applies to every line map writes, primary and secondary, after the selection: a chain that is not written is never aligned.  These are
- * this build's rules, not minimap2's: unit cost, a static band, no end extension, a waypoint at every anchor ("map").
+ * this build's rules, not minimap2's: unit cost, a static band, no end extension unless --extend ("map, end extension" below), a waypoint
+ * at every anchor ("map").
  *
  * Waypoints.  A written chain has anchors a_0 .. a_{n-1}, a_i = (p_i, qa_i): the target position and the position in the read in the strand
  * of rel.  Along a chain dt = p_{i+1} - p_i > 0 and dq = qa_{i+1} - qa_i > 0 (the chain rule).  The alignment passes through every
  * (p_i, qa_i) and through (p_{n-1} + k, qa_{n-1} + k): n segments, n - 1 between consecutive anchors and the last anchor's k-mer
- * (dt = dq = k).  It covers exactly [tstart, tend) x [qs, qe) of the chain.  Columns 1-9 and 12 and the tp, cm and s1 tags of a line are
+ * (dt = dq = k).  It covers exactly [tstart, tend) x [qs, qe) of the chain (unless --extend).  Columns 1-9 and 12 and the tp, cm and s1 tags of a line are
  * the same with and without alignment.
  *
  * Letters.  T[i] is the target letter at p + i.  Q[j] is the read letter at qa + j for rel = 0, and the complement of the read letter at
@@ -1120,10 +1121,66 @@ typedef struct tksmseq_align_info {
 /* align NULL: exactly tksmseq_map.  align_info may be NULL. */
 int tksmseq_map_align(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const char* reads_paths, const char* paf_out,
                       tksmseq_map_info* info, tksmseq_align_info* align_info);
+
+/* ---- map, end extension: X-drop extension of both ends of the written chains on the device (map --extend) -------------------------------------
+ * Without it a line covers exactly its chain: tstart is the first anchor, tend the last anchor plus k, and the first and last surviving
+ * minimizers of an erroneous read lie well inside it.  With it both corners of every line map writes, primary and secondary, after the
+ * selection, move outward as far as a banded alignment with an X-drop stop carries them, with and without alignment.  It never changes
+ * which lines are written, their order, mapq, tp, cm or s1.  These are this build's rules, not minimap2's ("map").
+ *
+ * Ends.  Coordinates are the chain's: the target runs forward, the read is in the strand of rel; T[i] and Q[j] and what matches are those
+ * of "Letters" above.  Right end: the corner is (tend, qe), T' = T[tend ...], Q' = Q[qe ...].  Left end: the corner is (tstart, qs), T' and
+ * Q' are the letters before the corner, read backwards.  Both are cut to at most max_ext letters, Lt and Lq; when Lt = 0 or Lq = 0 the end
+ * is not extended.
+ *
+ * Cells.  Match +1, mismatch -2, a gap column -2 (linear; fixed, not options).  Cell (i, j), 0 <= i <= Lt, 0 <= j <= Lq, is allowed iff
+ * |i - j| <= B: an anti-diagonal s = i + j holds at most B + 1 allowed cells.  H[0][0] = 0 with m[0][0] = 0 matches; otherwise H[i][j] is
+ * the largest, over the allowed predecessors, of H[i-1][j-1] + (T'[i-1] matches Q'[j-1] ? 1 : -2), H[i-1][j] - 2 (a column D) and
+ * H[i][j-1] - 2 (a column I); on equal values the first in this order wins, m is carried from the chosen predecessor, plus 1 on a
+ * matching diagonal, and the traceback follows the same choice.
+ *
+ * Best cell and stop.  The anti-diagonals are computed for s = 1, 2, ...; mx_s is the largest H of anti-diagonal s (mx_0 = 0).  The best
+ * cell is the one with the largest H: among equal positive values the later anti-diagonal wins, within one anti-diagonal the smallest i;
+ * when no cell is above 0 it is (0, 0).  After anti-diagonal s (its cells counted in) the extension stops when
+ * max(mx_s, mx_{s-1}) < best - Z, when s = Lt + Lq, or before an anti-diagonal without an allowed cell.  Single cells are never pruned.
+ *
+ * Line.  The best cell (ei, ej) moves the corner: tend += ei, qe += ej, or tstart -= ei, qs -= ej.  Columns 3, 4, 8 and 9 are those of
+ * the moved corners (for rel = 1 the read interval is converted as before).  Without alignment column 10 = the chain's nmatch + the m of
+ * both ends and column 11 = max(tend - tstart, qe - qs) of the moved corners.  With alignment the columns are the left end's traceback in
+ * target order, the chain's segments, the right end's traceback; columns 10 and 11, NM:i: and cg:Z: are computed over all of them by the
+ * rules above (eqx as there), and the CIGAR consumes exactly tend - tstart target letters and qend - qstart read letters.  No tag is
+ * added.  band B in [1, 63] (31), drop Z in [1, 1000] (40), max_ext in [1, 32768] (2000): choices, not measurements.  Everything is
+ * integer: the same bytes on every run and for every chunk size.
+ *
+ * On the device: one wave per (line, end); on anti-diagonal s lane (i - j + B) >> 1 owns cell (i, j), its own value of step s - 2 is the
+ * diagonal and its two neighbours of step s - 1, one of them its own and which one alternating with the parity of s + B, are the D and I
+ * predecessors; a wave-wide maximum per step serves the stop and the best cell; the letters are cut from the packed words, the left end
+ * walking them backwards.  A first pass keeps no store and gives (ei, ej, m).  With alignment a second pass over the ends that moved
+ * computes anti-diagonals 1 .. ei + ej again with two traceback bits per cell in a store of the wave, which the same wave walks back from
+ * (ei, ej): stores and columns are sized by what the first pass found, not by max_ext.  A chunk whose extension does not fit its budget
+ * of device bytes is split like one with too many anchors.
+ *
+ * TKSMSEQ_EINVAL: band, drop or max_ext out of range.  TKSMSEQ_ELIMIT: one read whose extension does not fit a chunk's budget. */
+typedef struct tksmseq_extend_params {
+    int32_t band;                    /* --ext-band (31) */
+    int32_t drop;                    /* --ext-drop (40) */
+    int32_t max_ext;                 /* --ext-max (2000) */
+    int32_t reserved;
+} tksmseq_extend_params;
+typedef struct tksmseq_extend_info {
+    uint64_t lines, ends_moved /* of 2 lines */, target_gained, read_gained /* letters, both ends */, matches /* the sum of m */;
+    uint64_t antidiagonals, cells /* computed by the first pass */, longest /* the largest ei + ej */;
+    float extend_ms, reserved;       /* by HIP events, all chunks, both passes */
+} tksmseq_extend_info;
+/* extend NULL: exactly tksmseq_map_align; align NULL: no alignment, as there.  align_info and extend_info may be NULL. */
+int tksmseq_map_extend(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const tksmseq_extend_params* extend, const char* reads_paths,
+                       const char* paf_out, tksmseq_map_info* info, tksmseq_align_info* align_info, tksmseq_extend_info* extend_info);
 /* `tksm map`: -r REF.fa[.gz][,REF2.fa] --reads F.fq[.gz][,MORE] -o OUT.paf[.gz] [-k 15] [-w 10] [--max-occ 500] [--max-gap 5000] [--bandwidth 500]
- * [--min-count 3] [--min-score 40] [-p 0.8] [-N 5] [-c [--eqx] [--align-band 63]] [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L].
+ * [--min-count 3] [--min-score 40] [-p 0.8] [-N 5] [-c [--eqx] [--align-band 63]] [--extend [--ext-band 31] [--ext-drop 40] [--ext-max 2000]]
+ * [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L].
  * Exit codes as the other model modules: 2 for a missing required option, an unknown option or a value out of range ("map: error: ..."; also
- * --eqx or --align-band without -c, and --max-gap above 65536 with -c), checked before any device is opened; 1 for everything that fails later. */
+ * --eqx or --align-band without -c, an --ext-* option without --extend, and --max-gap above 65536 with -c), checked before any device is
+ * opened; 1 for everything that fails later. */
 int tksmseq_map_main(int argc, char** argv);
 
 /* The batch as MDF text, the way molecule_descriptor::operator<< writes it (src/interval.h:898-905): "+id<TAB>depth<TAB>comment",

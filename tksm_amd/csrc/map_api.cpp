@@ -1,7 +1,8 @@
-// map_api.cpp -- C-ABI of map: tksmseq_map and tksmseq_map_align (include/tksmseq.h).  The host reads and checks (ms_host.cpp's FASTQ reader, map_host.cpp), packs
+// map_api.cpp -- C-ABI of map: tksmseq_map, tksmseq_map_align and tksmseq_map_extend (include/tksmseq.h).  The host reads and checks (ms_host.cpp's FASTQ reader, map_host.cpp), packs
 // the reads of a chunk and formats the PAF; the sketch of targets and reads, the index, the seeds, the chains and the choice of the lines run
 // on the device (map_kernels.hip, with the radix sort of abundance and the run kernels of model-sequence), and with alignment the anchors of
-// the written chains, their banded alignment and the run-length code of its columns (map_align_kernels.hip).
+// the written chains, their banded alignment and the run-length code of its columns (map_align_kernels.hip), and with extension the X-drop
+// extension of both ends of every written chain (map_extend_kernels.hip).
 #include <cstring>
 #include <string>
 #include <vector>
@@ -9,6 +10,7 @@
 #include "abund_host.h"
 #include "ctx.h"
 #include "map_align_kernels.h"
+#include "map_extend_kernels.h"
 #include "map_host.h"
 #include "map_kernels.h"
 #include "ms_kernels.h"
@@ -27,6 +29,9 @@ int bit_length(uint64_t n) { int b = 1; while (b < 64 && (n >> b)) b++; return b
 // what align reads of a chunk, and what it hands back: outs[l], and runs[run_off[l] .. run_off[l + 1]) of line l
 struct MapChunkBufs { const TmpBuf &d_codes, &d_valid, &d_seqs, &d_chain, &d_list, &d_gstart, &d_k1f, &d_pred; };
 struct MapAligned { std::vector<tkh::MapAlnOut> outs; std::vector<uint64_t> run_off, runs; };
+// what extend hands back: ends[2 l + end] of line l; with alignment traced[2 l + end] = the index of that end in outs and run_off, or -1
+// when it did not move
+struct MapExtended { std::vector<tkh::MapExtEnd> ends; std::vector<int64_t> traced; std::vector<tkh::MapAlnOut> outs; std::vector<uint64_t> run_off, runs; };
 
 // the state of one call
 struct MapRun {
@@ -39,6 +44,9 @@ struct MapRun {
     tksmseq_align_params ap{63, 0};
     tksmseq_align_info ainfo{};
     uint64_t align_budget = tkh::MAP_ALN_BYTES_MAX;
+    bool extended = false;
+    tksmseq_extend_params xp{31, 40, 2000, 0};
+    tksmseq_extend_info xinfo{};
     Events<2> ev;
     // the index: distinct hashes with their runs in the sorted entries
     TmpBuf d_tvalid, d_tseq, d_dkey, d_dcount, d_dstart, d_iseq, d_ips;
@@ -86,6 +94,7 @@ struct MapRun {
     int build_index();
     int chunk(uint32_t r0, uint32_t r1);
     int align(const std::vector<tkh::MapAlnLine>& lines, uint64_t segments, uint64_t col_words, bool alone, const std::string& first_name, const MapChunkBufs& c, MapAligned& a);
+    int extend(const std::vector<uint32_t>& line_chain, bool alone, const std::string& first_name, const MapChunkBufs& c, MapExtended& x);
 };
 
 int MapRun::build_index() {
@@ -258,7 +267,9 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
 
     // ---- the lines of the chunk: checked, with alignment aligned, then written
     std::vector<tkh::MapAlnLine> alines;
+    std::vector<uint32_t> line_chain;
     MapAligned al;
+    MapExtended ex;
     uint64_t segments = 0, col_words = 0;
     for (uint32_t r = 0; r < n; r++) {
         if (n_lines[r] > slots) { ctx->err = "map: more lines for a read than it may have"; return TKSMSEQ_EDEVICE; }
@@ -266,22 +277,50 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
             const uint32_t c = lines[(size_t)r * slots + i];
             if (c >= nc || chains[c].read != r || (chains[c].tr >> 1) >= ctx->contig_names.size()) { ctx->err = "map: a line of a chain that does not exist"; return TKSMSEQ_EDEVICE; }
             if (aligned) tkh::map_align_add_line(c, chains[c], segments, col_words, alines);
+            line_chain.push_back(c);
         }
     }
+    const MapChunkBufs bufs{d_codes, d_valid, d_seqs, d_chain, d_list, d_gstart, d_k1f, d_pred};
     if (aligned && !alines.empty())
-        if (int rc = align(alines, segments, col_words, n == 1, names[r0], {d_codes, d_valid, d_seqs, d_chain, d_list, d_gstart, d_k1f, d_pred}, al)) return rc;
+        if (int rc = align(alines, segments, col_words, n == 1, names[r0], bufs, al)) return rc;
+    if (extended && !line_chain.empty())
+        if (int rc = extend(line_chain, n == 1, names[r0], bufs, ex)) return rc;
     t0 = std::chrono::steady_clock::now();
     size_t at = 0;
+    std::vector<uint64_t> joined_runs;
     for (uint32_t r = 0; r < n; r++) {
         if (!n_lines[r]) { info.unmapped++; continue; }
         info.mapped++;
         for (uint32_t i = 0; i < n_lines[r]; i++, at++) {
             const uint32_t c = lines[(size_t)r * slots + i], t = chains[c].tr >> 1;
+            tkh::MapChain ch = chains[c];
+            const tkh::MapAlnOut* ao = aligned ? &al.outs[at] : nullptr;
+            const uint64_t* runs = aligned ? al.runs.data() + al.run_off[at] : nullptr;
+            tkh::MapAlnOut joined;
+            if (extended) {
+                const tkh::MapExtEnd &le = ex.ends[2 * at], &re = ex.ends[2 * at + 1];
+                if (le.ei > ch.tstart || le.ej > ch.qs || re.ei > ctx->contigs[2 * (size_t)t + 1] - ch.tend || re.ej > h_seqs[r].len - ch.qe) {
+                    ctx->err = "map: an extension left its sequence"; return TKSMSEQ_EDEVICE;
+                }
+                ch = tkh::map_extended_chain(ch, le, re);
+                ch.nmatch += le.m + re.m;
+                if (aligned) {
+                    const int64_t li = ex.traced[2 * at], ri = ex.traced[2 * at + 1];
+                    joined = tkh::map_join_columns(li < 0 ? nullptr : &ex.outs[li], li < 0 ? nullptr : ex.runs.data() + ex.run_off[li], *ao, runs,
+                                                   ri < 0 ? nullptr : &ex.outs[ri], ri < 0 ? nullptr : ex.runs.data() + ex.run_off[ri], joined_runs);
+                    ao = &joined; runs = joined_runs.data();
+                }
+                xinfo.lines++;
+                xinfo.ends_moved += (le.ei + le.ej > 0) + (re.ei + re.ej > 0);
+                xinfo.target_gained += le.ei + re.ei; xinfo.read_gained += le.ej + re.ej; xinfo.matches += le.m + re.m;
+                xinfo.antidiagonals += le.steps + re.steps; xinfo.cells += le.cells + re.cells;
+                xinfo.longest = std::max<uint64_t>(xinfo.longest, std::max(le.ei + le.ej, re.ei + re.ej));
+            }
             if (aligned)
-                tkh::map_paf_line_aligned(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], chains[c], i ? 0u : mapq[r], i == 0, al.outs[at],
-                                          al.runs.data() + al.run_off[at], ap.eqx != 0, paf);
+                tkh::map_paf_line_aligned(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], ch, i ? 0u : mapq[r], i == 0, *ao, runs,
+                                          ap.eqx != 0, paf);
             else
-                tkh::map_paf_line(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], chains[c], i ? 0u : mapq[r], i == 0, paf);
+                tkh::map_paf_line(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], ch, i ? 0u : mapq[r], i == 0, paf);
             info.lines++;
             if (i) info.secondary++;
         }
@@ -360,10 +399,102 @@ int MapRun::align(const std::vector<tkh::MapAlnLine>& lines, uint64_t segments, 
     return TKSMSEQ_OK;
 }
 
+// the extension of both ends of the chunk's lines: x.ends[2 l + end], and with alignment the columns and runs of the ends that moved.
+// RC_SPLIT (no counter touched) when it does not fit the budget and the chunk has more than one read
+int MapRun::extend(const std::vector<uint32_t>& line_chain, bool alone, const std::string& first_name, const MapChunkBufs& c, MapExtended& x) {
+    const uint64_t nt64 = 2ull * line_chain.size();
+    auto over = [&](const char* what) {
+        if (!alone) return (int)RC_SPLIT;
+        ctx->err = "map: the extension of read " + first_name + " (" + what + ") does not fit the device bytes a chunk may take";
+        return (int)TKSMSEQ_ELIMIT;
+    };
+    if (nt64 >= (1ull << 31) || tkh::map_extend_fixed_bytes(nt64, 0, 0, 0) >= align_budget) return over("its ends");
+    const uint32_t nt = (uint32_t)nt64;
+    std::vector<tkh::MapExtTask> tasks(nt);
+    for (uint32_t e = 0; e < nt; e++) tasks[e] = {line_chain[e / 2], e & 1u, 0u, 0u, 0u, 0u};
+    TmpBuf d_tasks(s), d_ends(s), d_words(s);
+    if (int rc = begin()) return rc;
+    HIPCHK(ctx, upload(d_tasks, tasks.data(), tasks.size(), s));
+    HIPCHK(ctx, d_ends.ensure((size_t)nt * sizeof(tk::MapExtEnd)));
+    HIPCHK(ctx, d_words.ensure(16));                               // flags
+    HIPCHK(ctx, hipMemsetAsync(d_words.p, 0, 16, s));
+    uint32_t* flags = d_words.as<uint32_t>();
+    const tk::MapAlnSeqs Q{ctx->d_packed.as<uint32_t>(), d_tvalid.as<uint32_t>(), d_tseq.as<tk::MapSeq>(), c.d_codes.as<uint32_t>(), c.d_valid.as<uint32_t>(), c.d_seqs.as<tk::MapSeq>()};
+    const tk::MapExtParams P{(uint32_t)xp.band, (uint32_t)xp.drop, (uint32_t)xp.max_ext, aligned && ap.eqx ? 1u : 0u};
+    HIPCHK(ctx, tk::launch_map_extend(d_tasks.as<tk::MapExtTask>(), nt, c.d_chain.as<tk::MapChain>(), Q, P, std::min<uint32_t>((nt + 3u) / 4u * 4u, tkh::MAP_ALN_WAVES), d_ends.as<tk::MapExtEnd>(),
+                                      flags, s));
+    x.ends.resize(nt);
+    uint32_t h_flags = 0;
+    HIPCHK(ctx, hipMemcpyAsync(x.ends.data(), d_ends.p, (size_t)nt * sizeof(tk::MapExtEnd), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(&h_flags, flags, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (h_flags) { ctx->err = "map: a written chain does not lie in its sequences (flags " + std::to_string(h_flags) + ")"; return TKSMSEQ_EDEVICE; }
+    x.traced.assign(nt, -1);
+    if (!aligned) return end(xinfo.extend_ms);
+
+    // ---- the second pass: the ends that moved, their columns sized by the cell the first pass found
+    std::vector<tkh::MapExtTask> moved;
+    uint64_t col_words = 0;
+    uint32_t longest = 0;
+    for (uint32_t e = 0; e < nt; e++) {
+        const tkh::MapExtEnd& b = x.ends[e];
+        if (b.ei > (uint32_t)xp.max_ext || b.ej > (uint32_t)xp.max_ext) { ctx->err = "map: an extension beyond max_ext"; return TKSMSEQ_EDEVICE; }
+        const uint32_t cap = b.ei + b.ej;
+        if (!cap) continue;
+        x.traced[e] = (int64_t)moved.size();
+        moved.push_back({tasks[e].chain, tasks[e].end, (uint32_t)col_words, cap, b.ei, b.ej});
+        col_words += ((uint64_t)cap + 15) / 16;
+        longest = std::max(longest, cap);
+    }
+    const uint32_t nm = (uint32_t)moved.size();
+    if (!nm) return end(xinfo.extend_ms);
+    // (at most a run a column is what this sizing assumes; the exact count is known before the runs are written)
+    const uint64_t fixed = tkh::map_extend_fixed_bytes(nt, nm, col_words, 0);
+    const uint32_t waves = tkh::map_align_waves(align_budget, fixed, nm, longest);   // (0 when the columns alone are over the budget: no col_off was cut short then)
+    if (!waves) { if (int rc = end(xinfo.extend_ms)) return rc; return over("its traceback store"); }
+    const uint32_t tb_stride = longest + 1u;
+    TmpBuf d_moved(s), d_cols(s), d_out(s), d_tb(s), d_lines(s), d_roff(s), d_runs(s);
+    HIPCHK(ctx, upload(d_moved, moved.data(), moved.size(), s));
+    HIPCHK(ctx, d_cols.ensure(col_words * 4));
+    HIPCHK(ctx, d_out.ensure((size_t)nm * sizeof(tk::MapAlnOut)));
+    HIPCHK(ctx, d_tb.ensure((size_t)waves * tb_stride * tkh::MAP_ALN_TB_BYTES));
+    HIPCHK(ctx, tk::launch_map_extend_trace(d_moved.as<tk::MapExtTask>(), nm, c.d_chain.as<tk::MapChain>(), Q, P, waves, tb_stride, d_tb.as<uint64_t>(), d_cols.as<uint32_t>(),
+                                            d_out.as<tk::MapAlnOut>(), flags, s));
+    x.outs.resize(nm);
+    HIPCHK(ctx, hipMemcpyAsync(x.outs.data(), d_out.p, (size_t)nm * sizeof(tk::MapAlnOut), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(&h_flags, flags, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (h_flags) { ctx->err = "map: an extension's way back left its cells (flags " + std::to_string(h_flags) + ")"; return TKSMSEQ_EDEVICE; }
+    // the encoder of the alignment takes the ends as lines of their own: a left end's columns start its words, a right end's end them
+    std::vector<tkh::MapAlnLine> lines(nm);
+    x.run_off.assign((size_t)nm + 1, 0);
+    for (uint32_t l = 0; l < nm; l++) {
+        const tkh::MapAlnOut& o = x.outs[l];
+        if (o.ncols > moved[l].cap || o.runs > o.ncols || !o.ncols || o.eq + o.x + o.del != moved[l].ei || o.eq + o.x + o.ins != moved[l].ej) {
+            ctx->err = "map: an extension's columns do not lead to its cell"; return TKSMSEQ_EDEVICE;
+        }
+        lines[l] = {moved[l].chain, 0u, moved[l].col_off, moved[l].end ? moved[l].cap : o.ncols};
+        x.run_off[l + 1] = x.run_off[l] + o.runs;
+    }
+    for (uint32_t e = 0; e < nt; e++)
+        if (x.traced[e] >= 0 && x.outs[(size_t)x.traced[e]].eq != x.ends[e].m) { ctx->err = "map: the two passes of an extension count other matches"; return TKSMSEQ_EDEVICE; }
+    const uint64_t n_runs = x.run_off[nm];
+    if (tkh::map_extend_fixed_bytes(nt, nm, col_words, n_runs) >= align_budget) { if (int rc = end(xinfo.extend_ms)) return rc; return over("its CIGAR"); }
+    d_tb.release();
+    HIPCHK(ctx, upload(d_lines, lines.data(), lines.size(), s));
+    HIPCHK(ctx, upload(d_roff, x.run_off.data(), x.run_off.size(), s));
+    HIPCHK(ctx, d_runs.ensure(std::max<uint64_t>(n_runs, 1) * 8));
+    HIPCHK(ctx, tk::launch_map_align_encode(d_lines.as<tk::MapAlnLine>(), nm, d_out.as<tk::MapAlnOut>(), d_cols.as<uint32_t>(), d_roff.as<uint64_t>(), ap.eqx ? 1u : 0u,
+                                            d_runs.as<uint64_t>(), s));
+    x.runs.resize((size_t)n_runs + 1);
+    if (n_runs) HIPCHK(ctx, hipMemcpyAsync(x.runs.data(), d_runs.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost, s));
+    return end(xinfo.extend_ms);
+}
+
 }  // namespace
 
-extern "C" int tksmseq_map_align(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const char* reads_paths, const char* paf_out,
-                                 tksmseq_map_info* info_out, tksmseq_align_info* align_info) {
+extern "C" int tksmseq_map_extend(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const tksmseq_extend_params* extend,
+                                  const char* reads_paths, const char* paf_out, tksmseq_map_info* info_out, tksmseq_align_info* align_info, tksmseq_extend_info* extend_info) {
     if (!ctx) return TKSMSEQ_EINVAL;
     if (!reads_paths || !paf_out || !*paf_out) { ctx->err = "map: null argument"; return TKSMSEQ_EINVAL; }
     tksmseq_map_params p{};
@@ -371,6 +502,7 @@ extern "C" int tksmseq_map_align(tksmseq_ctx* ctx, const tksmseq_map_params* par
     if (params) p = *params;
     if (!tkh::map_check_params(p, ctx->err)) return TKSMSEQ_EINVAL;
     if (align && !tkh::map_check_align(p, *align, ctx->err)) return TKSMSEQ_EINVAL;
+    if (extend && !tkh::map_check_extend(*extend, ctx->err)) return TKSMSEQ_EINVAL;
     if (ctx->contigs.empty()) { ctx->err = "map: the context has no reference"; return TKSMSEQ_EINVAL; }
     if (ctx->n_declared) { ctx->err = "map: the reference has contigs that are declared only"; return TKSMSEQ_EINVAL; }
     if (ctx->contigs.size() / 2 >= MAP_LIMIT) { ctx->err = "map: 2^31 targets or more"; return TKSMSEQ_ELIMIT; }
@@ -393,6 +525,7 @@ extern "C" int tksmseq_map_align(tksmseq_ctx* ctx, const tksmseq_map_params* par
     MapRun run(ctx, p);
     run.reads = &reads;
     if (align) { run.aligned = true; run.ap = *align; }
+    if (extend) { run.extended = true; run.xp = *extend; }
     run.names = reads.names();
     run.info.reads = n_reads;
     run.info.read_ms = ms_since(t0);
@@ -440,7 +573,13 @@ extern "C" int tksmseq_map_align(tksmseq_ctx* ctx, const tksmseq_map_params* par
     info.write_ms += ms_since(t0);
     if (info_out) *info_out = info;
     if (align_info) *align_info = run.ainfo;
+    if (extend_info) *extend_info = run.xinfo;
     return TKSMSEQ_OK;
+}
+
+extern "C" int tksmseq_map_align(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const char* reads_paths, const char* paf_out,
+                                 tksmseq_map_info* info_out, tksmseq_align_info* align_info) {
+    return tksmseq_map_extend(ctx, params, align, nullptr, reads_paths, paf_out, info_out, align_info, nullptr);
 }
 
 extern "C" int tksmseq_map(tksmseq_ctx* ctx, const tksmseq_map_params* params, const char* reads_paths, const char* paf_out, tksmseq_map_info* info_out) {

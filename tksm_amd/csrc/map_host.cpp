@@ -115,4 +115,33 @@ void map_paf_line_aligned(const std::string& qname, uint32_t qlen, const std::st
     out += '\n';
 }
 
+bool map_check_extend(const tksmseq_extend_params& e, std::string& err) {
+    if (e.band < 1 || e.band > 63) { err = "map: extend band must be in [1, 63]"; return false; }
+    if (e.drop < 1 || e.drop > 1000) { err = "map: extend drop must be in [1, 1000]"; return false; }
+    if (e.max_ext < 1 || e.max_ext > 32768) { err = "map: extend max_ext must be in [1, 32768]"; return false; }
+    return true;
+}
+
+uint64_t map_extend_fixed_bytes(uint64_t tasks, uint64_t traced, uint64_t col_words, uint64_t runs) {
+    return tasks * (sizeof(MapExtTask) + sizeof(MapExtEnd)) + 8 + traced * (sizeof(MapExtTask) + sizeof(MapAlnOut) + sizeof(MapAlnLine) + 8) + 8 + col_words * 4 + runs * 8;
+}
+
+MapAlnOut map_join_columns(const MapAlnOut* left, const uint64_t* left_runs, const MapAlnOut& mid, const uint64_t* mid_runs, const MapAlnOut* right,
+                           const uint64_t* right_runs, std::vector<uint64_t>& runs) {
+    MapAlnOut o{};
+    runs.clear();
+    auto add = [&](const MapAlnOut& a, const uint64_t* r) {
+        for (uint32_t i = 0; i < a.runs; i++) {
+            const uint64_t op = r[i] & 3u;
+            if (runs.empty() || (runs.back() & 3u) != op) runs.push_back(((r[i] >> 2) + o.ncols) << 2 | op);
+        }
+        o.ncols += a.ncols; o.eq += a.eq; o.x += a.x; o.ins += a.ins; o.del += a.del; o.cells += a.cells;
+    };
+    if (left) add(*left, left_runs);
+    add(mid, mid_runs);
+    if (right) add(*right, right_runs);
+    o.runs = (uint32_t)runs.size();
+    return o;
+}
+
 }  // namespace tkh

@@ -64,4 +64,25 @@ uint32_t map_align_waves(uint64_t budget, uint64_t fixed, uint64_t lines, uint32
 void map_paf_line_aligned(const std::string& qname, uint32_t qlen, const std::string& tname, uint64_t tlen, const MapChain& c, uint32_t mapq, bool primary,
                           const MapAlnOut& a, const uint64_t* runs, bool eqx, std::string& out);
 
+// ---- map --extend ("map, end extension" in include/tksmseq.h; the kernels are described in map_extend_kernels.h)
+// one end of a line (end 0: left, 1: right).  The second pass also reads where its columns go (words), the best cell and cap = ei + ej
+struct MapExtTask { uint32_t chain, end, col_off, cap, ei, ej; };
+// what the first pass found: the best cell, the matches on the way to it, the anti-diagonals and the allowed cells computed
+struct MapExtEnd { uint32_t ei, ej, m, steps; uint64_t cells; };
+
+// band in [1, 63], drop in [1, 1000], max_ext in [1, 32768]; false: err says which
+bool map_check_extend(const tksmseq_extend_params& e, std::string& err);
+// device bytes of a chunk's extension without the traceback stores: the tasks and ends of the first pass; of the second the tasks, their
+// results, their lines and run offsets for the encoder, their columns and their runs
+uint64_t map_extend_fixed_bytes(uint64_t tasks, uint64_t traced, uint64_t col_words, uint64_t runs);
+// the chain with both corners moved
+inline MapChain map_extended_chain(MapChain c, const MapExtEnd& left, const MapExtEnd& right) {
+    c.tstart -= left.ei; c.qs -= left.ej; c.tend += right.ei; c.qe += right.ej;
+    return c;
+}
+// the columns of a line with extension: the left end's (or NULL), the chain's, the right end's (or NULL), each with its runs.  The runs of
+// the parts are joined where two parts meet in the same op; `runs` gets first column << 2 | op of the whole line
+MapAlnOut map_join_columns(const MapAlnOut* left, const uint64_t* left_runs, const MapAlnOut& mid, const uint64_t* mid_runs, const MapAlnOut* right,
+                           const uint64_t* right_runs, std::vector<uint64_t>& runs);
+
 }  // namespace tkh
