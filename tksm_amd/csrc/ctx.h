@@ -341,7 +341,7 @@ struct tksmseq_ctx : ContigLookup {
         w_scratch, w_records, w_istats, w_dstats, w_sums, w_fullpool, w_biglist, w_bigscratch, w_bigtrace;
     unsigned long long full_pool_bytes = 1ull << 30;
     // fast Badread pipeline state (see kernels.h FastBuffers)
-    DevBuf f_state, f_frag, f_nb, f_fplanes, f_jmeta[2], f_redo, f_jpopd, f_trace, f_tracefull, f_slow, f_defer, f_defercnt, f_frag2, f_row64;
+    DevBuf f_state, f_nb, f_fplanes, f_jmeta[2], f_redo, f_jpopd, f_trace, f_tracefull, f_slow, f_defer, f_defercnt, f_frag2, f_row64;
     std::vector<uint32_t> h_row64;        // host copy of the state-row offsets of the current run
     // what the host and the device exchange in every round, in one copy each way: f_round = {job counts of the even rounds,
     // counters, job counts of the odd rounds} -> h_round; h_geo = {prefix, bases, range geometry} -> f_geoall (page-locked)

@@ -176,8 +176,7 @@ enum FailBit { FAIL_QUEUE = 0, FAIL_NOROW = 1, FAIL_SHIFT31 = 3, FAIL_SHIFT14 = 
 
 struct FastBuffers {
     ReadState* state;                 // [n_reads]
-    const uint32_t* row64;            // [n_reads + 1] first 64-position block of every read's state rows (ragged; kernels.hip frag_row ...)
-    uint8_t* st_frag;                 // [blocks][64] 2-bit codes of the padded fragments, one per byte
+    const uint32_t* row64;            // [n_reads + 1] first 64-position block of every read's state rows (ragged; kernels.hip nb_row ...)
     uint16_t* st_nb;                  // [blocks][64] slot codes
     unsigned long long* st_fplanes;   // [blocks + 8 n_reads][2] 2-bit planes of the padded fragments, {lo, hi} word pairs
     uint32_t* st_frag2;               // [4 blocks + 4 n_reads] the padded fragments, 16 bases per word, first base in the top bits: what the

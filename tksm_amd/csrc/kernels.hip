@@ -964,10 +964,9 @@ DEV void go_slow(const FastBuffers& FB, uint64_t r, int lane, int cause) {
     }
 }
 
-// Per-read state rows are ragged: read r owns the 64-position blocks row64[r] .. row64[r + 1] - 1 of st_frag / st_nb (its padded
+// Per-read state rows are ragged: read r owns the 64-position blocks row64[r] .. row64[r + 1] - 1 of st_nb (its padded
 // fragment and at least one spare block), as many pairs of plane words + 8, and four packed words per block + 4 -- one 100 kb molecule
 // among a million short ones costs its own row, not a million rows of its length.
-DEV uint8_t* frag_row(const FastBuffers& FB, uint64_t r) { return FB.st_frag + (size_t)FB.row64[r] * 64; }
 DEV uint16_t* nb_row(const FastBuffers& FB, uint64_t r) { return FB.st_nb + (size_t)FB.row64[r] * 64; }
 DEV unsigned long long* planes_row(const FastBuffers& FB, uint64_t r) { return FB.st_fplanes + 2 * ((size_t)FB.row64[r] + 8 * r); }
 DEV int planes_words(const FastBuffers& FB, uint64_t r) { return (int)(FB.row64[r + 1] - FB.row64[r]) + 8; }      // pairs {lo, hi}
@@ -980,8 +979,10 @@ DEV uint32_t early_bin(int L, double target) {
     const float sc = (float)L * (float)fmax(0.0, 1.0 - target);
     return (uint32_t)min(255, max(0, (int)(8.0f * __log2f(1.0f + sc))));
 }
+// a wave's fragment letters in k_init's LDS: whole 16-byte pieces (the image pass reads them as such)
+__host__ __device__ inline int init_lds_stride(int lcap) { return (lcap + 15) & ~15; }
 // ---- k_init: splice (S1), flanks, target identity, 2-bit planes of the fragment, classification
-// (seven waves per SIMD: 71 registers, no spills -- once the modification loop below is kept from unrolling; the compiler's own choice was 99
+// (seven waves per SIMD: 69 registers, no spills -- once the modification loop below is kept from unrolling; the compiler's own choice was 99
 // registers, four waves: 7.35 -> 5 ms per step.  Eight waves -- 52 registers -- spill six since the literal segments have a path of their own)
 __global__ __launch_bounds__(256, 7) void k_init(BatchView B, RefView R, ErrModelView EM, IdentView IM, SimParams P,
                                                SimBuffers O, FastBuffers FB) {
@@ -991,7 +992,7 @@ __global__ __launch_bounds__(256, 7) void k_init(BatchView B, RefView R, ErrMode
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpw = blockDim.x >> 6;
     const uint64_t r = (uint64_t)blockIdx.x * wpw + wave;
     if (r >= B.n_reads) return;
-    uint8_t* frag = lds_raw + (size_t)wave * P.lcap;
+    uint8_t* frag = lds_raw + (size_t)wave * init_lds_stride(P.lcap);
     const int k = EM.k;
     const uint64_t g = P.first_read + r * P.stride;
     const int raw_len = (int)O.raw_len[r];
@@ -1043,71 +1044,71 @@ __global__ __launch_bounds__(256, 7) void k_init(BatchView B, RefView R, ErrMode
         target = IM.value * (qa + (qb - qa) * fr);
     }
     wave_sync();
-    uint8_t* gfrag = frag_row(FB, r);
+    // ---- the fragment's images, all from ONE pass over the letters in LDS: a lane takes 16 consecutive bases per trip (one 16-byte
+    // LDS read, one conversion "ACGT" -> 0..3: bits 1 and 2 of the letter, xor-ed) and writes from those codes
+    //   the packed word of st_frag2 (16 bases per word, first base in the top bits: k_loop cuts a k-mer's table index out of two
+    //     consecutive words; the straggler kernel unpacks its alignment window from them),
+    //   the 16 slot codes of st_nb, pristine: length 1, the original base as the slot's only symbol, bit 15 (changed) clear -- so that
+    //     the alignment kernel decodes every slot the same way (k_alnf),
+    //   its 16-bit pieces of the two code planes; the four lanes of a quad put theirs together (quad_perm moves) and the quad's first
+    //     lane stores the {lo, hi} pair of the 64 positions.
+    // Everything past L is zero, to the end of the read's rows: the rest of the last word / group / plane pair, the spare block of
+    // st_nb, the 4 spare words of st_frag2, the 8 spare plane pairs (the alignment's window runs into them).  The rows are written
+    // whole here on every run, so nothing that a later kernel can load is left over from an earlier run (the host zeroes none of
+    // them).  What the readers of st_nb do with a slot at or past L:
+    //   k_loop        10 slots from the even position under a k-mer (up to L + 9 - k): only the k slots of the k-mer are looked at
+    //                 (dm, positions < L); lanes without a changing draw load the buffer's first 10 slots and look at none
+    //   k_loopw       stages 2 (TAIL: 32) slots per lane from t < L, looks up positions < L only (draws end at L - 1)
+    //   k_alnf        load_codes: 16 slots from an even position <= p0 + n + 1; a slot counts only if it is `on` (inside [p0, p0 + n))
+    //   join_window_planar, joined_len, join_out: p < n
+    //   k_err         stages slots < L + 2, reads [0, k), [L - k, L) and the joins above
+    //   (k_qjobs and the exact kernel k_simulate do not touch the rows)
+    // Letters other than ACGT are found here as well, from the letters (the code formula maps every byte onto 0..3): such a read
+    // never uses the images, it takes the wave-wide kernel, which splices its own fragment.
     unsigned long long* fpl = planes_row(FB, r);
-    const int fw_r = planes_words(FB, r), fw2_r = frag2_words(FB, r);
-    // the fragment goes to HBM as one 2-bit code per byte ("ACGT" -> 0..3: bits 1 and 2 of the letter, xor-ed), in 8-byte
-    // pieces (the slot is a multiple of 8 long; bytes past L are never used).  Reads with other letters never use it:
-    // they take the wave-wide kernel, which splices its own fragment.
-    for (int t = 8 * lane; t < L; t += 512) {
-        uint2 c = *reinterpret_cast<const uint2*>(frag + t);
-        c.x = ((c.x >> 1) ^ (c.x >> 2)) & 0x03030303u; c.y = ((c.y >> 1) ^ (c.y >> 2)) & 0x03030303u;
-        *reinterpret_cast<uint2*>(gfrag + t) = c;
-    }
-    // the slot codes start out pristine: length 1, the original base as the slot's only symbol, bit 15 (changed) clear -- so that the
-    // alignment kernel decodes every slot the same way (k_alnf); 8 slots (16 bytes) per lane and step
-    {
-        uint16_t* gnb0 = nb_row(FB, r);
-        for (int t = 8 * lane; t < L; t += 512) {
-            uint2 c = *reinterpret_cast<const uint2*>(frag + t);
-            c.x = ((c.x >> 1) ^ (c.x >> 2)) & 0x03030303u; c.y = ((c.y >> 1) ^ (c.y >> 2)) & 0x03030303u;
-            auto two = [](uint32_t b0, uint32_t b1) {            // two slot codes from two 2-bit base codes: 0x1000 | low bit | high bit << 5
-                return (0x1000u | (b0 & 1u) | ((b0 >> 1) << 5)) | ((0x1000u | (b1 & 1u) | ((b1 >> 1) << 5)) << 16);
-            };
-            uint4 o;
-            o.x = two(c.x & 3u, (c.x >> 8) & 3u); o.y = two((c.x >> 16) & 3u, (c.x >> 24) & 3u);
-            o.z = two(c.y & 3u, (c.y >> 8) & 3u); o.w = two((c.y >> 16) & 3u, (c.y >> 24) & 3u);
-            if (t + 8 > L) {                                      // slots past the fragment stay zero
-                const int keep = L - t;
-                uint32_t* ow = &o.x;
-                for (int x2 = 0; x2 < 8; x2++) if (x2 >= keep) ow[x2 >> 1] &= (x2 & 1) ? 0x0000ffffu : 0xffff0000u;
-            }
-            *reinterpret_cast<uint4*>(gnb0 + t) = o;
-        }
-    }
-    // ... and once more packed, 16 bases per word with the first base in the top bits, for the error loop (k_loop cuts a
-    // k-mer's table index out of two consecutive words); bases past L are zero
-    {
-        uint32_t* f2 = frag2_row(FB, r);
-        for (int w = lane; w < fw2_r; w += 64) {
-            uint32_t word = 0u;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int t = 16 * w + 4 * q;
-                uint32_t c = t < P.lcap ? *reinterpret_cast<const uint32_t*>(frag + t) : 0u;
-                if (t + 4 > L) c = t >= L ? 0u : c & (0xffffffffu >> (8 * (t + 4 - L)));
-                const uint32_t codes4 = ((c >> 1) ^ (c >> 2)) & 0x03030303u;
-                word |= ((codes4 * 0x40100401u) >> 24) << (24 - 8 * q);
-            }
-            f2[w] = word;
-        }
-    }
-    // code planes, 64 positions per pair of words: lane q keeps the pair of word q, one 16-byte store per lane then;
-    // the words past the fragment are zero (the alignment's window runs into them)
+    uint16_t* gnb0 = nb_row(FB, r);
+    uint32_t* f2 = frag2_row(FB, r);
+    const int nb64 = (int)(FB.row64[r + 1] - FB.row64[r]);       // 64-position blocks of the read's rows
+    const int fw_r = nb64 + 8, fw2_r = 4 * nb64 + 4;            // plane pairs, packed words (planes_words, frag2_words)
     bool dirty = false;
-    const int nw = (L + 63) >> 6;
-    for (int q0 = 0; q0 < fw_r; q0 += 64) {
-        unsigned long long mylo = 0ull, myhi = 0ull;
-        for (int q = q0; q < min(q0 + 64, nw); q++) {
-            const int p = q * 64 + lane;
-            const bool valid = p < L;
-            const uint8_t c = valid ? frag[p] : (uint8_t)'A';
-            const int code = code_of(c);
-            dirty |= code < 0;
-            const unsigned long long lo = __ballot(valid && (code & 1)), hi = __ballot(valid && (code & 2));
-            if (lane == q - q0) { mylo = lo; myhi = hi; }
+    for (int w0 = 0; w0 < 4 * fw_r; w0 += 64) {                  // (wave-uniform trip count: the quad moves below want every lane)
+        const int w = w0 + lane, t = 16 * w, nv = L - t;        // the lane's word, its first position, its letters inside the fragment
+        uint4 c = make_uint4(0u, 0u, 0u, 0u);
+        if (nv > 0) c = *reinterpret_cast<const uint4*>(frag + t);    // (the wave's LDS is a multiple of 16 long; what lies past L is masked)
+        const uint32_t c4[4] = {c.x, c.y, c.z, c.w};
+        uint32_t word = 0u, lo16 = 0u, hi16 = 0u, sc[8];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int nq = nv - 4 * q;
+            const uint32_t vm = nq >= 4 ? 0xffffffffu : nq <= 0 ? 0u : (1u << (8 * nq)) - 1u;     // 0xff per letter inside the fragment
+            const uint32_t cd = ((c4[q] >> 1) ^ (c4[q] >> 2)) & 0x03030303u & vm;                   // four codes, one per byte
+            const uint32_t b0 = cd & 0x01010101u, b1 = (cd >> 1) & 0x01010101u;
+            // the letter a code stands for: 'A' + {0, 2, 6, 19}
+            dirty |= ((c4[q] ^ (0x41414141u + 2u * b0 + 6u * b1 + 11u * (b0 & b1))) & vm) != 0u;
+            word |= ((cd * 0x40100401u) >> 24) << (24 - 8 * q);
+            lo16 |= ((b0 * 0x01020408u) >> 24) << (4 * q);        // bit j of the nibble: low / high code bit of letter j
+            hi16 |= ((b1 * 0x01020408u) >> 24) << (4 * q);
+            // two slot codes per word, 0x1000 | low bit | high bit << 5, zero past the fragment (bit 2 of a byte: letter inside)
+            const uint32_t cv = cd | (vm & 0x04040404u);
+            const uint32_t y0 = __builtin_amdgcn_perm(cv, cv, 0x0c010c00u), y1 = __builtin_amdgcn_perm(cv, cv, 0x0c030c02u);
+            sc[2 * q] = (y0 & 0x00010001u) | ((y0 & 0x00020002u) << 4) | ((y0 & 0x00040004u) << 10);
+            sc[2 * q + 1] = (y1 & 0x00010001u) | ((y1 & 0x00020002u) << 4) | ((y1 & 0x00040004u) << 10);
         }
-        if (q0 + lane < fw_r) { ulonglong2 v; v.x = mylo; v.y = myhi; *reinterpret_cast<ulonglong2*>(fpl + 2 * (q0 + lane)) = v; }
+        if (w < fw2_r) f2[w] = word;
+        if (w < 4 * nb64) {
+            uint4* d = reinterpret_cast<uint4*>(gnb0 + t);
+            d[0] = make_uint4(sc[0], sc[1], sc[2], sc[3]);
+            d[1] = make_uint4(sc[4], sc[5], sc[6], sc[7]);
+        }
+        const int pc = (int)(lo16 | (hi16 << 16));
+        const uint32_t p0 = (uint32_t)dpp_mov<0x00, 0xf>(0, pc), p1 = (uint32_t)dpp_mov<0x55, 0xf>(0, pc),
+                       p2 = (uint32_t)dpp_mov<0xaa, 0xf>(0, pc), p3 = (uint32_t)dpp_mov<0xff, 0xf>(0, pc);   // the quad's four pieces
+        if ((lane & 3) == 0 && (w >> 2) < fw_r) {
+            ulonglong2 v;
+            v.x = mk64((p2 & 0xffffu) | (p3 << 16), (p0 & 0xffffu) | (p1 << 16));
+            v.y = mk64((p2 >> 16) | (p3 & 0xffff0000u), (p0 >> 16) | (p1 & 0xffff0000u));
+            *reinterpret_cast<ulonglong2*>(fpl + 2 * (w >> 2)) = v;
+        }
     }
     const bool slow = __ballot(dirty) != 0ull;
     if (lane == 0) {
@@ -1207,16 +1208,17 @@ DEV int joined_len(const uint16_t* nb, int p0, int n, int lane) {
 }
 
 // Walks the slots [0, n) once, slot per lane, and writes the joined bases [lo, hi) to out_seq (the last visit).
-DEV void join_out(const uint8_t* frag, const uint16_t* nb, int n, uint8_t* out_seq, int lo, int hi, int lane) {
+DEV void join_out(const uint16_t* nb, int n, uint8_t* out_seq, int lo, int hi, int lane) {
     int base = 0;
     for (int q = 0; q < n; q += 64) {
         const int p = q + lane;
-        uint32_t code = 0; int len = 0; uint8_t orig = 0;
-        if (p < n) { code = nb[p]; len = slot_len(code); orig = frag[p]; }
+        uint32_t code = 0; int len = 0;
+        if (p < n) { code = nb[p]; len = slot_len(code); }
         int total;
         const int off = base + prefix_small(len, total);
-        // the slot's symbols, 2 bits each, planar: the original base of a pristine slot, else the stored codes
-        const uint32_t syms = code ? code & 0x3ffu : planar1((uint32_t)orig);
+        // the slot's symbols, 2 bits each, planar: a slot below L is never 0 -- pristine it is 0x1000 | the original base (k_init),
+        // changed it has bit 15 set (k_loop, k_loopw) -- so its code alone says what it holds
+        const uint32_t syms = code & 0x3ffu;
         for (int x2 = 0; x2 < len; x2++) { const int c = off + x2; if (c >= lo && c < hi) out_seq[c - lo] = base_char((int)(((syms >> x2) & 1u) | (((syms >> (5 + x2)) & 1u) << 1))); }
         base += total;
     }
@@ -1621,7 +1623,7 @@ DEV int join_window_planar(const uint16_t* gnb, int p0, int n, uint8_t* N, uint1
         const int off = base + prefix_small(len, total);
         if (off + len <= ncap)
             for (int x2 = 0; x2 < len; x2++) {
-                N[off + x2] = (uint8_t)(((code >> x2) & 1u) | (((code >> (5 + x2)) & 1u) << 1));     // 2-bit code, as st_frag has the fragment (band_align compares for equality only)
+                N[off + x2] = (uint8_t)(((code >> x2) & 1u) | (((code >> (5 + x2)) & 1u) << 1));     // 2-bit code, as the window's fragment bytes are (band_align compares for equality only)
                 owner[off + x2] = (uint16_t)p;
             }
         base += total;
@@ -1733,8 +1735,19 @@ __global__ __launch_bounds__(64) void k_loopw(ErrModelView EM, SimParams P, Fast
     enum { RUN = 0, NEED_ALN = 1, DONE = 2 };
     int st = RUN;
     int st_aligns = S.st_aligns;
-    const uint8_t* gfrag = frag_row(FB, r);
-    if (TAIL && L <= 1000) { for (int t = lane; t < L; t += 64) Fw[t] = gfrag[t]; }     // (a longer fragment: the window of each alignment)
+    // the fragment codes of an alignment window, one per byte, unpacked from the read's packed words: a lane takes 16 positions (two
+    // words, the row has four spare ones) and stores 16 bytes -- what lands past the window is inside Fw and not looked at
+    auto window_codes = [&](int p0, int nrows) {
+        for (int t = 16 * lane; t < nrows; t += 1024) {
+            const int x = p0 + t, w = x >> 4, o = x & 15;
+            const uint32_t c16 = (uint32_t)((mk64(f2[w], f2[w + 1]) << (2 * o)) >> 32);      // 16 codes, the first in the top bits
+            uint32_t b[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int j = 0; j < 16; j++) b[j >> 2] |= ((c16 >> (30 - 2 * j)) & 3u) << (8 * (j & 3));
+            *reinterpret_cast<uint4*>(Fw + t) = make_uint4(b[0], b[1], b[2], b[3]);
+        }
+    };
+    if (TAIL && L <= 1000) window_codes(0, L);              // (a longer fragment: the window of each alignment)
     for (;;) {                                               // (TAIL: one turn per visit of the read; else a single turn)
         while (st == RUN) {
             double est_cur = est_keep;
@@ -1845,7 +1858,7 @@ __global__ __launch_bounds__(64) void k_loopw(ErrModelView EM, SimParams P, Fast
                 p0 = (int)__umulhi(philox(P.seed, g, ST_ALNPOS, aln_no).x, (uint32_t)(L - 1000 + 1));
                 nrows = 1000;
                 wave_sync();
-                for (int t = lane; t < nrows; t += 64) Fw[t] = gfrag[p0 + t];
+                window_codes(p0, nrows);
             }
             wave_sync();
             const int m = join_window_planar(gnb, p0, nrows, Nw, ownw, wcap, lane);
@@ -1898,8 +1911,9 @@ __global__ __launch_bounds__(64) void k_loopw(ErrModelView EM, SimParams P, Fast
 }
 
 // ---- k_err: the last visit of a read, one wave per read: trims, q-score lookups from the ops of its q-score alignment (S5),
-// output sequence, record sizes.  LDS per wave: frag[lcap] | nb[lcap] u16 | aux[ncap + 128] (the alignment's op bytes).
-// STATE_IN_HBM (long reads): the fragment and its slot codes are read where they are in HBM -- their LDS footprint would leave
+// output sequence, record sizes.  LDS per wave: nb[lcap] u16 | aux[ncap + 128] (the alignment's op bytes); the fragment itself is not needed: a slot's code
+// holds its symbols, the original base of a pristine slot included.
+// STATE_IN_HBM (long reads): the slot codes are read where they are in HBM -- their LDS footprint would leave
 // a handful of waves per CU; only the aux area is in LDS.
 template <bool STATE_IN_HBM>
 __global__ __launch_bounds__(256, 8) void k_err(BatchView B, ErrModelView EM, QsModelView QM, SimParams P, SimBuffers O,
@@ -1935,11 +1949,10 @@ __global__ __launch_bounds__(256, 8) void k_err(BatchView B, ErrModelView EM, Qs
     if (S.stage == 2 || S.slow) return;
     if (S.stage == 0) return;                                  // still in its error loop (k_loop's business)
     uint16_t* gnb = nb_row(FB, r);
-    const int per_wave = STATE_IN_HBM ? lds_ncap + 128 : lds_lcap * 3 + lds_ncap + 128;
+    const int per_wave = STATE_IN_HBM ? lds_ncap + 128 : lds_lcap * 2 + lds_ncap + 128;
     uint8_t* lds_wave = lds_raw + (size_t)wave * per_wave;
-    uint8_t* frag = STATE_IN_HBM ? frag_row(FB, r) : lds_wave;
-    uint16_t* nb = STATE_IN_HBM ? gnb : reinterpret_cast<uint16_t*>(lds_wave + lds_lcap);
-    uint8_t* aux = STATE_IN_HBM ? lds_wave : lds_wave + 3 * (size_t)lds_lcap;
+    uint16_t* nb = STATE_IN_HBM ? gnb : reinterpret_cast<uint16_t*>(lds_wave);
+    uint8_t* aux = STATE_IN_HBM ? lds_wave : lds_wave + 2 * (size_t)lds_lcap;
     const int k = EM.k;
     const uint64_t g = P.first_read + r * P.stride;
     const int raw_len = __builtin_amdgcn_readfirstlane(S.raw_len);
@@ -1949,8 +1962,6 @@ __global__ __launch_bounds__(256, 8) void k_err(BatchView B, ErrModelView EM, Qs
     uint8_t* out_seq = O.scratch + slot;
     uint8_t* out_qual = out_seq + cap;
     if (!STATE_IN_HBM) {
-        const uint8_t* gfrag0 = frag_row(FB, r);
-        for (int t = lane * 4; t < L; t += 256) *reinterpret_cast<uint32_t*>(frag + t) = *reinterpret_cast<const uint32_t*>(gfrag0 + t);
         for (int t = lane * 2; t < L; t += 128) *reinterpret_cast<uint32_t*>(nb + t) = *reinterpret_cast<const uint32_t*>(gnb + t);
     }
     wave_sync();
@@ -2088,7 +2099,7 @@ __global__ __launch_bounds__(256, 8) void k_err(BatchView B, ErrModelView EM, Qs
     } else {
         identity = 1.0 - errors / frag_len;
     }
-    join_out(frag, nb, L, out_seq, lo, hi, lane);
+    join_out(nb, L, out_seq, lo, hi, lane);
     if (P.quirk_perfect) identity = 1.0;
     finish_read(B, P, O, r, P.quirk_perfect ? out_len : raw_len, out_len, identity, status, st_draws, change_count, st_aligns, L, m,
                 start_trim, end_trim, errors, target, lane);
@@ -3095,13 +3106,13 @@ hipError_t launch_simulate_big(const BatchView& b, const RefView& r, const ErrMo
 hipError_t launch_init(const BatchView& b, const RefView& r, const ErrModelView& em, const IdentView& im, const SimParams& p,
                        const SimBuffers& o, const FastBuffers& fb, int wpw, hipStream_t s) {
     if (!b.n_reads) return hipSuccess;
-    const int lds = wpw * p.lcap;
+    const int lds = wpw * init_lds_stride(p.lcap);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_init), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_init, dim3((unsigned)((b.n_reads + wpw - 1) / wpw)), dim3(64 * wpw), lds, s, b, r, em, im, p, o, fb);
     return hipGetLastError();
 }
-int err_lds_bytes(int lcap, int ncap, int wpw, bool state_in_hbm) { return wpw * ((state_in_hbm ? 0 : lcap * 3) + ncap + 128); }
+int err_lds_bytes(int lcap, int ncap, int wpw, bool state_in_hbm) { return wpw * ((state_in_hbm ? 0 : lcap * 2) + ncap + 128); }
 hipError_t launch_err(const BatchView& b, const ErrModelView& em, const QsModelView& qm, const SimParams& p, const SimBuffers& o,
                       const FastBuffers& fb, const uint32_t* order, uint32_t begin, uint32_t count, int lds_lcap, int lds_ncap,
                       int from_jobs, uint32_t c0, uint32_t c1, int wpw, bool state_in_hbm, hipStream_t s) {

@@ -247,7 +247,6 @@ struct FastRun {
         if (nblk >= (1ull << 32)) { ctx->err = "batch too large (split it)"; return TKSMSEQ_ELIMIT; }
         HIPCHK(ctx, ctx->f_state.ensure(n * sizeof(tk::ReadState) + 64));
         HIPCHK(ctx, ctx->f_row64.ensure((n + 1) * 4 + 64));
-        HIPCHK(ctx, ctx->f_frag.ensure(nblk * 64 + 256));
         HIPCHK(ctx, ctx->f_nb.ensure(nblk * 128 + 256));
         HIPCHK(ctx, ctx->f_fplanes.ensure((nblk + 8 * n) * 16 + 256));
         HIPCHK(ctx, ctx->f_frag2.ensure((4 * nblk + 4 * n) * 4 + 1024));
@@ -264,7 +263,7 @@ struct FastRun {
         HIPCHK(ctx, ctx->h_round.ensure(round_bytes));
         HIPCHK(ctx, ctx->h_geo.ensure(geo_bytes));
         HIPCHK(ctx, hipMemcpyAsync(ctx->f_row64.p, ctx->h_row64.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
-        FB.state = ctx->f_state.as<tk::ReadState>(); FB.st_frag = ctx->f_frag.as<uint8_t>(); FB.st_nb = ctx->f_nb.as<uint16_t>();
+        FB.state = ctx->f_state.as<tk::ReadState>(); FB.st_nb = ctx->f_nb.as<uint16_t>();
         FB.st_fplanes = ctx->f_fplanes.as<unsigned long long>(); FB.st_frag2 = ctx->f_frag2.as<uint32_t>(); FB.row64 = ctx->f_row64.as<uint32_t>();
         FB.trace = ctx->f_trace.p;
         FB.redo_list = ctx->f_redo.as<uint32_t>();
@@ -353,7 +352,7 @@ struct FastRun {
         HIPCHK(ctx, place_ranges());
         cnt = ctx->h_round.as<uint32_t>() + nrb / 4;
         make_buckets();
-        HIPCHK(ctx, hipMemsetAsync(ctx->f_nb.p, 0, nblk * 128, s));
+        // (the state rows -- f_nb, f_frag2, f_fplanes -- are not cleared: k_init writes every read's rows whole)
         HIPCHK(ctx, hipMemsetAsync(ctx->f_round.p, 0, round_bytes, s));
         TRY(tick(GAP));
         pl.mark("buffers ready");
