@@ -1175,12 +1175,81 @@ typedef struct tksmseq_extend_info {
 /* extend NULL: exactly tksmseq_map_align; align NULL: no alignment, as there.  align_info and extend_info may be NULL. */
 int tksmseq_map_extend(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const tksmseq_extend_params* extend, const char* reads_paths,
                        const char* paf_out, tksmseq_map_info* info, tksmseq_align_info* align_info, tksmseq_extend_info* extend_info);
+
+/* ---- map, split reads: supplementary lines for chimeric and hairpin reads on the device (map --split) ----------------------------------------
+ * Without it a (read, target, strand) group gives one chain and a read one primary line with its alternatives: of a read glued from several
+ * molecules (`unsegment`) or folded back onto itself (`tail-noise --palindromic`) one piece is reported.  With it every further piece gets a
+ * tp:A:P line of its own, the way minimap2 writes supplementary alignments in a PAF.  A read whose lines all overlap gets exactly the lines
+ * it gets without it.  These are this build's rules, not minimap2's ("map").
+ *
+ * Rounds.  Round 1 of a group is the chain of "Chain" above over all its anchors, unchanged.  When the chain of round r is kept, its read
+ * interval in the strand of rel is [qs, qe): every anchor of the group whose k-mer meets it (qa < qe and qa + k > qs) leaves the group, the
+ * chain's own anchors among them.  When at least min_count anchors remain, round r + 1 applies the same chain rule to the remaining anchors
+ * in their (p, qa) order: the 64 predecessors of a step are the 64 REMAINING anchors before it.  The rounds of a group end with the first
+ * chain that is not kept, with fewer than min_count remaining anchors, or after `chains` rounds, chains in [1, 16] (4).  A chain of a later
+ * round has the fields of a round-1 chain and is kept by the same min_count / min_score test.
+ *
+ * Step A.  The primary, its mapq and the secondaries are chosen exactly as in "Per read" above, from the round-1 chains alone.
+ *
+ * Step B.  The candidates are the read's kept chains of all rounds that step A did not write, ordered by (score descending, target
+ * ascending, rel ascending, round ascending) and walked in that order.  Read intervals are in original read coordinates, [qstart, qend) of
+ * "Line" above, of the chain's own corners (before any --extend).  A candidate is accepted when its read interval shares at most `overlap`
+ * letters, overlap in [0, 2^31) (30), with the primary's and with that of every candidate accepted before it; otherwise it is rejected, and
+ * the walk goes on.  The walk ends after segments - 1 acceptances, segments in [2, 64] (8); candidates it does not reach are neither
+ * accepted nor rejected.  Secondaries take no part in the overlap test.  The three defaults are choices, not measurements of anything.
+ *
+ * mapq of a supplementary line: min(60, 60 (s - s2) / s), and 0 when s2 >= s.  s is the line's score; s2 is the largest score among the
+ * read's kept chains of any round that are not written as tp:A:P and share more than `overlap` letters with this line's read interval, or 0
+ * when there is none.
+ *
+ * Lines of a read: the primary, its secondaries, then the supplementary lines in order of acceptance.  A supplementary line is formatted
+ * like a primary: tp:A:P, its own cm:i: and s1:i:.  When a read has n >= 2 tp:A:P lines, each of them carries sn:i:n and si:i:i directly
+ * after s1:i: (before NM:i: with alignment): i is the line's 0-based rank among the read's tp:A:P lines by (qstart, qend, order of
+ * acceptance, the primary first), of the chain's own corners.  Secondary lines, and all lines of a read with one tp:A:P line, are byte for
+ * byte those without --split.  -c and --extend apply to a supplementary line as to any written line, by their rules above: the selection
+ * precedes both, so neither changes which lines are written.  `abundance` and `model-truncation` read these lines as they read any other
+ * (INTEGRATION.md).
+ *
+ * Counters.  split_reads: reads with a supplementary line.  supplementary: those lines.  later_chains: kept chains of rounds >= 2.  rounds:
+ * all rounds run, all groups (a group that is chained runs at least one).  rejected_overlap: candidates the walk of step B rejected.  With
+ * split tksmseq_map_info.lines = mapped + secondary + supplementary.  split_ms: by HIP events, the chain stage and the select
+ * stage whole, that is stage_ms[3] + stage_ms[4] of the same call: the chain kernel with all its rounds, and the selection with its key
+ * kernel, the sort of the chain keys and the copies of the lines to the host.  One kernel runs all rounds of a group, so the first
+ * round is not timed apart, and the two stages are not bracketed more tightly than without split.
+ *
+ * Estimate.  Every segment of a molecule but the first was glued with probability p, so with J supplementary lines in M mapped reads the
+ * module logs "split: J junctions in M mapped reads: unsegment -p estimate J / (M + J - 1)".
+ *
+ * On the device: one wave chains all rounds of a group.  It gathers the anchors through a list of the remaining original indices (one
+ * scratch word per anchor; round 1 is the identity) and keeps the register scheme of the chain kernel, a lane holding one of the last 64
+ * anchors of the LIST.  After a kept round it compacts the list in place, tile by tile (a ballot of the survivors, ranks by popcount).
+ * The predecessor table keeps original group-relative indices and a round writes only the entries of anchors still in the list, so -c
+ * walks a written chain of any round back from its end anchor exactly as before ((p, qa) is unique in a group: the binary search for the
+ * end anchor stays unique).  Chains go to chain[c * chains + r], kept = 0 for a round not run: the stable sort by (read, score) keeps
+ * (target, rel, round) on ties.  One lane per read does steps A and B, the accepted chains in LDS.  The list and the further chains
+ * count in the chunk budget; a chunk that does not fit is split, never truncated.
+ *
+ * TKSMSEQ_EINVAL: chains, overlap or segments out of range. */
+typedef struct tksmseq_split_params {
+    int32_t chains;                  /* --split-chains (4) */
+    int32_t overlap;                 /* --split-overlap (30) */
+    int32_t segments;                /* --split-segments (8) */
+    int32_t reserved;
+} tksmseq_split_params;
+typedef struct tksmseq_split_info {
+    uint64_t split_reads, supplementary, later_chains, rounds, rejected_overlap;
+    float split_ms, reserved;        /* by HIP events, all chunks */
+} tksmseq_split_info;
+/* split NULL: exactly tksmseq_map_extend; align NULL, extend NULL: as there.  align_info, extend_info and split_info may be NULL. */
+int tksmseq_map_split(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const tksmseq_extend_params* extend,
+                      const tksmseq_split_params* split, const char* reads_paths, const char* paf_out, tksmseq_map_info* info, tksmseq_align_info* align_info,
+                      tksmseq_extend_info* extend_info, tksmseq_split_info* split_info);
 /* `tksm map`: -r REF.fa[.gz][,REF2.fa] --reads F.fq[.gz][,MORE] -o OUT.paf[.gz] [-k 15] [-w 10] [--max-occ 500] [--max-gap 5000] [--bandwidth 500]
  * [--min-count 3] [--min-score 40] [-p 0.8] [-N 5] [-c [--eqx] [--align-band 63]] [--extend [--ext-band 31] [--ext-drop 40] [--ext-max 2000]]
- * [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L].
+ * [--split [--split-chains 4] [--split-overlap 30] [--split-segments 8]] [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L].
  * Exit codes as the other model modules: 2 for a missing required option, an unknown option or a value out of range ("map: error: ..."; also
- * --eqx or --align-band without -c, an --ext-* option without --extend, and --max-gap above 65536 with -c), checked before any device is
- * opened; 1 for everything that fails later. */
+ * --eqx or --align-band without -c, an --ext-* option without --extend, a --split-* option without --split, and --max-gap above 65536 with
+ * -c), checked before any device is opened; 1 for everything that fails later. */
 int tksmseq_map_main(int argc, char** argv);
 
 /* The batch as MDF text, the way molecule_descriptor::operator<< writes it (src/interval.h:898-905): "+id<TAB>depth<TAB>comment",

@@ -203,6 +203,15 @@ class ExtendInfo(C.Structure):             # tksmseq_extend_info
                [("extend_ms", C.c_float), ("reserved", C.c_float)]
 
 
+class SplitParams(C.Structure):            # tksmseq_split_params
+    _fields_ = [("chains", C.c_int32), ("overlap", C.c_int32), ("segments", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SplitInfo(C.Structure):              # tksmseq_split_info
+    _fields_ = [(n, C.c_uint64) for n in ("split_reads", "supplementary", "later_chains", "rounds", "rejected_overlap")] + \
+               [("split_ms", C.c_float), ("reserved", C.c_float)]
+
+
 BM_CAND_TILE = 256                           # candidates per workgroup row of the barcode match: a multiple of this (bm_kernels.h)
 BM_TARGET_WAVES = 2048                       # ... split until about this many waves (bm_kernels.h)
 BM_LIST = 8                                  # barcodes listed per read
@@ -237,7 +246,7 @@ SYMBOLS = [
     "tksmseq_abundance_free", "tksmseq_abundance_main",
     "tksmseq_model_sequence", "tksmseq_model_sequence_main",
     "tksmseq_barcode_match", "tksmseq_barcode_match_main",
-    "tksmseq_map", "tksmseq_map_main", "tksmseq_map_align", "tksmseq_map_extend",
+    "tksmseq_map", "tksmseq_map_main", "tksmseq_map_align", "tksmseq_map_extend", "tksmseq_map_split",
     "tksmseq_filter", "tksmseq_concat", "tksmseq_filter_main",
     "tksmseq_glue", "tksmseq_glue_joins", "tksmseq_shuffle", "tksmseq_unsegment_main", "tksmseq_shuffle_main",
     "tksmseq_variants_load", "tksmseq_variants_info", "tksmseq_variants_free", "tksmseq_mutate", "tksmseq_mutate_main",
@@ -358,6 +367,8 @@ def load():
         "tksmseq_map_main": (C.c_int, [C.c_int, P(C.c_char_p)]),
         "tksmseq_map_align": (C.c_int, [vp, P(MapParams), P(AlignParams), C.c_char_p, C.c_char_p, P(MapInfo), P(AlignInfo)]),
         "tksmseq_map_extend": (C.c_int, [vp, P(MapParams), P(AlignParams), P(ExtendParams), C.c_char_p, C.c_char_p, P(MapInfo), P(AlignInfo), P(ExtendInfo)]),
+        "tksmseq_map_split": (C.c_int, [vp, P(MapParams), P(AlignParams), P(ExtendParams), P(SplitParams), C.c_char_p, C.c_char_p, P(MapInfo), P(AlignInfo), P(ExtendInfo),
+                                        P(SplitInfo)]),
         "tksmseq_filter": (C.c_int, [vp, vp, P(FilterParams), P(vp), P(vp)]),
         "tksmseq_concat": (C.c_int, [vp, P(vp), u64, i32, P(vp)]),
         "tksmseq_filter_main": (C.c_int, [C.c_int, P(C.c_char_p)]),

@@ -1,8 +1,9 @@
-// map_api.cpp -- C-ABI of map: tksmseq_map, tksmseq_map_align and tksmseq_map_extend (include/tksmseq.h).  The host reads and checks (ms_host.cpp's FASTQ reader, map_host.cpp), packs
+// map_api.cpp -- C-ABI of map: tksmseq_map, tksmseq_map_align, tksmseq_map_extend and tksmseq_map_split (include/tksmseq.h).  The host reads and checks (ms_host.cpp's FASTQ reader, map_host.cpp), packs
 // the reads of a chunk and formats the PAF; the sketch of targets and reads, the index, the seeds, the chains and the choice of the lines run
 // on the device (map_kernels.hip, with the radix sort of abundance and the run kernels of model-sequence), and with alignment the anchors of
 // the written chains, their banded alignment and the run-length code of its columns (map_align_kernels.hip), and with extension the X-drop
-// extension of both ends of every written chain (map_extend_kernels.hip).
+// extension of both ends of every written chain (map_extend_kernels.hip), and with split the rounds of every group and the supplementary lines
+// of every read (map_split_kernels.hip) in place of the chain launch and the selection.
 #include <cstring>
 #include <string>
 #include <vector>
@@ -13,6 +14,7 @@
 #include "map_extend_kernels.h"
 #include "map_host.h"
 #include "map_kernels.h"
+#include "map_split_kernels.h"
 #include "ms_kernels.h"
 #include "tool_run.h"
 
@@ -47,6 +49,9 @@ struct MapRun {
     bool extended = false;
     tksmseq_extend_params xp{31, 40, 2000, 0};
     tksmseq_extend_info xinfo{};
+    bool split = false;
+    tksmseq_split_params sp{4, 30, 8, 0};
+    tksmseq_split_info sinfo{};
     Events<2> ev;
     // the index: distinct hashes with their runs in the sorted entries
     TmpBuf d_tvalid, d_tseq, d_dkey, d_dcount, d_dstart, d_iseq, d_ips;
@@ -155,7 +160,8 @@ int MapRun::build_index() {
 
 // reads [r0, r1): their lines appended to paf, or RC_SPLIT (nothing appended, no counter touched) when they have more anchors than the budget
 int MapRun::chunk(uint32_t r0, uint32_t r1) {
-    const uint32_t n = r1 - r0, slots = (uint32_t)p.max_secondary + 1u;
+    const uint32_t n = r1 - r0, slots = (uint32_t)p.max_secondary + (split ? (uint32_t)sp.segments : 1u);
+    const uint32_t rounds = split ? (uint32_t)sp.chains : 1u;                    // chains a group has room for
     std::vector<uint32_t> h_codes, h_valid;
     std::vector<tkh::MapSeq> h_seqs;
     std::vector<tkh::MapTile> tiles;
@@ -231,39 +237,61 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
     }
     if (int rc = end(ST_SEED)) return rc;
 
-    // ---- chain: one wave per surviving group
-    const uint32_t nc = (uint32_t)n_chained;
-    TmpBuf d_pred(s), d_chain(s);
+    // ---- chain: one wave per surviving group; with split all rounds of the group, chain c * rounds + r its round r
+    const uint32_t n_listed = (uint32_t)n_chained, nc = n_listed * rounds;       // (n_listed <= 2^24 anchors, rounds <= 16)
+    TmpBuf d_pred(s), d_chain(s), d_rem(s), d_listx(s);
     std::vector<tkh::MapChain> chains(nc);
+    float chain_ms = 0.f, select_ms = 0.f;
     if (int rc = begin()) return rc;
     HIPCHK(ctx, d_pred.ensure(std::max<size_t>(na, 1) * 4));
     HIPCHK(ctx, d_chain.ensure(std::max<size_t>(nc, 1) * sizeof(tk::MapChain)));
     const tk::MapChainParams CP{(uint32_t)p.k, (uint32_t)p.max_gap, (uint32_t)p.bandwidth, (uint32_t)p.min_count, (uint32_t)p.min_score};
-    HIPCHK(ctx, tk::launch_map_chain(d_k1f.as<uint64_t>(), d_k2s.as<uint64_t>(), d_gstart.as<uint32_t>(), d_list.as<uint32_t>(), nc, CP, d_pred.as<uint32_t>(),
-                                     d_chain.as<tk::MapChain>(), s));
-    if (int rc = end(ST_CHAIN)) return rc;
+    if (split) {
+        HIPCHK(ctx, d_rem.ensure(std::max<size_t>(na, 1) * 4));
+        HIPCHK(ctx, d_listx.ensure(std::max<size_t>(nc, 1) * 4));
+        HIPCHK(ctx, tk::launch_map_chain_split(d_k1f.as<uint64_t>(), d_k2s.as<uint64_t>(), d_gstart.as<uint32_t>(), d_list.as<uint32_t>(), n_listed, CP, rounds,
+                                               d_rem.as<uint32_t>(), d_pred.as<uint32_t>(), d_chain.as<tk::MapChain>(), s));
+        HIPCHK(ctx, tk::launch_map_split_list(d_list.as<uint32_t>(), n_listed, rounds, d_listx.as<uint32_t>(), s));
+    } else {
+        HIPCHK(ctx, tk::launch_map_chain(d_k1f.as<uint64_t>(), d_k2s.as<uint64_t>(), d_gstart.as<uint32_t>(), d_list.as<uint32_t>(), nc, CP, d_pred.as<uint32_t>(),
+                                         d_chain.as<tk::MapChain>(), s));
+    }
+    if (int rc = end(chain_ms)) return rc;
+    info.stage_ms[ST_CHAIN] += chain_ms;
 
     // ---- select: the kept chains by (read, score descending), target and rel ascending by the sort's stability
-    TmpBuf d_key(s), d_keys(s), d_perm(s), d_nl(s), d_mq(s), d_lines(s);
-    std::vector<uint32_t> n_lines(n), mapq(n), lines((size_t)n * slots);
+    // (with split every line has a mapq of its own, and a read says how many of its lines step A wrote and how many candidates step B refused)
+    TmpBuf d_key(s), d_keys(s), d_perm(s), d_nl(s), d_mq(s), d_lines(s), d_nf(s), d_rej(s);
+    std::vector<uint32_t> n_lines(n), mapq(split ? (size_t)n * slots : n), lines((size_t)n * slots), n_first(split ? n : 0), rejected(split ? n : 0);
     if (int rc = begin()) return rc;
     HIPCHK(ctx, d_key.ensure(std::max<size_t>(nc, 1) * 8));
     HIPCHK(ctx, d_keys.ensure(std::max<size_t>(nc, 1) * 8));
     HIPCHK(ctx, d_perm.ensure(std::max<size_t>(nc, 1) * 4));
     HIPCHK(ctx, d_nl.ensure((size_t)n * 4));
-    HIPCHK(ctx, d_mq.ensure((size_t)n * 4));
+    HIPCHK(ctx, d_mq.ensure(mapq.size() * 4));
     HIPCHK(ctx, d_lines.ensure((size_t)n * slots * 4));
     if (nc) {
         HIPCHK(ctx, tk::launch_map_chain_keys(d_chain.as<tk::MapChain>(), nc, d_key.as<uint64_t>(), s));
         if (int rc = sort_pairs<uint64_t>(ctx, tk::abund_sort_u64, d_key.as<uint64_t>(), d_keys.as<uint64_t>(), d_perm.as<uint32_t>(), nc, 64)) return rc;
     }
-    HIPCHK(ctx, tk::launch_map_select(d_keys.as<uint64_t>(), d_perm.as<uint32_t>(), nc, n, permille, (uint32_t)p.max_secondary, d_nl.as<uint32_t>(), d_mq.as<uint32_t>(),
-                                      d_lines.as<uint32_t>(), s));
+    if (split) {
+        HIPCHK(ctx, d_nf.ensure((size_t)n * 4));
+        HIPCHK(ctx, d_rej.ensure((size_t)n * 4));
+        const tk::MapSplitSelect SS{permille, (uint32_t)p.max_secondary, rounds, (uint32_t)sp.overlap, (uint32_t)sp.segments};
+        HIPCHK(ctx, tk::launch_map_select_split(d_keys.as<uint64_t>(), d_perm.as<uint32_t>(), d_chain.as<tk::MapChain>(), d_seqs.as<tk::MapSeq>(), nc, n, SS, d_nl.as<uint32_t>(),
+                                                d_nf.as<uint32_t>(), d_mq.as<uint32_t>(), d_lines.as<uint32_t>(), d_rej.as<uint32_t>(), s));
+        HIPCHK(ctx, hipMemcpyAsync(n_first.data(), d_nf.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(rejected.data(), d_rej.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    } else {
+        HIPCHK(ctx, tk::launch_map_select(d_keys.as<uint64_t>(), d_perm.as<uint32_t>(), nc, n, permille, (uint32_t)p.max_secondary, d_nl.as<uint32_t>(), d_mq.as<uint32_t>(),
+                                          d_lines.as<uint32_t>(), s));
+    }
     HIPCHK(ctx, hipMemcpyAsync(n_lines.data(), d_nl.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(mapq.data(), d_mq.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(mapq.data(), d_mq.p, mapq.size() * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipMemcpyAsync(lines.data(), d_lines.p, (size_t)n * slots * 4, hipMemcpyDeviceToHost, s));
     if (nc) HIPCHK(ctx, hipMemcpyAsync(chains.data(), d_chain.p, (size_t)nc * sizeof(tk::MapChain), hipMemcpyDeviceToHost, s));
-    if (int rc = end(ST_SELECT)) return rc;
+    if (int rc = end(select_ms)) return rc;
+    info.stage_ms[ST_SELECT] += select_ms;
 
     // ---- the lines of the chunk: checked, with alignment aligned, then written
     std::vector<tkh::MapAlnLine> alines;
@@ -272,7 +300,9 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
     MapExtended ex;
     uint64_t segments = 0, col_words = 0;
     for (uint32_t r = 0; r < n; r++) {
-        if (n_lines[r] > slots) { ctx->err = "map: more lines for a read than it may have"; return TKSMSEQ_EDEVICE; }
+        if (n_lines[r] > slots || (split && (n_first[r] > n_lines[r] || n_first[r] > (uint32_t)p.max_secondary + 1u || (n_lines[r] && !n_first[r])))) {
+            ctx->err = "map: more lines for a read than it may have"; return TKSMSEQ_EDEVICE;
+        }
         for (uint32_t i = 0; i < n_lines[r]; i++) {
             const uint32_t c = lines[(size_t)r * slots + i];
             if (c >= nc || chains[c].read != r || (chains[c].tr >> 1) >= ctx->contig_names.size()) { ctx->err = "map: a line of a chain that does not exist"; return TKSMSEQ_EDEVICE; }
@@ -280,7 +310,7 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
             line_chain.push_back(c);
         }
     }
-    const MapChunkBufs bufs{d_codes, d_valid, d_seqs, d_chain, d_list, d_gstart, d_k1f, d_pred};
+    const MapChunkBufs bufs{d_codes, d_valid, d_seqs, d_chain, split ? d_listx : d_list, d_gstart, d_k1f, d_pred};
     if (aligned && !alines.empty())
         if (int rc = align(alines, segments, col_words, n == 1, names[r0], bufs, al)) return rc;
     if (extended && !line_chain.empty())
@@ -288,11 +318,28 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
     t0 = std::chrono::steady_clock::now();
     size_t at = 0;
     std::vector<uint64_t> joined_runs;
+    std::vector<std::pair<uint32_t, uint32_t>> p_iv;                // the read intervals of a read's tp:A:P lines, the primary first
+    std::vector<uint32_t> p_rank;
     for (uint32_t r = 0; r < n; r++) {
         if (!n_lines[r]) { info.unmapped++; continue; }
         info.mapped++;
+        const uint32_t first = split ? n_first[r] : n_lines[r], sn = 1u + n_lines[r] - first;
+        if (sn > 1u) {
+            p_iv.clear();
+            for (uint32_t i = 0; i < n_lines[r]; i = std::max(i + 1u, first)) {
+                const tkh::MapChain& x = chains[lines[(size_t)r * slots + i]];
+                p_iv.push_back((x.tr & 1u) ? std::make_pair(h_seqs[r].len - x.qe, h_seqs[r].len - x.qs) : std::make_pair(x.qs, x.qe));
+            }
+            tkh::map_split_ranks(p_iv, p_rank);
+            sinfo.split_reads++;
+            sinfo.supplementary += sn - 1u;
+        }
+        if (split) sinfo.rejected_overlap += rejected[r];
         for (uint32_t i = 0; i < n_lines[r]; i++, at++) {
             const uint32_t c = lines[(size_t)r * slots + i], t = chains[c].tr >> 1;
+            const bool is_p = i == 0 || i >= first;                 // the primary or a supplementary line
+            const uint32_t mq = split ? mapq[(size_t)r * slots + i] : (i ? 0u : mapq[r]);
+            const uint32_t si = sn > 1u && is_p ? p_rank[i ? 1u + i - first : 0u] : 0u, tag_n = is_p ? sn : 0u;
             tkh::MapChain ch = chains[c];
             const tkh::MapAlnOut* ao = aligned ? &al.outs[at] : nullptr;
             const uint64_t* runs = aligned ? al.runs.data() + al.run_off[at] : nullptr;
@@ -317,12 +364,12 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
                 xinfo.longest = std::max<uint64_t>(xinfo.longest, std::max(le.ei + le.ej, re.ei + re.ej));
             }
             if (aligned)
-                tkh::map_paf_line_aligned(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], ch, i ? 0u : mapq[r], i == 0, *ao, runs,
-                                          ap.eqx != 0, paf);
+                tkh::map_paf_line_aligned(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], ch, mq, is_p, *ao, runs,
+                                          ap.eqx != 0, paf, tag_n, si);
             else
-                tkh::map_paf_line(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], ch, i ? 0u : mapq[r], i == 0, paf);
+                tkh::map_paf_line(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], ch, mq, is_p, paf, tag_n, si);
             info.lines++;
-            if (i) info.secondary++;
+            if (!is_p) info.secondary++;
         }
     }
     for (size_t l = 0; l < al.outs.size(); l++) {
@@ -338,6 +385,13 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
     info.groups += n_groups;
     info.chained_groups += n_chained;
     info.chunks++;
+    if (split) {
+        for (uint32_t c = 0; c < nc; c++) {
+            sinfo.rounds += chains[c].cnt > 0;                      // (a round that ran has a chain of at least one anchor)
+            sinfo.later_chains += chains[c].kept && c % rounds;
+        }
+        sinfo.split_ms += chain_ms + select_ms;
+    }
     return TKSMSEQ_OK;
 }
 
@@ -493,8 +547,9 @@ int MapRun::extend(const std::vector<uint32_t>& line_chain, bool alone, const st
 
 }  // namespace
 
-extern "C" int tksmseq_map_extend(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const tksmseq_extend_params* extend,
-                                  const char* reads_paths, const char* paf_out, tksmseq_map_info* info_out, tksmseq_align_info* align_info, tksmseq_extend_info* extend_info) {
+extern "C" int tksmseq_map_split(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const tksmseq_extend_params* extend,
+                                 const tksmseq_split_params* split, const char* reads_paths, const char* paf_out, tksmseq_map_info* info_out, tksmseq_align_info* align_info,
+                                 tksmseq_extend_info* extend_info, tksmseq_split_info* split_info) {
     if (!ctx) return TKSMSEQ_EINVAL;
     if (!reads_paths || !paf_out || !*paf_out) { ctx->err = "map: null argument"; return TKSMSEQ_EINVAL; }
     tksmseq_map_params p{};
@@ -503,6 +558,7 @@ extern "C" int tksmseq_map_extend(tksmseq_ctx* ctx, const tksmseq_map_params* pa
     if (!tkh::map_check_params(p, ctx->err)) return TKSMSEQ_EINVAL;
     if (align && !tkh::map_check_align(p, *align, ctx->err)) return TKSMSEQ_EINVAL;
     if (extend && !tkh::map_check_extend(*extend, ctx->err)) return TKSMSEQ_EINVAL;
+    if (split && !tkh::map_check_split(*split, ctx->err)) return TKSMSEQ_EINVAL;
     if (ctx->contigs.empty()) { ctx->err = "map: the context has no reference"; return TKSMSEQ_EINVAL; }
     if (ctx->n_declared) { ctx->err = "map: the reference has contigs that are declared only"; return TKSMSEQ_EINVAL; }
     if (ctx->contigs.size() / 2 >= MAP_LIMIT) { ctx->err = "map: 2^31 targets or more"; return TKSMSEQ_ELIMIT; }
@@ -526,6 +582,7 @@ extern "C" int tksmseq_map_extend(tksmseq_ctx* ctx, const tksmseq_map_params* pa
     run.reads = &reads;
     if (align) { run.aligned = true; run.ap = *align; }
     if (extend) { run.extended = true; run.xp = *extend; }
+    if (split) { run.split = true; run.sp = *split; }
     run.names = reads.names();
     run.info.reads = n_reads;
     run.info.read_ms = ms_since(t0);
@@ -538,7 +595,8 @@ extern "C" int tksmseq_map_extend(tksmseq_ctx* ctx, const tksmseq_map_params* pa
     {
         size_t free_b = 0, total_b = 0;
         HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
-        run.anchor_budget = std::max(MAP_ANCHORS_MIN, std::min<uint64_t>(MAP_ANCHORS_MAX, free_b / 4 / MAP_ANCHOR_BYTES));
+        const uint64_t anchor_bytes = MAP_ANCHOR_BYTES + (split ? tkh::map_split_anchor_bytes(*split, p.min_count) : 0);
+        run.anchor_budget = std::max(MAP_ANCHORS_MIN, std::min<uint64_t>(MAP_ANCHORS_MAX, free_b / 4 / anchor_bytes));
         run.align_budget = std::min<uint64_t>(tkh::MAP_ALN_BYTES_MAX, std::max<uint64_t>(free_b / 4, 1ull << 20));
         if (!chunk_reads) {
             // per read: its packed letters, and about two minimizers in w + 1 positions through sketch and seed
@@ -574,7 +632,13 @@ extern "C" int tksmseq_map_extend(tksmseq_ctx* ctx, const tksmseq_map_params* pa
     if (info_out) *info_out = info;
     if (align_info) *align_info = run.ainfo;
     if (extend_info) *extend_info = run.xinfo;
+    if (split_info) *split_info = run.sinfo;
     return TKSMSEQ_OK;
+}
+
+extern "C" int tksmseq_map_extend(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const tksmseq_extend_params* extend,
+                                  const char* reads_paths, const char* paf_out, tksmseq_map_info* info_out, tksmseq_align_info* align_info, tksmseq_extend_info* extend_info) {
+    return tksmseq_map_split(ctx, params, align, extend, nullptr, reads_paths, paf_out, info_out, align_info, extend_info, nullptr);
 }
 
 extern "C" int tksmseq_map_align(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const char* reads_paths, const char* paf_out,

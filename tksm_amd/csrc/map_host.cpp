@@ -76,10 +76,19 @@ void paf_fields(const std::string& qname, uint32_t qlen, const std::string& tnam
     out += "\tcm:i:"; out += std::to_string(c.cnt);
     out += "\ts1:i:"; out += std::to_string(c.score);
 }
+
+// the two tags of a read with several tp:A:P lines
+void split_tags(uint32_t sn, uint32_t si, std::string& out) {
+    if (sn < 2) return;
+    out += "\tsn:i:"; out += std::to_string(sn);
+    out += "\tsi:i:"; out += std::to_string(si);
+}
 }  // namespace
 
-void map_paf_line(const std::string& qname, uint32_t qlen, const std::string& tname, uint64_t tlen, const MapChain& c, uint32_t mapq, bool primary, std::string& out) {
+void map_paf_line(const std::string& qname, uint32_t qlen, const std::string& tname, uint64_t tlen, const MapChain& c, uint32_t mapq, bool primary, std::string& out,
+                  uint32_t sn, uint32_t si) {
     paf_fields(qname, qlen, tname, tlen, c, mapq, primary, c.nmatch, std::max(c.tend - c.tstart, c.qe - c.qs), out);
+    split_tags(sn, si, out);
     out += '\n';
 }
 
@@ -102,8 +111,9 @@ uint32_t map_align_waves(uint64_t budget, uint64_t fixed, uint64_t lines, uint32
 }
 
 void map_paf_line_aligned(const std::string& qname, uint32_t qlen, const std::string& tname, uint64_t tlen, const MapChain& c, uint32_t mapq, bool primary,
-                          const MapAlnOut& a, const uint64_t* runs, bool eqx, std::string& out) {
+                          const MapAlnOut& a, const uint64_t* runs, bool eqx, std::string& out, uint32_t sn, uint32_t si) {
     paf_fields(qname, qlen, tname, tlen, c, mapq, primary, a.eq, a.ncols, out);
+    split_tags(sn, si, out);
     out += "\tNM:i:"; out += std::to_string((uint64_t)a.x + a.ins + a.del);
     out += "\tcg:Z:";
     const char* ops = eqx ? "=XID" : "MMID";
@@ -142,6 +152,27 @@ MapAlnOut map_join_columns(const MapAlnOut* left, const uint64_t* left_runs, con
     if (right) add(*right, right_runs);
     o.runs = (uint32_t)runs.size();
     return o;
+}
+
+bool map_check_split(const tksmseq_split_params& s, std::string& err) {
+    if (s.chains < 1 || s.chains > 16) { err = "map: split chains must be in [1, 16]"; return false; }
+    if (s.overlap < 0) { err = "map: split overlap must not be negative"; return false; }
+    if (s.segments < 2 || s.segments > 64) { err = "map: split segments must be in [2, 64]"; return false; }
+    return true;
+}
+
+uint64_t map_split_anchor_bytes(const tksmseq_split_params& s, int32_t min_count) {
+    // a chain, its key before and after the sort, its place in the permutation and its group's entry in the expanded list
+    const uint64_t per_chain = sizeof(MapChain) + 8 + 8 + 4 + 4, groups_share = (uint64_t)std::max(min_count, 1);
+    return 4 + ((uint64_t)s.chains * per_chain + groups_share - 1) / groups_share;
+}
+
+void map_split_ranks(const std::vector<std::pair<uint32_t, uint32_t>>& iv, std::vector<uint32_t>& rank) {
+    std::vector<uint32_t> order(iv.size());
+    for (uint32_t i = 0; i < order.size(); i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return iv[a] < iv[b]; });
+    rank.assign(iv.size(), 0u);
+    for (uint32_t i = 0; i < order.size(); i++) rank[order[i]] = i;
 }
 
 }  // namespace tkh

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/tksmseq.h"
@@ -33,7 +34,9 @@ void map_add_tiles(uint32_t seq, uint64_t len, uint32_t k, uint32_t w, std::vect
 void map_pack_reads(const MsReads& reads, uint32_t r0, uint32_t r1, std::vector<uint32_t>& codes, std::vector<uint32_t>& valid, std::vector<MapSeq>& seqs);
 
 // one line of the PAF for a chain of read `qname` (qlen letters) on target `tname` (tlen letters)
-void map_paf_line(const std::string& qname, uint32_t qlen, const std::string& tname, uint64_t tlen, const MapChain& c, uint32_t mapq, bool primary, std::string& out);
+// (sn >= 2: the sn:i: and si:i: tags of "map, split reads" follow s1:i:)
+void map_paf_line(const std::string& qname, uint32_t qlen, const std::string& tname, uint64_t tlen, const MapChain& c, uint32_t mapq, bool primary, std::string& out,
+                  uint32_t sn = 0, uint32_t si = 0);
 
 // ---- map -c ("map, alignment" in include/tksmseq.h; the kernels are described in map_align_kernels.h)
 constexpr int32_t MAP_ALN_MAX_GAP = 65536;         // a segment's traceback store is sized by dt + dq
@@ -62,7 +65,7 @@ uint64_t map_align_fixed_bytes(uint64_t lines, uint64_t segments, uint64_t col_w
 uint32_t map_align_waves(uint64_t budget, uint64_t fixed, uint64_t lines, uint32_t longest);
 // the aligned form of map_paf_line: columns 10 and 11 from the columns, NM:i: and cg:Z: appended.  runs[r] = first column << 2 | op.
 void map_paf_line_aligned(const std::string& qname, uint32_t qlen, const std::string& tname, uint64_t tlen, const MapChain& c, uint32_t mapq, bool primary,
-                          const MapAlnOut& a, const uint64_t* runs, bool eqx, std::string& out);
+                          const MapAlnOut& a, const uint64_t* runs, bool eqx, std::string& out, uint32_t sn = 0, uint32_t si = 0);
 
 // ---- map --extend ("map, end extension" in include/tksmseq.h; the kernels are described in map_extend_kernels.h)
 // one end of a line (end 0: left, 1: right).  The second pass also reads where its columns go (words), the best cell and cap = ei + ej
@@ -84,5 +87,14 @@ inline MapChain map_extended_chain(MapChain c, const MapExtEnd& left, const MapE
 // the parts are joined where two parts meet in the same op; `runs` gets first column << 2 | op of the whole line
 MapAlnOut map_join_columns(const MapAlnOut* left, const uint64_t* left_runs, const MapAlnOut& mid, const uint64_t* mid_runs, const MapAlnOut* right,
                            const uint64_t* right_runs, std::vector<uint64_t>& runs);
+
+// ---- map --split ("map, split reads" in include/tksmseq.h; the kernels are described in map_split_kernels.h)
+// chains in [1, 16], overlap in [0, 2^31), segments in [2, 64]; false: err says which
+bool map_check_split(const tksmseq_split_params& s, std::string& err);
+// device bytes an anchor takes more with split: its word of the list, and its share of the further chains of its group (a chained group has
+// at least min_count anchors) through the key sort and the selection
+uint64_t map_split_anchor_bytes(const tksmseq_split_params& s, int32_t min_count);
+// rank[i] = the 0-based rank of tp:A:P line i of a read by (qstart, qend, i); iv[i] = {qstart, qend} in original read coordinates
+void map_split_ranks(const std::vector<std::pair<uint32_t, uint32_t>>& iv, std::vector<uint32_t>& rank);
 
 }  // namespace tkh

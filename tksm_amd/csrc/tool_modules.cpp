@@ -334,8 +334,9 @@ extern "C" int tksmseq_map_main(int argc, char** argv) {
     p.k = 15; p.w = 10; p.max_occ = 500; p.max_gap = 5000; p.bandwidth = 500; p.min_count = 3; p.min_score = 40; p.secondary_ratio = 0.8; p.max_secondary = 5;
     tksmseq_align_params ap{63, 0};
     tksmseq_extend_params xp{31, 40, 2000, 0};
-    bool align = false, band_given = false, extend = false;
-    std::string ext_given;                                      // the first --ext-* option seen
+    tksmseq_split_params sp{4, 30, 8, 0};
+    bool align = false, band_given = false, extend = false, split = false;
+    std::string ext_given, split_given;                         // the first --ext-* and the first --split-* option seen
     std::string reference, reads;
     Ranges ranges;
     if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
@@ -343,6 +344,7 @@ extern "C" int tksmseq_map_main(int argc, char** argv) {
             if (o == "-c") { align = true; return TOOK_FLAG; }
             if (o == "--eqx") { ap.eqx = 1; return TOOK_FLAG; }
             if (o == "--extend") { extend = true; return TOOK_FLAG; }
+            if (o == "--split") { split = true; return TOOK_FLAG; }
             long long iv = 0;
             if ((o == "-r" || o == "--reference") && v) reference = v;
             else if (o == "--reads" && v) reads = v;
@@ -350,6 +352,9 @@ extern "C" int tksmseq_map_main(int argc, char** argv) {
             else if (o == "--ext-band" && v) { if (!ranges.check(o, v, 1, 63, "must be between 1 and 63", iv)) return MALFORMED; xp.band = (int32_t)iv; if (ext_given.empty()) ext_given = o; }
             else if (o == "--ext-drop" && v) { if (!ranges.check(o, v, 1, 1000, "must be between 1 and 1000", iv)) return MALFORMED; xp.drop = (int32_t)iv; if (ext_given.empty()) ext_given = o; }
             else if (o == "--ext-max" && v) { if (!ranges.check(o, v, 1, 32768, "must be between 1 and 32768", iv)) return MALFORMED; xp.max_ext = (int32_t)iv; if (ext_given.empty()) ext_given = o; }
+            else if (o == "--split-chains" && v) { if (!ranges.check(o, v, 1, 16, "must be between 1 and 16", iv)) return MALFORMED; sp.chains = (int32_t)iv; if (split_given.empty()) split_given = o; }
+            else if (o == "--split-overlap" && v) { if (!ranges.check(o, v, 0, 0x7FFFFFFF, "must be between 0 and 2147483647", iv)) return MALFORMED; sp.overlap = (int32_t)iv; if (split_given.empty()) split_given = o; }
+            else if (o == "--split-segments" && v) { if (!ranges.check(o, v, 2, 64, "must be between 2 and 64", iv)) return MALFORMED; sp.segments = (int32_t)iv; if (split_given.empty()) split_given = o; }
             else if (o == "-k" && v) { if (!ranges.check(o, v, 4, 28, "must be between 4 and 28", iv)) return MALFORMED; p.k = (int32_t)iv; }
             else if (o == "-w" && v) { if (!ranges.check(o, v, 1, 64, "must be between 1 and 64", iv)) return MALFORMED; p.w = (int32_t)iv; }
             else if (o == "--max-occ" && v) { if (!ranges.check(o, v, 1, 0x7FFFFFFF, "must be between 1 and 2147483647", iv)) return MALFORMED; p.max_occ = (int32_t)iv; }
@@ -367,24 +372,27 @@ extern "C" int tksmseq_map_main(int argc, char** argv) {
             return TOOK_VALUE;
         })) return 2;
     if (c.help) { printf("Maps long reads to transcripts by chains of minimizers; with -c the written chains are aligned base by base (cg:Z: and NM:i: tags);\n"
-                         "with --extend both ends of every line are extended to where an X-drop alignment carries them.\n"
+                         "with --extend both ends of every line are extended to where an X-drop alignment carries them; with --split every further piece of a\n"
+                         "chimeric or hairpin read gets a supplementary tp:A:P line (sn:i: and si:i: tags).\n"
                          "usage: map -r REF.fa[.gz][,REF2.fa] --reads F.fq[.gz][,MORE] -o OUT.paf[.gz] [-k 15] [-w 10] [--max-occ 500] [--max-gap 5000] [--bandwidth 500]\n"
                          "           [--min-count 3] [--min-score 40] [-p 0.8] [-N 5] [-c [--eqx] [--align-band 63]] [--extend [--ext-band 31] [--ext-drop 40] [--ext-max 2000]]\n"
-                         "           [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L]\n"
+                         "           [--split [--split-chains 4] [--split-overlap 30] [--split-segments 8]] [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L]\n"
                          "the output is the file `tksm abundance -p` and `tksm model-truncation -i` read; with -c also the one `tksm model-sequence --alignment` reads\n"); return 0; }
     if (!have_required("map", {{reference, "-r/--reference"}, {reads, "--reads"}, {c.output, "-o/--output"}})) return 2;
     if (!ranges.error.empty()) { fprintf(stderr, "map: error: %s\n", ranges.error.c_str()); return 2; }
     if (!align && (ap.eqx || band_given)) { fprintf(stderr, "map: error: %s needs -c\n", ap.eqx ? "--eqx" : "--align-band"); return 2; }
     if (!extend && !ext_given.empty()) { fprintf(stderr, "map: error: %s needs --extend\n", ext_given.c_str()); return 2; }
+    if (!split && !split_given.empty()) { fprintf(stderr, "map: error: %s needs --split\n", split_given.c_str()); return 2; }
     if (align && p.max_gap > 65536) { fprintf(stderr, "map: error: --max-gap must be at most 65536 with -c\n"); return 2; }
     Logger log;
     if (!open_log(c, "map", log)) return 1;
     tksmseq_map_info info{};
     tksmseq_align_info ainfo{};
     tksmseq_extend_info xinfo{};
+    tksmseq_split_info sinfo{};
     return with_context(c, [&](tksmseq_ctx* ctx) {
         if (int rc = load_references(ctx, reference, log)) return rc;
-        return tksmseq_map_extend(ctx, &p, align ? &ap : nullptr, extend ? &xp : nullptr, reads.c_str(), c.output.c_str(), &info, &ainfo, &xinfo);
+        return tksmseq_map_split(ctx, &p, align ? &ap : nullptr, extend ? &xp : nullptr, split ? &sp : nullptr, reads.c_str(), c.output.c_str(), &info, &ainfo, &xinfo, &sinfo);
     }, [&](Clock::time_point t0) {
         log.log(Logger::INFO, "map: %llu target minimizers under %llu hashes (%llu over --max-occ); %llu read minimizers, %llu anchors, %llu groups, %llu chained",
                 (unsigned long long)info.target_minimizers, (unsigned long long)info.distinct_hashes, (unsigned long long)info.dropped_hashes,
@@ -401,6 +409,14 @@ extern "C" int tksmseq_map_main(int argc, char** argv) {
             log.log(Logger::INFO, "map: %llu lines extended, %llu ends moved (the longest by %llu anti-diagonals): %llu target and %llu read letters gained, %llu matches; %llu anti-diagonals, %llu cells (device %.2f ms)",
                     (unsigned long long)xinfo.lines, (unsigned long long)xinfo.ends_moved, (unsigned long long)xinfo.longest, (unsigned long long)xinfo.target_gained,
                     (unsigned long long)xinfo.read_gained, (unsigned long long)xinfo.matches, (unsigned long long)xinfo.antidiagonals, (unsigned long long)xinfo.cells, xinfo.extend_ms);
+        if (split) {
+            log.log(Logger::INFO, "map: %llu reads split, %llu supplementary lines; %llu rounds, %llu kept chains of later rounds, %llu candidates refused for overlap (device %.2f ms)",
+                    (unsigned long long)sinfo.split_reads, (unsigned long long)sinfo.supplementary, (unsigned long long)sinfo.rounds, (unsigned long long)sinfo.later_chains,
+                    (unsigned long long)sinfo.rejected_overlap, sinfo.split_ms);
+            // every segment of a molecule but the first was glued with probability p
+            const unsigned long long J = sinfo.supplementary, M = info.mapped;
+            log.log(Logger::INFO, "split: %llu junctions in %llu mapped reads: unsegment -p estimate %.6f", J, M, M + J > 1 ? (double)J / (double)(M + J - 1) : 0.0);
+        }
         return 0;
     });
 }

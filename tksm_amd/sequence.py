@@ -606,26 +606,37 @@ class Sequencer:
         return out
 
     def map(self, reads, paf_out, k=15, w=10, max_occ=500, max_gap=5000, bandwidth=500, min_count=3, min_score=40, secondary_ratio=0.8, max_secondary=5,
-            chunk_reads=0, align=False, eqx=False, align_band=63, extend=False, ext_band=31, ext_drop=40, ext_max=2000):
+            chunk_reads=0, align=False, eqx=False, align_band=63, extend=False, ext_band=31, ext_drop=40, ext_max=2000, split=False, split_chains=4,
+            split_overlap=30, split_segments=8):
         """Long reads to the contigs of this context's reference (a cDNA FASTA) by minimizer chains on the device (tksmseq_map, the rules in
         include/tksmseq.h): `reads` (one FASTQ path or a list of them, .gz or plain) -> `paf_out`, the PAF `abundance(paf=...)` and
         `model_truncation` read.  align=True (map -c) aligns the written chains base by base (tksmseq_map_align): the lines gain NM:i: and cg:Z:
         tags, which `model_sequence` reads, with = and X in place of M when eqx, inside a band of align_band.  extend=True (map --extend,
         tksmseq_map_extend) moves both ends of every line outward by a banded X-drop extension (band ext_band, drop ext_drop, at most
-        ext_max letters an end): the PAF to hand to `model_truncation`.  Returns the counters of tksmseq_map_info as a dict, with align=True
-        also those of tksmseq_align_info under "align", with extend=True those of tksmseq_extend_info under "extend"."""
+        ext_max letters an end): the PAF to hand to `model_truncation`.  split=True (map --split, tksmseq_map_split) chains every group in up
+        to split_chains rounds and writes a supplementary tp:A:P line for every further piece of a chimeric or hairpin read, at most
+        split_segments tp:A:P lines a read, their read intervals sharing at most split_overlap letters.  Returns the counters of
+        tksmseq_map_info as a dict, with align=True also those of tksmseq_align_info under "align", with extend=True those of
+        tksmseq_extend_info under "extend", with split=True those of tksmseq_split_info under "split"."""
         if not align and (eqx or align_band != 63):
             raise ValueError("eqx and align_band need align=True")
         if not extend and (ext_band != 31 or ext_drop != 40 or ext_max != 2000):
             raise ValueError("ext_band, ext_drop and ext_max need extend=True")
+        if not split and (split_chains != 4 or split_overlap != 30 or split_segments != 8):
+            raise ValueError("split_chains, split_overlap and split_segments need split=True")
         if not isinstance(reads, (list, tuple)):
             reads = [reads]
         p = L.MapParams(int(k), int(w), int(max_occ), int(max_gap), int(bandwidth), int(min_count), int(min_score), 0, float(secondary_ratio), int(max_secondary), 0,
                         int(chunk_reads))
         info = L.MapInfo()
         paths = ",".join(str(r) for r in reads).encode()
-        ainfo, xinfo = L.AlignInfo(), L.ExtendInfo()
-        if extend:
+        ainfo, xinfo, sinfo = L.AlignInfo(), L.ExtendInfo(), L.SplitInfo()
+        if split:
+            ap, xp = L.AlignParams(int(align_band), 1 if eqx else 0), L.ExtendParams(int(ext_band), int(ext_drop), int(ext_max), 0)
+            sp = L.SplitParams(int(split_chains), int(split_overlap), int(split_segments), 0)
+            self._chk(self._lib.tksmseq_map_split(self._ctx, C.byref(p), C.byref(ap) if align else None, C.byref(xp) if extend else None, C.byref(sp), paths,
+                                                  str(paf_out).encode(), C.byref(info), C.byref(ainfo), C.byref(xinfo), C.byref(sinfo)))
+        elif extend:
             ap, xp = L.AlignParams(int(align_band), 1 if eqx else 0), L.ExtendParams(int(ext_band), int(ext_drop), int(ext_max), 0)
             self._chk(self._lib.tksmseq_map_extend(self._ctx, C.byref(p), C.byref(ap) if align else None, C.byref(xp), paths, str(paf_out).encode(), C.byref(info),
                                                    C.byref(ainfo), C.byref(xinfo)))
@@ -640,6 +651,8 @@ class Sequencer:
             out["align"] = {n: getattr(ainfo, n) for n, _ in L.AlignInfo._fields_ if n != "reserved"}
         if extend:
             out["extend"] = {n: getattr(xinfo, n) for n, _ in L.ExtendInfo._fields_ if n != "reserved"}
+        if split:
+            out["split"] = {n: getattr(sinfo, n) for n, _ in L.SplitInfo._fields_ if n != "reserved"}
         return out
 
     # ---- random-wgs: whole-genome fragments made on the device
