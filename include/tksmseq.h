@@ -1244,12 +1244,99 @@ typedef struct tksmseq_split_info {
 int tksmseq_map_split(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const tksmseq_extend_params* extend,
                       const tksmseq_split_params* split, const char* reads_paths, const char* paf_out, tksmseq_map_info* info, tksmseq_align_info* align_info,
                       tksmseq_extend_info* extend_info, tksmseq_split_info* split_info);
-/* `tksm map`: -r REF.fa[.gz][,REF2.fa] --reads F.fq[.gz][,MORE] -o OUT.paf[.gz] [-k 15] [-w 10] [--max-occ 500] [--max-gap 5000] [--bandwidth 500]
+
+/* ---- map, annotated targets: map to transcripts spliced from genome + GTF on the device (map -g, --genome-coords, --targets-out) ------------------
+ * The mapper above wants a cDNA FASTA as its reference.  A target set is that reference made from what the simulator starts from: the
+ * context's reference (the genome) and its transcript table (tksmseq_transcripts_add_gtf).  Target t is by definition the molecule
+ * `transcribe` emits for its transcript.  These are this build's rules; no tool of the reference does this.
+ *
+ * Which transcripts become targets.  The walk goes over the transcript table in table order.  A transcript is skipped and counted when it
+ * has no exon or all its exons are empty, start = end (skipped_empty); else when any exon names a contig the context's reference lacks, or
+ * one that is declared only (skipped_unknown_contig); else when any exon has end < start or end > its contig's length (skipped_bad_exon).
+ * The kept ones are the targets 0 .. n - 1 in table order; the name of a target is the table's id.  transcripts = targets + the three.
+ *
+ * Letters.  Target t is the concatenation of its exons in FILE order (src/gtf.h:295-301: exons stay in file order, each with its own
+ * strand).  A `+` exon gives the contig's letters [start, end), upper-cased; a `-` exon their reverse complement, exon by exon.  This is
+ * the sequence `tksm sequence --perfect` writes for the molecule `tksm transcribe` emits for that transcript.  A letter is valid iff the
+ * genome letter is one of ACGT; an invalid letter has code 0 and validity bit 0.
+ *
+ * Image.  The layout is the one the mapper reads: target t starts at validity word voff[t], its code words at 2 voff[t]; 16 letters a code
+ * word, letter g in bits 2 (g & 15); 32 letters a validity word, letter g in bit g & 31.  voff[0] = 0, voff[t + 1] = voff[t] +
+ * ceil(len[t] / 32), image_vwords = voff[n].  Every bit at or behind len[t] in a target's last words is 0 in both images: no result depends
+ * on what recycled device memory held.
+ *
+ * FASTA.  ">name\n", then the letters decoded from the downloaded image, N for an invalid letter, wrapped at line_width letters (0: one
+ * line), every record ends with '\n'.  A path that ends in .gz is compressed by the host's zlib.  The file goes to <path>.tmp and is renamed.
+ *
+ * Projectable.  A target is projectable when its non-empty exons all lie on one contig with one strand and do not turn back: in file
+ * order start[i + 1] >= end[i] for `+`, end[i + 1] <= start[i] for `-`.  Empty exons are ignored.
+ *
+ * Staleness.  A target set belongs to the context that made it and records that context's reference version (it changes with every contig
+ * added or declared) and the serial of the transcript table.  Using it after either has changed is TKSMSEQ_EINVAL.
+ *
+ * Limits.  2^31 targets, a target of 2^31 letters, or 2^36 letters in all: TKSMSEQ_ELIMIT.  No transcript table, no reference, or no
+ * target kept: TKSMSEQ_EINVAL.
+ *
+ * On the device: the validity of the genome is built as for the mapper (one bit a letter, from the exception blocks); one kernel then
+ * builds both images in one pass from the genome's packed image, that validity and the kept exons as tuples (first letter in the genome,
+ * letters of the target before it, length and strand): one lane per validity word finds its target and its first exon by binary search
+ * and walks the exons until its 32 letters are filled, a `+` exon by a funnel shift of adjacent genome words, a `-` exon from the mirrored
+ * words.  The transcripts are not uploaded as text and the host does not splice.  splice_ms: by HIP events, the validity and the splice.
+ *
+ * Mapping.  tksmseq_map_targets with targets == NULL is exactly tksmseq_map_split.  With a target set, its image, names and lengths take
+ * the place of the context's reference in the index, the alignment, the extension and the lines; sketch, seed, chain, select, -c,
+ * --extend and --split keep their rules.  Defining property: with genome_coords = 0 the PAF is byte for byte the PAF of tksmseq_map_split
+ * on a context whose reference is the FASTA of tksmseq_targets_write_fasta, for every combination of the modes and every chunk_reads.
+ *
+ * Projection (genome_coords = 1; needs targets, else TKSMSEQ_EINVAL), on the host as the lines are written.
+ * Mapping a position: let m be the transcript's strand; transcript position x lies in (non-empty) exon e at offset o; G(x) = start_e + o
+ * for `+`, G(x) = end_e - 1 - o for `-`.
+ * Which lines: a line with target interval [a, b) on a projectable target is projected; a line on any other target is written unchanged
+ * and counted (unprojected); after such a call tksmseq_last_error names the first such transcript, and the module logs that line once.
+ * Columns of a projected line: column 5 is `+` iff rel ^ m == 0; column 6 is the contig's name, column 7 its length; columns 8 and 9 are
+ * G(a), G(b - 1) + 1 for `+` and G(b - 1), G(a) + 1 for `-`; columns 1 to 4, 10, 11, 12 and the tp cm s1 sn si NM tags are unchanged;
+ * tx:Z:<transcript id> is appended as the last tag.
+ * CIGAR of a projected line (with -c): the runs are walked in transcript order.  A run that consumes the target (M = X D) is cut at exon
+ * ends; immediately before the first target-consuming column of the next exon a run <gap>N is inserted, gap = start_next - end_prev for
+ * `+` and start_prev - end_next for `-`; a gap of 0 inserts nothing.  I runs stay where they are: an I at a junction stays with the exon
+ * before it in transcript order.  Equal neighbours are then merged, and for a `-` transcript the list is reversed.  The CIGAR then consumes
+ * column 9 - column 8 genome letters, N included, and qend - qstart read letters.
+ * Counters: lines = projected + unprojected; junctions: the N runs written, or without -c the exon boundaries the projected intervals cross. */
+typedef struct tksmseq_targets tksmseq_targets;               /* opaque; belongs to the context that made it */
+typedef struct tksmseq_targets_info {
+    uint64_t transcripts, targets, letters, exons;            /* table size; targets kept; their letters; their (non-empty) exons */
+    uint64_t skipped_empty, skipped_unknown_contig, skipped_bad_exon;
+    uint64_t projectable;                                     /* targets that genome_coords can project */
+    uint64_t image_vwords;                                    /* validity words of the image (32 letters each) */
+    float splice_ms, reserved;                                /* by HIP events */
+} tksmseq_targets_info;
+int tksmseq_targets_from_transcripts(tksmseq_ctx* ctx, tksmseq_targets** out, tksmseq_targets_info* info /* or NULL */);
+/* target t: its name (valid until the set is freed), length, first validity word, and whether it is projectable; any may be NULL */
+int tksmseq_targets_get(const tksmseq_targets* targets, uint64_t t, const char** name, uint32_t* len, uint64_t* voff, int32_t* projectable);
+int tksmseq_targets_download(tksmseq_ctx* ctx, const tksmseq_targets* targets, uint32_t* codes /* 2 * image_vwords */, uint32_t* valid /* image_vwords */);
+int tksmseq_targets_write_fasta(tksmseq_ctx* ctx, const tksmseq_targets* targets, const char* path, int32_t line_width /* 0: one line; the CLI writes 60 */);
+void tksmseq_targets_free(tksmseq_ctx* ctx, tksmseq_targets* targets);
+typedef struct tksmseq_map_targets_params {
+    int32_t genome_coords;           /* --genome-coords */
+    int32_t reserved;
+} tksmseq_map_targets_params;
+typedef struct tksmseq_project_info {
+    uint64_t lines, projected, unprojected, junctions;
+} tksmseq_project_info;
+/* targets NULL: exactly tksmseq_map_split (tp NULL or genome_coords 0).  tp NULL: genome_coords 0.  The info pointers may be NULL. */
+int tksmseq_map_targets(tksmseq_ctx* ctx, const tksmseq_targets* targets, const tksmseq_map_targets_params* tp, const tksmseq_map_params* params,
+                        const tksmseq_align_params* align, const tksmseq_extend_params* extend, const tksmseq_split_params* split, const char* reads_paths,
+                        const char* paf_out, tksmseq_map_info* info, tksmseq_align_info* align_info, tksmseq_extend_info* extend_info, tksmseq_split_info* split_info,
+                        tksmseq_project_info* project_info);
+/* `tksm map`: -r REF.fa[.gz][,REF2.fa] [-g GTF[,GTF...] [--genome-coords] [--targets-out CDNA.fa[.gz]]] --reads F.fq[.gz][,MORE] -o OUT.paf[.gz] [-k 15] [-w 10] [--max-occ 500] [--max-gap 5000] [--bandwidth 500]
  * [--min-count 3] [--min-score 40] [-p 0.8] [-N 5] [-c [--eqx] [--align-band 63]] [--extend [--ext-band 31] [--ext-drop 40] [--ext-max 2000]]
  * [--split [--split-chains 4] [--split-overlap 30] [--split-segments 8]] [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L].
  * Exit codes as the other model modules: 2 for a missing required option, an unknown option or a value out of range ("map: error: ..."; also
  * --eqx or --align-band without -c, an --ext-* option without --extend, a --split-* option without --split, and --max-gap above 65536 with
- * -c), checked before any device is opened; 1 for everything that fails later. */
+ * -c), checked before any device is opened; 1 for everything that fails later.
+ * With -g the reference is the genome and the targets are the transcripts of the GTFs (read with skip_non_coding = 0), "map, annotated
+ * targets" above; --targets-out writes their FASTA (60 letters a line).  --genome-coords or --targets-out without -g is exit 2.  With -g
+ * --targets-out, --reads and -o may both be absent: the FASTA is then the only output; one of the two without the other is exit 2. */
 int tksmseq_map_main(int argc, char** argv);
 
 /* The batch as MDF text, the way molecule_descriptor::operator<< writes it (src/interval.h:898-905): "+id<TAB>depth<TAB>comment",

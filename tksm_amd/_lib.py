@@ -212,6 +212,20 @@ class SplitInfo(C.Structure):              # tksmseq_split_info
                [("split_ms", C.c_float), ("reserved", C.c_float)]
 
 
+class TargetsInfo(C.Structure):            # tksmseq_targets_info
+    _fields_ = [(n, C.c_uint64) for n in ("transcripts", "targets", "letters", "exons", "skipped_empty", "skipped_unknown_contig", "skipped_bad_exon",
+                                          "projectable", "image_vwords")] + \
+               [("splice_ms", C.c_float), ("reserved", C.c_float)]
+
+
+class MapTargetsParams(C.Structure):       # tksmseq_map_targets_params
+    _fields_ = [("genome_coords", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ProjectInfo(C.Structure):            # tksmseq_project_info
+    _fields_ = [(n, C.c_uint64) for n in ("lines", "projected", "unprojected", "junctions")]
+
+
 BM_CAND_TILE = 256                           # candidates per workgroup row of the barcode match: a multiple of this (bm_kernels.h)
 BM_TARGET_WAVES = 2048                       # ... split until about this many waves (bm_kernels.h)
 BM_LIST = 8                                  # barcodes listed per read
@@ -247,6 +261,7 @@ SYMBOLS = [
     "tksmseq_model_sequence", "tksmseq_model_sequence_main",
     "tksmseq_barcode_match", "tksmseq_barcode_match_main",
     "tksmseq_map", "tksmseq_map_main", "tksmseq_map_align", "tksmseq_map_extend", "tksmseq_map_split",
+    "tksmseq_targets_from_transcripts", "tksmseq_targets_get", "tksmseq_targets_download", "tksmseq_targets_write_fasta", "tksmseq_targets_free", "tksmseq_map_targets",
     "tksmseq_filter", "tksmseq_concat", "tksmseq_filter_main",
     "tksmseq_glue", "tksmseq_glue_joins", "tksmseq_shuffle", "tksmseq_unsegment_main", "tksmseq_shuffle_main",
     "tksmseq_variants_load", "tksmseq_variants_info", "tksmseq_variants_free", "tksmseq_mutate", "tksmseq_mutate_main",
@@ -369,6 +384,13 @@ def load():
         "tksmseq_map_extend": (C.c_int, [vp, P(MapParams), P(AlignParams), P(ExtendParams), C.c_char_p, C.c_char_p, P(MapInfo), P(AlignInfo), P(ExtendInfo)]),
         "tksmseq_map_split": (C.c_int, [vp, P(MapParams), P(AlignParams), P(ExtendParams), P(SplitParams), C.c_char_p, C.c_char_p, P(MapInfo), P(AlignInfo), P(ExtendInfo),
                                         P(SplitInfo)]),
+        "tksmseq_targets_from_transcripts": (C.c_int, [vp, P(vp), P(TargetsInfo)]),
+        "tksmseq_targets_get": (C.c_int, [vp, u64, P(C.c_char_p), P(C.c_uint32), P(u64), P(i32)]),
+        "tksmseq_targets_download": (C.c_int, [vp, vp, vp, vp]),
+        "tksmseq_targets_write_fasta": (C.c_int, [vp, vp, C.c_char_p, i32]),
+        "tksmseq_targets_free": (None, [vp, vp]),
+        "tksmseq_map_targets": (C.c_int, [vp, vp, P(MapTargetsParams), P(MapParams), P(AlignParams), P(ExtendParams), P(SplitParams), C.c_char_p, C.c_char_p, P(MapInfo),
+                                          P(AlignInfo), P(ExtendInfo), P(SplitInfo), P(ProjectInfo)]),
         "tksmseq_filter": (C.c_int, [vp, vp, P(FilterParams), P(vp), P(vp)]),
         "tksmseq_concat": (C.c_int, [vp, P(vp), u64, i32, P(vp)]),
         "tksmseq_filter_main": (C.c_int, [C.c_int, P(C.c_char_p)]),

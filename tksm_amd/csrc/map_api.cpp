@@ -1,4 +1,4 @@
-// map_api.cpp -- C-ABI of map: tksmseq_map, tksmseq_map_align, tksmseq_map_extend and tksmseq_map_split (include/tksmseq.h).  The host reads and checks (ms_host.cpp's FASTQ reader, map_host.cpp), packs
+// map_api.cpp -- C-ABI of map: tksmseq_map, tksmseq_map_align, tksmseq_map_extend, tksmseq_map_split and tksmseq_map_targets (include/tksmseq.h).  The host reads and checks (ms_host.cpp's FASTQ reader, map_host.cpp), packs
 // the reads of a chunk and formats the PAF; the sketch of targets and reads, the index, the seeds, the chains and the choice of the lines run
 // on the device (map_kernels.hip, with the radix sort of abundance and the run kernels of model-sequence), and with alignment the anchors of
 // the written chains, their banded alignment and the run-length code of its columns (map_align_kernels.hip), and with extension the X-drop
@@ -15,6 +15,7 @@
 #include "map_host.h"
 #include "map_kernels.h"
 #include "map_split_kernels.h"
+#include "map_targets.h"
 #include "ms_kernels.h"
 #include "tool_run.h"
 
@@ -35,6 +36,16 @@ struct MapAligned { std::vector<tkh::MapAlnOut> outs; std::vector<uint64_t> run_
 // when it did not move
 struct MapExtended { std::vector<tkh::MapExtEnd> ends; std::vector<int64_t> traced; std::vector<tkh::MapAlnOut> outs; std::vector<uint64_t> run_off, runs; };
 
+// what the call maps to: the context's reference, or a target set ("map, annotated targets").  The image and the { voff, len } table on the
+// device; names, lengths and first validity words on the host
+struct MapTargetView {
+    const uint32_t *codes = nullptr, *valid = nullptr;
+    const tk::MapSeq* seqs = nullptr;
+    const std::vector<std::string>* names = nullptr;
+    std::vector<uint64_t> lens, voff;
+    size_t n() const { return lens.size(); }
+};
+
 // the state of one call
 struct MapRun {
     tksmseq_ctx* ctx;
@@ -53,6 +64,11 @@ struct MapRun {
     tksmseq_split_params sp{4, 30, 8, 0};
     tksmseq_split_info sinfo{};
     Events<2> ev;
+    MapTargetView tv;
+    const tksmseq_targets* targets = nullptr;                  // with it tv is its image; without, build_index fills tv from the reference
+    bool genome_coords = false;
+    tksmseq_project_info pinfo{};
+    std::string first_unprojected;
     // the index: distinct hashes with their runs in the sorted entries
     TmpBuf d_tvalid, d_tseq, d_dkey, d_dcount, d_dstart, d_iseq, d_ips;
     uint32_t n_distinct = 0;
@@ -103,26 +119,29 @@ struct MapRun {
 };
 
 int MapRun::build_index() {
-    const size_t n_t = ctx->contigs.size() / 2;
+    const size_t n_t = tv.n();
     std::vector<tkh::MapSeq> tseq(n_t);
     std::vector<tkh::MapTile> tiles;
     for (size_t t = 0; t < n_t; t++) {
-        tseq[t] = {ctx->contigs[2 * t] / 32, (uint32_t)ctx->contigs[2 * t + 1], 0u};
-        tkh::map_add_tiles((uint32_t)t, ctx->contigs[2 * t + 1], (uint32_t)p.k, (uint32_t)p.w, tiles);
+        tseq[t] = {tv.voff[t], (uint32_t)tv.lens[t], 0u};
+        tkh::map_add_tiles((uint32_t)t, tv.lens[t], (uint32_t)p.k, (uint32_t)p.w, tiles);
     }
     const tk::RefView R{ctx->d_packed.as<uint32_t>(), ctx->d_blocktab.as<uint32_t>(), ctx->d_pool.as<uint8_t>(), ctx->d_contigs.as<uint64_t>(), (uint32_t)n_t};
     const uint64_t n_vwords = ctx->total_alloc / 32;
     TmpBuf d_tiles(s), d_hash(s), d_seq(s), d_ps(s);
     auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(ctx, upload(d_tseq, tseq.data(), tseq.size(), s));
-    HIPCHK(ctx, d_tvalid.ensure(std::max<size_t>(n_vwords, 1) * 4));
-    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (!targets) {
+        HIPCHK(ctx, upload(d_tseq, tseq.data(), tseq.size(), s));
+        HIPCHK(ctx, d_tvalid.ensure(std::max<size_t>(n_vwords, 1) * 4));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        tv.codes = R.packed; tv.valid = d_tvalid.as<uint32_t>(); tv.seqs = d_tseq.as<tk::MapSeq>();
+    }
     info.upload_ms += ms_since(t0);
 
     if (int rc = begin()) return rc;
-    HIPCHK(ctx, tk::launch_map_ref_valid(R, n_vwords, d_tvalid.as<uint32_t>(), s));
+    if (!targets) HIPCHK(ctx, tk::launch_map_ref_valid(R, n_vwords, d_tvalid.as<uint32_t>(), s));
     uint64_t n_tm = 0;
-    if (int rc = sketch(R.packed, d_tvalid.as<uint32_t>(), d_tseq.as<tk::MapSeq>(), tiles, d_tiles, d_hash, d_seq, d_ps, n_tm)) return rc;
+    if (int rc = sketch(tv.codes, tv.valid, tv.seqs, tiles, d_tiles, d_hash, d_seq, d_ps, n_tm)) return rc;
     if (int rc = end(ST_SKETCH)) return rc;
     info.target_minimizers = n_tm;
 
@@ -305,7 +324,7 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
         }
         for (uint32_t i = 0; i < n_lines[r]; i++) {
             const uint32_t c = lines[(size_t)r * slots + i];
-            if (c >= nc || chains[c].read != r || (chains[c].tr >> 1) >= ctx->contig_names.size()) { ctx->err = "map: a line of a chain that does not exist"; return TKSMSEQ_EDEVICE; }
+            if (c >= nc || chains[c].read != r || (chains[c].tr >> 1) >= tv.n()) { ctx->err = "map: a line of a chain that does not exist"; return TKSMSEQ_EDEVICE; }
             if (aligned) tkh::map_align_add_line(c, chains[c], segments, col_words, alines);
             line_chain.push_back(c);
         }
@@ -346,7 +365,7 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
             tkh::MapAlnOut joined;
             if (extended) {
                 const tkh::MapExtEnd &le = ex.ends[2 * at], &re = ex.ends[2 * at + 1];
-                if (le.ei > ch.tstart || le.ej > ch.qs || re.ei > ctx->contigs[2 * (size_t)t + 1] - ch.tend || re.ej > h_seqs[r].len - ch.qe) {
+                if (le.ei > ch.tstart || le.ej > ch.qs || re.ei > tv.lens[t] - ch.tend || re.ej > h_seqs[r].len - ch.qe) {
                     ctx->err = "map: an extension left its sequence"; return TKSMSEQ_EDEVICE;
                 }
                 ch = tkh::map_extended_chain(ch, le, re);
@@ -363,11 +382,25 @@ int MapRun::chunk(uint32_t r0, uint32_t r1) {
                 xinfo.antidiagonals += le.steps + re.steps; xinfo.cells += le.cells + re.cells;
                 xinfo.longest = std::max<uint64_t>(xinfo.longest, std::max(le.ei + le.ej, re.ei + re.ej));
             }
+            const size_t line_at = paf.size();
             if (aligned)
-                tkh::map_paf_line_aligned(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], ch, mq, is_p, *ao, runs,
-                                          ap.eqx != 0, paf, tag_n, si);
+                tkh::map_paf_line_aligned(names[r0 + r], h_seqs[r].len, (*tv.names)[t], tv.lens[t], ch, mq, is_p, *ao, runs, ap.eqx != 0, paf, tag_n, si);
             else
-                tkh::map_paf_line(names[r0 + r], h_seqs[r].len, ctx->contig_names[t], ctx->contigs[2 * (size_t)t + 1], ch, mq, is_p, paf, tag_n, si);
+                tkh::map_paf_line(names[r0 + r], h_seqs[r].len, (*tv.names)[t], tv.lens[t], ch, mq, is_p, paf, tag_n, si);
+            if (genome_coords) {
+                pinfo.lines++;
+                if (targets->h.projectable[t] && ch.tend > ch.tstart) {
+                    std::string line = paf.substr(line_at, paf.size() - 1 - line_at);
+                    const uint32_t ci = targets->h.contig[t];
+                    pinfo.junctions += tkh::map_project_line(line, targets->h, t, targets->names[t], targets->contig_names[ci], targets->contig_lens[ci]);
+                    paf.resize(line_at);
+                    paf += line; paf += '\n';
+                    pinfo.projected++;
+                } else {
+                    if (!pinfo.unprojected) first_unprojected = targets->names[t];
+                    pinfo.unprojected++;
+                }
+            }
             info.lines++;
             if (!is_p) info.secondary++;
         }
@@ -425,7 +458,7 @@ int MapRun::align(const std::vector<tkh::MapAlnLine>& lines, uint64_t segments, 
     if (!waves) { if (int rc = end(ainfo.align_ms)) return rc; return over("its traceback store"); }
     const uint32_t tb_stride = longest + 1u;
     HIPCHK(ctx, d_tb.ensure((size_t)waves * tb_stride * tkh::MAP_ALN_TB_BYTES));
-    const tk::MapAlnSeqs Q{ctx->d_packed.as<uint32_t>(), d_tvalid.as<uint32_t>(), d_tseq.as<tk::MapSeq>(), c.d_codes.as<uint32_t>(), c.d_valid.as<uint32_t>(), c.d_seqs.as<tk::MapSeq>()};
+    const tk::MapAlnSeqs Q{tv.codes, tv.valid, tv.seqs, c.d_codes.as<uint32_t>(), c.d_valid.as<uint32_t>(), c.d_seqs.as<tk::MapSeq>()};
     HIPCHK(ctx, tk::launch_map_align(d_lines.as<tk::MapAlnLine>(), nl, c.d_chain.as<tk::MapChain>(), d_path.as<uint64_t>(), Q, (uint32_t)p.k, (uint32_t)ap.band, ap.eqx ? 1u : 0u,
                                      waves, tb_stride, d_tb.as<uint64_t>(), d_cols.as<uint32_t>(), d_out.as<tk::MapAlnOut>(), words + 1, s));
     a.outs.resize(nl);
@@ -473,7 +506,7 @@ int MapRun::extend(const std::vector<uint32_t>& line_chain, bool alone, const st
     HIPCHK(ctx, d_words.ensure(16));                               // flags
     HIPCHK(ctx, hipMemsetAsync(d_words.p, 0, 16, s));
     uint32_t* flags = d_words.as<uint32_t>();
-    const tk::MapAlnSeqs Q{ctx->d_packed.as<uint32_t>(), d_tvalid.as<uint32_t>(), d_tseq.as<tk::MapSeq>(), c.d_codes.as<uint32_t>(), c.d_valid.as<uint32_t>(), c.d_seqs.as<tk::MapSeq>()};
+    const tk::MapAlnSeqs Q{tv.codes, tv.valid, tv.seqs, c.d_codes.as<uint32_t>(), c.d_valid.as<uint32_t>(), c.d_seqs.as<tk::MapSeq>()};
     const tk::MapExtParams P{(uint32_t)xp.band, (uint32_t)xp.drop, (uint32_t)xp.max_ext, aligned && ap.eqx ? 1u : 0u};
     HIPCHK(ctx, tk::launch_map_extend(d_tasks.as<tk::MapExtTask>(), nt, c.d_chain.as<tk::MapChain>(), Q, P, std::min<uint32_t>((nt + 3u) / 4u * 4u, tkh::MAP_ALN_WAVES), d_ends.as<tk::MapExtEnd>(),
                                       flags, s));
@@ -547,11 +580,16 @@ int MapRun::extend(const std::vector<uint32_t>& line_chain, bool alone, const st
 
 }  // namespace
 
-extern "C" int tksmseq_map_split(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const tksmseq_extend_params* extend,
-                                 const tksmseq_split_params* split, const char* reads_paths, const char* paf_out, tksmseq_map_info* info_out, tksmseq_align_info* align_info,
-                                 tksmseq_extend_info* extend_info, tksmseq_split_info* split_info) {
+extern "C" int tksmseq_map_targets(tksmseq_ctx* ctx, const tksmseq_targets* targets, const tksmseq_map_targets_params* tp, const tksmseq_map_params* params,
+                                   const tksmseq_align_params* align, const tksmseq_extend_params* extend, const tksmseq_split_params* split, const char* reads_paths,
+                                   const char* paf_out, tksmseq_map_info* info_out, tksmseq_align_info* align_info, tksmseq_extend_info* extend_info,
+                                   tksmseq_split_info* split_info, tksmseq_project_info* project_info) {
     if (!ctx) return TKSMSEQ_EINVAL;
     if (!reads_paths || !paf_out || !*paf_out) { ctx->err = "map: null argument"; return TKSMSEQ_EINVAL; }
+    const bool genome_coords = tp && tp->genome_coords;
+    if (genome_coords && !targets) { ctx->err = "map: genome_coords needs a target set"; return TKSMSEQ_EINVAL; }
+    if (targets)
+        if (int rc = map_targets_check(ctx, targets)) return rc;
     tksmseq_map_params p{};
     p.k = 15; p.w = 10; p.max_occ = 500; p.max_gap = 5000; p.bandwidth = 500; p.min_count = 3; p.min_score = 40; p.secondary_ratio = 0.8; p.max_secondary = 5;
     if (params) p = *params;
@@ -559,11 +597,13 @@ extern "C" int tksmseq_map_split(tksmseq_ctx* ctx, const tksmseq_map_params* par
     if (align && !tkh::map_check_align(p, *align, ctx->err)) return TKSMSEQ_EINVAL;
     if (extend && !tkh::map_check_extend(*extend, ctx->err)) return TKSMSEQ_EINVAL;
     if (split && !tkh::map_check_split(*split, ctx->err)) return TKSMSEQ_EINVAL;
-    if (ctx->contigs.empty()) { ctx->err = "map: the context has no reference"; return TKSMSEQ_EINVAL; }
-    if (ctx->n_declared) { ctx->err = "map: the reference has contigs that are declared only"; return TKSMSEQ_EINVAL; }
-    if (ctx->contigs.size() / 2 >= MAP_LIMIT) { ctx->err = "map: 2^31 targets or more"; return TKSMSEQ_ELIMIT; }
-    for (size_t t = 0; t < ctx->contigs.size() / 2; t++)
-        if (ctx->contigs[2 * t + 1] >= MAP_LIMIT) { ctx->err = "map: target " + ctx->contig_names[t] + " has 2^31 bases or more"; return TKSMSEQ_ELIMIT; }
+    if (!targets) {
+        if (ctx->contigs.empty()) { ctx->err = "map: the context has no reference"; return TKSMSEQ_EINVAL; }
+        if (ctx->n_declared) { ctx->err = "map: the reference has contigs that are declared only"; return TKSMSEQ_EINVAL; }
+        if (ctx->contigs.size() / 2 >= MAP_LIMIT) { ctx->err = "map: 2^31 targets or more"; return TKSMSEQ_ELIMIT; }
+        for (size_t t = 0; t < ctx->contigs.size() / 2; t++)
+            if (ctx->contigs[2 * t + 1] >= MAP_LIMIT) { ctx->err = "map: target " + ctx->contig_names[t] + " has 2^31 bases or more"; return TKSMSEQ_ELIMIT; }
+    }
 
     // ---- the host reads
     auto t0 = std::chrono::steady_clock::now();
@@ -584,6 +624,17 @@ extern "C" int tksmseq_map_split(tksmseq_ctx* ctx, const tksmseq_map_params* par
     if (extend) { run.extended = true; run.xp = *extend; }
     if (split) { run.split = true; run.sp = *split; }
     run.names = reads.names();
+    MapTargetView& tv = run.tv;
+    if (targets) {                                               // (the limits of a target set were checked when it was made)
+        run.targets = targets; run.genome_coords = genome_coords;
+        tv.codes = targets->d_codes.as<uint32_t>(); tv.valid = targets->d_valid.as<uint32_t>(); tv.seqs = targets->d_seqs.as<tk::MapSeq>();
+        tv.names = &targets->names;
+        tv.lens.assign(targets->h.len.begin(), targets->h.len.end());
+        tv.voff.assign(targets->h.voff.begin(), targets->h.voff.end() - 1);
+    } else {
+        tv.names = &ctx->contig_names;
+        for (size_t t = 0; t < ctx->contigs.size() / 2; t++) { tv.voff.push_back(ctx->contigs[2 * t] / 32); tv.lens.push_back(ctx->contigs[2 * t + 1]); }
+    }
     run.info.reads = n_reads;
     run.info.read_ms = ms_since(t0);
 
@@ -633,7 +684,16 @@ extern "C" int tksmseq_map_split(tksmseq_ctx* ctx, const tksmseq_map_params* par
     if (align_info) *align_info = run.ainfo;
     if (extend_info) *extend_info = run.xinfo;
     if (split_info) *split_info = run.sinfo;
+    if (project_info) *project_info = run.pinfo;
+    // (not an error: the note the module logs, tksmseq_last_error after TKSMSEQ_OK)
+    if (run.pinfo.unprojected) ctx->err = "map: " + std::to_string(run.pinfo.unprojected) + " lines stay in transcript coordinates, the first on " + run.first_unprojected;
     return TKSMSEQ_OK;
+}
+
+extern "C" int tksmseq_map_split(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const tksmseq_extend_params* extend,
+                                 const tksmseq_split_params* split, const char* reads_paths, const char* paf_out, tksmseq_map_info* info_out, tksmseq_align_info* align_info,
+                                 tksmseq_extend_info* extend_info, tksmseq_split_info* split_info) {
+    return tksmseq_map_targets(ctx, nullptr, nullptr, params, align, extend, split, reads_paths, paf_out, info_out, align_info, extend_info, split_info, nullptr);
 }
 
 extern "C" int tksmseq_map_extend(tksmseq_ctx* ctx, const tksmseq_map_params* params, const tksmseq_align_params* align, const tksmseq_extend_params* extend,

@@ -175,4 +175,129 @@ void map_split_ranks(const std::vector<std::pair<uint32_t, uint32_t>>& iv, std::
     for (uint32_t i = 0; i < order.size(); i++) rank[order[i]] = i;
 }
 
+int map_targets_select(const tsb::Transcripts& T, const std::vector<int32_t>& contig_of, const std::vector<uint64_t>& contigs, MapTargets& out, std::string& err) {
+    out = MapTargets();
+    tksmseq_targets_info& info = out.info;
+    info.transcripts = T.n();
+    for (uint64_t t = 0; t < T.n(); t++) {
+        const uint32_t e0 = T.exon_first[t], e1 = T.exon_first[t + 1];
+        bool all_empty = true, unknown = false, bad = false;
+        uint64_t sum = 0;
+        for (uint32_t e = e0; e < e1; e++) {
+            all_empty = all_empty && T.ex_start[e] == T.ex_end[e];
+            const int32_t ci = contig_of[T.ex_contig[e]];
+            if (ci < 0) { unknown = true; continue; }
+            if (T.ex_end[e] < T.ex_start[e] || T.ex_end[e] > contigs[2 * (size_t)ci + 1]) bad = true;
+            else sum += T.ex_end[e] - T.ex_start[e];
+        }
+        if (all_empty) { info.skipped_empty++; continue; }
+        if (unknown) { info.skipped_unknown_contig++; continue; }
+        if (bad) { info.skipped_bad_exon++; continue; }
+        const std::string id(T.id_pool.data() + T.id_off[t], T.id_len[t]);
+        if (out.n() + 1 >= (1ull << 31)) { err = "map: 2^31 targets or more"; return TKSMSEQ_ELIMIT; }
+        if (sum >= (1ull << 31)) { err = "map: target " + id + " has 2^31 letters or more"; return TKSMSEQ_ELIMIT; }
+        if (info.letters + sum >= (1ull << 36)) { err = "map: 2^36 target letters or more"; return TKSMSEQ_ELIMIT; }
+        // the non-empty exons in file order, and whether they walk one strand of one contig without turning back
+        bool proj = true;
+        uint32_t cum = 0;
+        const size_t first = out.exons.size();
+        for (uint32_t e = e0; e < e1; e++) {
+            const uint32_t s = T.ex_start[e], en = T.ex_end[e], minus = T.ex_minus[e] ? 1u : 0u;
+            if (s == en) continue;
+            const uint32_t ci = (uint32_t)contig_of[T.ex_contig[e]];
+            if (out.exons.size() > first) {
+                const size_t prev = out.exons.size() - 1;
+                proj = proj && ci == out.contig.back() && minus == out.minus.back() && (minus ? en <= out.ex_start[prev] : s >= out.ex_end[prev]);
+            } else {
+                out.contig.push_back(ci);
+                out.minus.push_back((uint8_t)minus);
+            }
+            out.exons.push_back({contigs[2 * (size_t)ci] + s, cum, (en - s) | minus << 31});
+            out.ex_start.push_back(s);
+            out.ex_end.push_back(en);
+            cum += en - s;
+        }
+        out.tx.push_back((uint32_t)t);
+        out.len.push_back((uint32_t)sum);
+        out.projectable.push_back(proj ? 1 : 0);
+        out.voff.push_back(out.voff.back() + (sum + 31) / 32);
+        out.efirst.push_back(out.exons.size());
+        info.letters += sum;
+        info.projectable += proj;
+    }
+    info.targets = out.n();
+    info.exons = out.exons.size();
+    info.image_vwords = out.voff.back();
+    if (!out.n()) { err = "map: no transcript of the table can be a target"; return TKSMSEQ_EINVAL; }
+    return TKSMSEQ_OK;
+}
+
+void map_targets_fasta(const MapTargets& T, const std::vector<std::string>& names, const uint32_t* codes, const uint32_t* valid, int32_t line_width, std::string& out) {
+    for (size_t t = 0; t < T.n(); t++) {
+        out += '>'; out += names[t]; out += '\n';
+        const uint32_t *c = codes + 2 * T.voff[t], *v = valid + T.voff[t];
+        const uint32_t len = T.len[t], width = line_width > 0 ? (uint32_t)line_width : len;
+        for (uint32_t j = 0; j < len; j++) {
+            out += (v[j >> 5] >> (j & 31u)) & 1u ? "ACGT"[(c[j >> 4] >> (2u * (j & 15u))) & 3u] : 'N';
+            if ((j + 1) % width == 0 && j + 1 < len) out += '\n';
+        }
+        out += '\n';
+    }
+}
+
+uint64_t map_project_line(std::string& line, const MapTargets& T, uint32_t t, const std::string& tx_name, const std::string& contig_name, uint64_t contig_len) {
+    std::vector<std::string> f;
+    for (size_t at = 0;;) {
+        const size_t tab = line.find('\t', at);
+        f.push_back(line.substr(at, tab == std::string::npos ? std::string::npos : tab - at));
+        if (tab == std::string::npos) break;
+        at = tab + 1;
+    }
+    const uint64_t a = std::stoull(f[7]), b = std::stoull(f[8]);
+    const bool minus = T.minus[t] != 0, rel = f[4] == "-";
+    const size_t e0 = (size_t)T.efirst[t], e1 = (size_t)T.efirst[t + 1];
+    auto exon_len = [&](size_t e) { return (uint64_t)(T.exons[e].len_minus & 0x7FFFFFFFu); };
+    auto exon_of = [&](uint64_t x) { size_t e = e0; while (e + 1 < e1 && T.exons[e + 1].cum <= x) e++; return e; };
+    auto G = [&](uint64_t x) { const size_t e = exon_of(x); const uint64_t o = x - T.exons[e].cum; return minus ? T.ex_end[e] - 1 - o : T.ex_start[e] + o; };
+    const size_t ea = exon_of(a), eb = exon_of(b - 1);
+    uint64_t junctions = eb - ea;
+    f[4] = rel != minus ? "-" : "+";
+    f[5] = contig_name;
+    f[6] = std::to_string(contig_len);
+    f[7] = std::to_string(minus ? G(b - 1) : G(a));
+    f[8] = std::to_string((minus ? G(a) : G(b - 1)) + 1);
+    for (size_t i = 12; i < f.size(); i++) {
+        if (f[i].compare(0, 5, "cg:Z:") != 0) continue;
+        std::vector<std::pair<uint64_t, char>> runs;
+        auto add = [&](uint64_t n, char op) { if (!runs.empty() && runs.back().second == op) runs.back().first += n; else runs.emplace_back(n, op); };
+        uint64_t x = a;
+        size_t e = ea;
+        junctions = 0;
+        for (size_t at = 5; at < f[i].size();) {
+            uint64_t n = 0;
+            while (at < f[i].size() && f[i][at] >= '0' && f[i][at] <= '9') n = n * 10 + (uint64_t)(f[i][at++] - '0');
+            const char op = f[i][at++];
+            if (op == 'I') { add(n, op); continue; }
+            while (n) {
+                if (x == T.exons[e].cum + exon_len(e) && e + 1 < e1) {      // the next exon's first target-consuming column
+                    const uint64_t gap = minus ? T.ex_start[e] - T.ex_end[e + 1] : T.ex_start[e + 1] - T.ex_end[e];
+                    if (gap) { add(gap, 'N'); junctions++; }
+                    e++;
+                }
+                uint64_t take = std::min<uint64_t>(n, T.exons[e].cum + exon_len(e) - x);
+                if (!take) take = n;                                       // (columns behind the target's end: none in a line of this build)
+                add(take, op);
+                x += take; n -= take;
+            }
+        }
+        if (minus) std::reverse(runs.begin(), runs.end());
+        f[i] = "cg:Z:";
+        for (const auto& r : runs) { f[i] += std::to_string(r.first); f[i] += r.second; }
+    }
+    f.push_back("tx:Z:" + tx_name);
+    line.clear();
+    for (size_t i = 0; i < f.size(); i++) { if (i) line += '\t'; line += f[i]; }
+    return junctions;
+}
+
 }  // namespace tkh

@@ -9,6 +9,7 @@
 
 #include "../../include/tksmseq.h"
 #include "ms_host.h"
+#include "tsb_host.h"
 
 namespace tkh {
 
@@ -96,5 +97,33 @@ bool map_check_split(const tksmseq_split_params& s, std::string& err);
 uint64_t map_split_anchor_bytes(const tksmseq_split_params& s, int32_t min_count);
 // rank[i] = the 0-based rank of tp:A:P line i of a read by (qstart, qend, i); iv[i] = {qstart, qend} in original read coordinates
 void map_split_ranks(const std::vector<std::pair<uint32_t, uint32_t>>& iv, std::vector<uint32_t>& rank);
+
+// ---- map -g ("map, annotated targets" in include/tksmseq.h; the kernel is described in map_targets_kernels.h)
+// an exon as the splice kernel reads it: g = its first letter in the genome's global coordinate, cum = the letters of its target before it,
+// len_minus = its letters | strand << 31.  Empty exons are not in the list: every tuple has at least one letter
+struct MapTargetExon { uint64_t g; uint32_t cum, len_minus; };
+// the kept transcripts of a table: target t is transcript tx[t], len[t] letters from validity word voff[t], exons [efirst[t], efirst[t + 1])
+// of `exons` (the device tuples) and of ex_start / ex_end (their genomic intervals, for the projection); contig[t], minus[t]: of a
+// projectable target
+struct MapTargets {
+    tksmseq_targets_info info{};
+    std::vector<uint32_t> tx, len, contig;
+    std::vector<uint64_t> voff{0}, efirst{0};
+    std::vector<MapTargetExon> exons;
+    std::vector<uint32_t> ex_start, ex_end;
+    std::vector<uint8_t> minus, projectable;
+    size_t n() const { return tx.size(); }
+};
+// the walk over the table in table order ("Which transcripts become targets").  contig_of[i]: the reference's contig for the table's contig
+// name i, or -1 (unknown, or declared only); contigs: the reference's {gstart, len} pairs.  TKSMSEQ_OK, or TKSMSEQ_ELIMIT / TKSMSEQ_EINVAL
+// with err
+int map_targets_select(const tsb::Transcripts& T, const std::vector<int32_t>& contig_of, const std::vector<uint64_t>& contigs, MapTargets& out, std::string& err);
+// the FASTA of the downloaded image: ">name\n", the letters (N where the validity bit is clear) wrapped at line_width (0: one line)
+void map_targets_fasta(const MapTargets& T, const std::vector<std::string>& names, const uint32_t* codes, const uint32_t* valid, int32_t line_width, std::string& out);
+
+// ---- map --genome-coords: the projection of a written line ("map, annotated targets": "Projection")
+// line: one PAF line of target t without its '\n'; T.projectable[t].  Replaces columns 5 to 9 and the cg:Z: tag and appends tx:Z:;
+// returns the N runs written, or without a cg:Z: tag the exon boundaries [tstart, tend) crosses
+uint64_t map_project_line(std::string& line, const MapTargets& T, uint32_t t, const std::string& tx_name, const std::string& contig_name, uint64_t contig_len);
 
 }  // namespace tkh

@@ -337,17 +337,21 @@ extern "C" int tksmseq_map_main(int argc, char** argv) {
     tksmseq_split_params sp{4, 30, 8, 0};
     bool align = false, band_given = false, extend = false, split = false;
     std::string ext_given, split_given;                         // the first --ext-* and the first --split-* option seen
-    std::string reference, reads;
+    std::string reference, reads, gtfs, targets_out;
+    bool genome_coords = false;
     Ranges ranges;
     if (!parse_args(argc, argv, c, [&](const std::string& o, const char* v) -> int {
             if (among(o, NO_INPUT_SEED)) return NO_SUCH;
             if (o == "-c") { align = true; return TOOK_FLAG; }
+            if (o == "--genome-coords") { genome_coords = true; return TOOK_FLAG; }
             if (o == "--eqx") { ap.eqx = 1; return TOOK_FLAG; }
             if (o == "--extend") { extend = true; return TOOK_FLAG; }
             if (o == "--split") { split = true; return TOOK_FLAG; }
             long long iv = 0;
             if ((o == "-r" || o == "--reference") && v) reference = v;
             else if (o == "--reads" && v) reads = v;
+            else if ((o == "-g" || o == "--gtf") && v) gtfs = v;
+            else if (o == "--targets-out" && v) targets_out = v;
             else if (o == "--align-band" && v) { if (!ranges.check(o, v, 1, 63, "must be between 1 and 63", iv)) return MALFORMED; ap.band = (int32_t)iv; band_given = true; }
             else if (o == "--ext-band" && v) { if (!ranges.check(o, v, 1, 63, "must be between 1 and 63", iv)) return MALFORMED; xp.band = (int32_t)iv; if (ext_given.empty()) ext_given = o; }
             else if (o == "--ext-drop" && v) { if (!ranges.check(o, v, 1, 1000, "must be between 1 and 1000", iv)) return MALFORMED; xp.drop = (int32_t)iv; if (ext_given.empty()) ext_given = o; }
@@ -373,12 +377,19 @@ extern "C" int tksmseq_map_main(int argc, char** argv) {
         })) return 2;
     if (c.help) { printf("Maps long reads to transcripts by chains of minimizers; with -c the written chains are aligned base by base (cg:Z: and NM:i: tags);\n"
                          "with --extend both ends of every line are extended to where an X-drop alignment carries them; with --split every further piece of a\n"
-                         "chimeric or hairpin read gets a supplementary tp:A:P line (sn:i: and si:i: tags).\n"
-                         "usage: map -r REF.fa[.gz][,REF2.fa] --reads F.fq[.gz][,MORE] -o OUT.paf[.gz] [-k 15] [-w 10] [--max-occ 500] [--max-gap 5000] [--bandwidth 500]\n"
+                         "chimeric or hairpin read gets a supplementary tp:A:P line (sn:i: and si:i: tags).  With -g the reference is the genome and the reads\n"
+                         "are mapped to the transcripts of the GTFs, spliced on the device; --targets-out writes them as a FASTA, --genome-coords writes the\n"
+                         "lines in genome coordinates (N runs in cg:Z:, tx:Z: tag).\n"
+                         "usage: map -r REF.fa[.gz][,REF2.fa] [-g GTF[,GTF...] [--genome-coords] [--targets-out CDNA.fa[.gz]]] --reads F.fq[.gz][,MORE] -o OUT.paf[.gz] [-k 15] [-w 10] [--max-occ 500] [--max-gap 5000] [--bandwidth 500]\n"
                          "           [--min-count 3] [--min-score 40] [-p 0.8] [-N 5] [-c [--eqx] [--align-band 63]] [--extend [--ext-band 31] [--ext-drop 40] [--ext-max 2000]]\n"
                          "           [--split [--split-chains 4] [--split-overlap 30] [--split-segments 8]] [--chunk-reads N] [--devices D] [--verbosity V] [--log-file L]\n"
                          "the output is the file `tksm abundance -p` and `tksm model-truncation -i` read; with -c also the one `tksm model-sequence --alignment` reads\n"); return 0; }
-    if (!have_required("map", {{reference, "-r/--reference"}, {reads, "--reads"}, {c.output, "-o/--output"}})) return 2;
+    // with -g --targets-out the FASTA may be the only output
+    const bool fasta_only = !gtfs.empty() && !targets_out.empty() && reads.empty() && c.output.empty();
+    if (fasta_only ? !have_required("map", {{reference, "-r/--reference"}}) : !have_required("map", {{reference, "-r/--reference"}, {reads, "--reads"}, {c.output, "-o/--output"}}))
+        return 2;
+    if (gtfs.empty() && (genome_coords || !targets_out.empty())) { fprintf(stderr, "map: error: %s needs -g\n", genome_coords ? "--genome-coords" : "--targets-out"); return 2; }
+    if (fasta_only && genome_coords) { fprintf(stderr, "map: error: --genome-coords needs --reads and -o\n"); return 2; }
     if (!ranges.error.empty()) { fprintf(stderr, "map: error: %s\n", ranges.error.c_str()); return 2; }
     if (!align && (ap.eqx || band_given)) { fprintf(stderr, "map: error: %s needs -c\n", ap.eqx ? "--eqx" : "--align-band"); return 2; }
     if (!extend && !ext_given.empty()) { fprintf(stderr, "map: error: %s needs --extend\n", ext_given.c_str()); return 2; }
@@ -390,10 +401,47 @@ extern "C" int tksmseq_map_main(int argc, char** argv) {
     tksmseq_align_info ainfo{};
     tksmseq_extend_info xinfo{};
     tksmseq_split_info sinfo{};
+    tksmseq_targets_info tinfo{};
+    tksmseq_project_info pinfo{};
+    std::string unprojected_note;
     return with_context(c, [&](tksmseq_ctx* ctx) {
         if (int rc = load_references(ctx, reference, log)) return rc;
-        return tksmseq_map_split(ctx, &p, align ? &ap : nullptr, extend ? &xp : nullptr, split ? &sp : nullptr, reads.c_str(), c.output.c_str(), &info, &ainfo, &xinfo, &sinfo);
+        if (gtfs.empty())
+            return tksmseq_map_split(ctx, &p, align ? &ap : nullptr, extend ? &xp : nullptr, split ? &sp : nullptr, reads.c_str(), c.output.c_str(), &info, &ainfo, &xinfo, &sinfo);
+        for (size_t a = 0; a <= gtfs.size();) {
+            size_t b = gtfs.find(',', a);
+            if (b == std::string::npos) b = gtfs.size();
+            if (b > a) {
+                log.log(Logger::INFO, "Reading %s", gtfs.substr(a, b - a).c_str());
+                if (int rc = tksmseq_transcripts_add_gtf(ctx, gtfs.substr(a, b - a).c_str(), 0)) return rc;
+            }
+            a = b + 1;
+        }
+        tksmseq_targets* targets = nullptr;
+        int rc = tksmseq_targets_from_transcripts(ctx, &targets, &tinfo);
+        if (!rc && !targets_out.empty()) rc = tksmseq_targets_write_fasta(ctx, targets, targets_out.c_str(), 60);
+        if (!rc && !fasta_only) {
+            const tksmseq_map_targets_params tp{genome_coords ? 1 : 0, 0};
+            rc = tksmseq_map_targets(ctx, targets, &tp, &p, align ? &ap : nullptr, extend ? &xp : nullptr, split ? &sp : nullptr, reads.c_str(), c.output.c_str(), &info, &ainfo,
+                                     &xinfo, &sinfo, &pinfo);
+            if (!rc && pinfo.unprojected) unprojected_note = tksmseq_last_error(ctx);
+        }
+        tksmseq_targets_free(ctx, targets);
+        return rc;
     }, [&](Clock::time_point t0) {
+        if (!gtfs.empty()) {
+            log.log(Logger::INFO, "map: %llu transcripts: %llu targets of %llu letters in %llu exons (%llu projectable); skipped: %llu empty, %llu on unknown contigs, %llu with a bad exon; "
+                    "spliced in %.3f ms on the device%s%s",
+                    (unsigned long long)tinfo.transcripts, (unsigned long long)tinfo.targets, (unsigned long long)tinfo.letters, (unsigned long long)tinfo.exons,
+                    (unsigned long long)tinfo.projectable, (unsigned long long)tinfo.skipped_empty, (unsigned long long)tinfo.skipped_unknown_contig,
+                    (unsigned long long)tinfo.skipped_bad_exon, tinfo.splice_ms, targets_out.empty() ? "" : ", written to ", targets_out.c_str());
+            if (fasta_only) return 0;
+        }
+        if (genome_coords) {
+            log.log(Logger::INFO, "map: %llu lines: %llu projected to the genome over %llu junctions, %llu left in transcript coordinates", (unsigned long long)pinfo.lines,
+                    (unsigned long long)pinfo.projected, (unsigned long long)pinfo.junctions, (unsigned long long)pinfo.unprojected);
+            if (!unprojected_note.empty()) log.log(Logger::INFO, "%s", unprojected_note.c_str());
+        }
         log.log(Logger::INFO, "map: %llu target minimizers under %llu hashes (%llu over --max-occ); %llu read minimizers, %llu anchors, %llu groups, %llu chained",
                 (unsigned long long)info.target_minimizers, (unsigned long long)info.distinct_hashes, (unsigned long long)info.dropped_hashes,
                 (unsigned long long)info.read_minimizers, (unsigned long long)info.anchors, (unsigned long long)info.groups, (unsigned long long)info.chained_groups);

@@ -134,6 +134,47 @@ class TranscribePlan:
             pass
 
 
+class Targets:
+    """The transcripts of the Sequencer's table spliced from its reference on the device (tksmseq_targets_from_transcripts; the rules in
+    include/tksmseq.h, "map, annotated targets"): .info the counters of tksmseq_targets_info, .names, .lengths, .voff and .projectable per
+    target.  Pass it to Sequencer.map(targets=...).  Stale once the reference or the transcript table of the Sequencer changes; free it
+    before the Sequencer is closed."""
+
+    def __init__(self, seq, handle, info):
+        self._seq, self._h = seq, handle
+        self.info = {n: getattr(info, n) for n, _ in L.TargetsInfo._fields_ if n != "reserved"}
+        self.names, self.lengths, self.voff, self.projectable = [], [], [], []
+        name, ln, voff, proj = C.c_char_p(), C.c_uint32(), C.c_uint64(), C.c_int32()
+        for t in range(info.targets):
+            seq._lib.tksmseq_targets_get(handle, t, C.byref(name), C.byref(ln), C.byref(voff), C.byref(proj))
+            self.names.append(name.value.decode())
+            self.lengths.append(ln.value)
+            self.voff.append(voff.value)
+            self.projectable.append(bool(proj.value))
+
+    def download(self):
+        """(codes, valid): the image as uint32 arrays of 2 * image_vwords and image_vwords words"""
+        n = self.info["image_vwords"]
+        codes, valid = np.empty(2 * n, np.uint32), np.empty(n, np.uint32)
+        self._seq._chk(self._seq._lib.tksmseq_targets_download(self._seq._ctx, self._h, codes.ctypes.data, valid.ctypes.data))
+        return codes, valid
+
+    def write_fasta(self, path, line_width=60):
+        """the targets as a FASTA (.gz: compressed on the host), N for a letter outside ACGT; line_width 0: one line a target"""
+        self._seq._chk(self._seq._lib.tksmseq_targets_write_fasta(self._seq._ctx, self._h, str(path).encode(), int(line_width)))
+
+    def free(self):
+        if self._h:
+            self._seq._lib.tksmseq_targets_free(self._seq._ctx, self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Variants:
     """A variant table in its normal form (tksmseq_variants_load): .rows lines read, of which .snvs, .insertions and .deletions; the
     deletions' union is .deleted_ranges disjoint ranges, and .dropped_points SNVs / insertions lie inside one.  Host only; may be used
@@ -607,7 +648,7 @@ class Sequencer:
 
     def map(self, reads, paf_out, k=15, w=10, max_occ=500, max_gap=5000, bandwidth=500, min_count=3, min_score=40, secondary_ratio=0.8, max_secondary=5,
             chunk_reads=0, align=False, eqx=False, align_band=63, extend=False, ext_band=31, ext_drop=40, ext_max=2000, split=False, split_chains=4,
-            split_overlap=30, split_segments=8):
+            split_overlap=30, split_segments=8, targets=None, genome_coords=False):
         """Long reads to the contigs of this context's reference (a cDNA FASTA) by minimizer chains on the device (tksmseq_map, the rules in
         include/tksmseq.h): `reads` (one FASTQ path or a list of them, .gz or plain) -> `paf_out`, the PAF `abundance(paf=...)` and
         `model_truncation` read.  align=True (map -c) aligns the written chains base by base (tksmseq_map_align): the lines gain NM:i: and cg:Z:
@@ -617,7 +658,12 @@ class Sequencer:
         to split_chains rounds and writes a supplementary tp:A:P line for every further piece of a chimeric or hairpin read, at most
         split_segments tp:A:P lines a read, their read intervals sharing at most split_overlap letters.  Returns the counters of
         tksmseq_map_info as a dict, with align=True also those of tksmseq_align_info under "align", with extend=True those of
-        tksmseq_extend_info under "extend", with split=True those of tksmseq_split_info under "split"."""
+        tksmseq_extend_info under "extend", with split=True those of tksmseq_split_info under "split".  targets=self.targets() maps to the
+        transcripts spliced from genome + GTF instead of the reference's contigs (tksmseq_map_targets); genome_coords=True then writes the
+        lines of projectable targets in genome coordinates (N runs in cg:Z:, a tx:Z: tag) and adds the counters of tksmseq_project_info
+        under "project"."""
+        if genome_coords and targets is None:
+            raise ValueError("genome_coords needs targets=")
         if not align and (eqx or align_band != 63):
             raise ValueError("eqx and align_band need align=True")
         if not extend and (ext_band != 31 or ext_drop != 40 or ext_max != 2000):
@@ -630,8 +676,15 @@ class Sequencer:
                         int(chunk_reads))
         info = L.MapInfo()
         paths = ",".join(str(r) for r in reads).encode()
-        ainfo, xinfo, sinfo = L.AlignInfo(), L.ExtendInfo(), L.SplitInfo()
-        if split:
+        ainfo, xinfo, sinfo, pinfo = L.AlignInfo(), L.ExtendInfo(), L.SplitInfo(), L.ProjectInfo()
+        if targets is not None:
+            ap, xp = L.AlignParams(int(align_band), 1 if eqx else 0), L.ExtendParams(int(ext_band), int(ext_drop), int(ext_max), 0)
+            sp = L.SplitParams(int(split_chains), int(split_overlap), int(split_segments), 0)
+            tp = L.MapTargetsParams(1 if genome_coords else 0, 0)
+            self._chk(self._lib.tksmseq_map_targets(self._ctx, targets._h, C.byref(tp), C.byref(p), C.byref(ap) if align else None, C.byref(xp) if extend else None,
+                                                    C.byref(sp) if split else None, paths, str(paf_out).encode(), C.byref(info), C.byref(ainfo), C.byref(xinfo),
+                                                    C.byref(sinfo), C.byref(pinfo)))
+        elif split:
             ap, xp = L.AlignParams(int(align_band), 1 if eqx else 0), L.ExtendParams(int(ext_band), int(ext_drop), int(ext_max), 0)
             sp = L.SplitParams(int(split_chains), int(split_overlap), int(split_segments), 0)
             self._chk(self._lib.tksmseq_map_split(self._ctx, C.byref(p), C.byref(ap) if align else None, C.byref(xp) if extend else None, C.byref(sp), paths,
@@ -653,7 +706,15 @@ class Sequencer:
             out["extend"] = {n: getattr(xinfo, n) for n, _ in L.ExtendInfo._fields_ if n != "reserved"}
         if split:
             out["split"] = {n: getattr(sinfo, n) for n, _ in L.SplitInfo._fields_ if n != "reserved"}
+        if targets is not None:
+            out["project"] = {n: getattr(pinfo, n) for n, _ in L.ProjectInfo._fields_}
         return out
+
+    def targets(self):
+        """The transcripts of the table (add_gtf) spliced from this context's reference (the genome) on the device: a Targets."""
+        h, info = C.c_void_p(), L.TargetsInfo()
+        self._chk(self._lib.tksmseq_targets_from_transcripts(self._ctx, C.byref(h), C.byref(info)))
+        return Targets(self, h, info)
 
     # ---- random-wgs: whole-genome fragments made on the device
     def wgs(self, dist, a, b=0, base_count=None, depth=None, seed=42, first_candidate=0, n_candidates=1 << 20, state=None):
