@@ -2262,17 +2262,22 @@ DEV AlnResF aln_fused(const AlnJobF& J, uint4* trl, int tg, int cl, uint32_t ls,
     bool bad = false;
     // ---- slot codes: 16 slots (32 bytes) at a time, the next 16 in flight
     struct __attribute__((packed, aligned(4))) U4b { uint32_t x, y, z, w; };
-    uint32_t cw[8], cwn[8];
-    auto load_codes = [&](int s, uint32_t (&d)[8]) {
+    // (14 stored rows: no second full set of registers for the 16 in flight.  The next pass's 32 bytes are fetched after iteration 7,
+    // half a pass ahead of their first use: the first 16 into the half of `cw` the pass has just used up, the second into four
+    // registers beside it.  Both fetches in one place, as before: the second is answered by the cache line the first brought in --
+    // eight iterations apart it went to L2 again, and in the q-score round, whose codes are cold, to memory: +30 % L2 misses)
+    constexpr bool CW_IN_PLACE = ROWS == 14;
+    uint32_t cw[8], cwn[CW_IN_PLACE ? 4 : 8];
+    auto load_half = [&](int s, int h, uint32_t* d) {             // half h of the 16 slots from s
         const int src = (s <= n + skip) ? base + s : base;        // (lanes past their window re-read its start)
-        const U4b* cp = reinterpret_cast<const U4b*>(J.nb + src);
-        const U4b c0 = cp[0], c1 = cp[1];
-        d[0] = c0.x; d[1] = c0.y; d[2] = c0.z; d[3] = c0.w; d[4] = c1.x; d[5] = c1.y; d[6] = c1.z; d[7] = c1.w;
+        const U4b c = reinterpret_cast<const U4b*>(J.nb + src)[h];
+        d[0] = c.x; d[1] = c.y; d[2] = c.z; d[3] = c.w;
     };
+    auto load_codes = [&](int s, uint32_t* d) { load_half(s, 0, d); load_half(s, 1, d + 4); };
     load_codes(0, cw);
     constexpr int HS = 16;                                        // slots (iterations) per pass of the loop below
     constexpr int LPH = HS / NC;                                  // lines of codes per pass
-    uint32_t tw[16], shw[4] = {0u, 0u, 0u, 0u};
+    uint32_t tw[ROWS == 14 ? 4 : 16], shw[4] = {0u, 0u, 0u, 0u};
     int ql = 0;                                                   // lines written (wave-uniform)
     bool ovf = false;
     int s0 = 0;
@@ -2281,7 +2286,7 @@ DEV AlnResF aln_fused(const AlnJobF& J, uint4* trl, int tg, int cl, uint32_t ls,
         const bool drain = __ballot(npend > (more ? BACKLOG_DRAIN : 0)) != 0ull;
         if (!more && !drain) break;
         if (ql + LPH > (ROWS == 64 ? cl : tg - 1)) { ovf = true; break; }             // the job's lines are used up (drain passes of an insertion-heavy window)
-        if (!drain) load_codes(s0 + HS, cwn);
+        if (!CW_IN_PLACE && !drain) load_codes(s0 + HS, cwn);
         const int inc = drain ? 0 : 1;
         // (idle lanes write the job's spare line: with the lines of fewer than 64 jobs interleaved -- the full-width pool -- theirs
         // are another lane's)
@@ -2380,13 +2385,12 @@ DEV AlnResF aln_fused(const AlnJobF& J, uint4* trl, int tg, int cl, uint32_t ls,
                 }
             }
             if constexpr (ROWS == 14) {
-                tw[q & 7] = ent0;
-                if ((q & 7) == 7) {                               // half a line at a time
-                    // (the four 16-byte pieces of a lane's line lie 64 pieces apart -- [wave][line][piece][lane] --: one store instruction
-                    // of the wave writes 1 KB of consecutive bytes, whole cache lines, instead of a quarter of each of 64 lines)
-                    uint4* d = dl + 128 * (q >> 3);
-                    d[0] = make_uint4(tw[0], tw[1], tw[2], tw[3]); d[64] = make_uint4(tw[4], tw[5], tw[6], tw[7]);
-                }
+                tw[q & 3] = ent0;
+                // a 16-byte piece at a time, as soon as its four entries exist
+                // (the four pieces of a lane's line lie 64 pieces apart -- [wave][line][piece][lane] --: one store instruction
+                // of the wave writes 1 KB of consecutive bytes, whole cache lines, instead of a quarter of each of 64 lines)
+                if ((q & 3) == 3) dl[64 * (q >> 2)] = make_uint4(tw[0], tw[1], tw[2], tw[3]);
+                if (CW_IN_PLACE && q == 7 && !drain) { load_half(s0 + HS, 0, cw); load_half(s0 + HS, 1, cwn); }
             } else {
                 tw[4 * (q & 3)] = ent0; tw[4 * (q & 3) + 1] = ent1; tw[4 * (q & 3) + 2] = ent2; tw[4 * (q & 3) + 3] = ent3;
                 shw[q >> 2] = (q & 3) == 0 ? shb : shw[q >> 2] | (shb << (8 * (q & 3)));
@@ -2423,7 +2427,7 @@ DEV AlnResF aln_fused(const AlnJobF& J, uint4* trl, int tg, int cl, uint32_t ls,
                 }
             }
 #pragma unroll
-            for (int i2 = 0; i2 < 8; i2++) cw[i2] = cwn[i2];
+            for (int i2 = 0; i2 < (CW_IN_PLACE ? 4 : 8); i2++) cw[(CW_IN_PLACE ? 4 : 0) + i2] = cwn[i2];
             s0 += HS;
         }
     }
@@ -2568,8 +2572,9 @@ DEV void store_result_f(const FastBuffers& FB, uint32_t r, const AlnResF& R) {
 // path left them (counters[CNT_REDO_LIST] of them in redo_list) with all 64 rows, lines in the full-width pool: a fixed grid whose waves loop over
 // the list.  Rounds with few jobs are bound by the latency of one lane's pass: all their jobs go straight to the 64-row version
 // (LIST false; counters[CNT_FULL_ROWS] allocates pool lines per wave).
-// (register budget: the 14-row pass needs ~131 vector registers -- 3 waves per SIMD; forced into 128 it spills, and a spill inside
-// the pop's divergent region cost correct results once: never again below its natural size)
+// (register budget: the 14-row pass takes 108 / 110 vector registers by its source alone -- 4 waves per SIMD, and at no more than 112 the
+// 64 registers they leave hold a wave of k_err, k_emit or k_loopw of another context: the build gates it, DESIGN.md section 4.1.  Forced
+// below its natural size it spills, and a spill inside the pop's divergent region cost correct results once: never a forced count)
 constexpr int ALNF_WAVES = 4;
 constexpr int LONG_QJOB = 3000;         // slots; q-score jobs above it skip the 14-row pass
 #ifdef TKSM_ALNF_NUM_VGPR                                        // (diagnostic builds of tools/spill_probe.sh: a register cap without a change of occupancy)
